@@ -14,7 +14,13 @@ kernel matrix, the factor and the solves are rebuilt, and the one thing the libr
 a data tensor between calls -- the NaN scan of ``y`` (``matrix.any_missing``) -- is forgotten at the
 start of every step, so each step pays for its scan like a first call.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense_f64|sum_f32|batched_f32|sparse_f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense_f64|sum_f32|batched_f32|sparse_f32] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, runs W untimed and K timed steps, and prints the line: ``value`` (steps per second, or GPs per second for the
+batched workload) and ``ms_per_step`` come from the K timed steps alone.  ``--dump-outputs DIR`` writes what the last timed step
+returned (``logpdf``, ``mean``, ``var``; ``logpdf`` of the batched workload; ``elbo`` of the sparse one) as ``DIR/<name>.npy`` in the
+workload's precision; the inputs are seeded, so two builds given the same arguments can be compared output for output.
 
 ``--gpus N`` with N > 1: one process per GPU.  Either the driver launches this file under
 ``python -m torch.distributed.run --nproc-per-node N ...`` (RANK / WORLD_SIZE in the environment), or --
@@ -23,11 +29,13 @@ port) and passes the one JSON line through.  The dense workload does not shard (
 factorisation), so every rank runs an independent replica ("replicas only"); the batched configuration
 (BASELINE.json configs[3]: 512 independent GPs, the one north_star scales over GPUs) shards its GPs over
 the ranks and all-gathers the log-densities (stheno_amd/dist.py): it is the headline of
-``--workload batched_f32`` and rides along as the ``batched`` sub-record of every other workload's line.
+``--workload batched_f32`` and rides along as the ``batched`` sub-record of every other workload's ``--full`` line.
 ``--dry-run-dist`` proves the launch / rendezvous / collective / reporting path on a GPU-less box (gloo,
 a stand-in step that does no GP arithmetic; the line says ``"dry_run": true``).
 
-Rank 0 prints ONE JSON line.  ``roofline`` is the dominant kernel -- the MFMA GEMM variant with the
+Rank 0 prints ONE JSON line.  What takes runs or host time of its own comes with ``--full`` only (``"full": true`` in the line):
+``other_call_order``, ``roofline``, the measured peak, ``allgather_us``, the ``batched`` sub-record and ``cpu_baseline``; a plain
+run's line has ``roofline`` and ``cpu_baseline`` null.  ``roofline`` is the dominant kernel -- the MFMA GEMM variant with the
 largest summed duration in a step; for the dense workloads that is the persistent two-segment
 trailing update of the look-ahead Cholesky, ``gemm_persist_kernel<double, 128, false>`` --:
 algorithmic flops of its launches in one step / their summed duration, measured with HIP
@@ -192,6 +200,41 @@ def measured_peak(dtype, min_ms=60.0):
     best["what"] = ("gpk_mfma_peak: 256 threads x waves_per_simd per CU, 8 independent accumulators per wave, v_mfma_%s_16x16x4 on pseudo-random "
                     "operands, no memory traffic, >= %.0f ms of device time" % ("f32" if dtype == "f32" else "f64", min_ms))
     return best
+
+
+def dominant_kernel_roofline(name, w, step, prof_steps=2):
+    """Live roofline of the dominant kernel (``--full``): extra untimed steps under HIP-event hooks, every GEMM kernel variant's
+    summed time, the one with the most time priced against the nominal peak."""
+    import ctypes
+
+    lib = _native.load()
+    lib.gpk_prof_start()
+    for _ in range(prof_steps):
+        keep = step()
+    torch.cuda.synchronize()
+    del keep
+    ms, nl, fl = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+    best = None
+    for code in range(PROF_CODES):    # every GEMM kernel variant: the dominant one is the one with the most time
+        lib.gpk_prof_stop(code, ctypes.byref(ms), ctypes.byref(nl), ctypes.byref(fl))
+        if nl.value > 0 and (best is None or ms.value > best[1]):
+            best = (code, ms.value, nl.value, fl.value)
+    if best is None or best[1] <= 0:
+        return None
+    peak = PEAK_TFLOPS[w["dtype"]]
+    code, tms, launches, flops = best
+    achieved = flops / (tms * 1e-3) / 1e12
+    kname = _variant_name(code, w["dtype"])
+    return {
+        "kernel": kname,
+        "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+        "traffic": pmc_traffic(name, w, kname)[0],
+        "traffic_source": pmc_traffic(name, w, kname)[1],
+        "launches_per_step": launches // prof_steps,
+        "avg_launch_us": tms * 1e3 / launches,
+        "algorithmic_flops_per_step": flops / prof_steps,
+        "kernel_ms_per_step": tms / prof_steps,
+    }
 
 
 def _variant_name(code, dtype):
@@ -387,7 +430,7 @@ class _StandInProcess:
 
 
 def _timed(step, steps, warmup, barrier, use_dist, device):
-    """W untimed + K timed steps between barriers; the MAX over ranks of the elapsed time."""
+    """W untimed + K timed steps between barriers; the MAX over ranks of the elapsed time, and what the last timed step returned."""
     keep = None
     for _ in range(warmup):
         keep = step()
@@ -403,8 +446,22 @@ def _timed(step, steps, warmup, barrier, use_dist, device):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax[0])
-    del keep
-    return elapsed
+    return elapsed, keep
+
+
+#: names of what one step of each workload returns, in ``make_step``'s order (``--dump-outputs`` writes ``<name>.npy`` for each)
+OUTPUT_NAMES = {"dense_f64": ("logpdf", "mean", "var"), "sum_f32": ("logpdf", "mean", "var"), "batched_f32": ("logpdf",),
+                "sparse_f32": ("elbo",)}
+
+
+def dump_outputs(name, result, out_dir):
+    """``--dump-outputs DIR``: what the last timed step computed -- the arrays a caller of the step receives -- as ``DIR/<name>.npy``
+    in the workload's own precision (float32 or float64); at most 33 kB per workload, so nothing is sampled."""
+    arrays = result if isinstance(result, tuple) else (result,)
+    assert len(arrays) == len(OUTPUT_NAMES[name]), (name, len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in zip(OUTPUT_NAMES[name], arrays):
+        np.save(os.path.join(out_dir, key + ".npy"), torch.as_tensor(a).detach().cpu().numpy())
 
 
 def _allgather_us(total, world, device, barrier, reps=50):
@@ -445,7 +502,7 @@ def _batched_record(device, rank, world, steps, warmup, barrier, use_dist, dry_r
         st.B.epsilon = 1e-6
         step = make_step(name, w, t)
     try:
-        elapsed = _timed(step, steps, warmup, barrier, use_dist, device)
+        elapsed, _ = _timed(step, steps, warmup, barrier, use_dist, device)
         full = step()
     finally:
         if not dry_run:
@@ -483,7 +540,14 @@ def main():
     ap.add_argument("--dry-run-dist", action="store_true",
                     help="GPU-less proof of the N-rank path: gloo, a stand-in step, the same launch / barrier / all-gather / JSON code")
     ap.add_argument("--dry-run-gps", type=int, default=16, help="--dry-run-dist: how many stand-in GPs are sharded over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the other call order, the roofline of the dominant kernel, the measured peak, the "
+                         "all-gather alone, the `batched` sub-record and the CPU baseline (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; the inputs are seeded)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     global DEFER_CHECKS, ORDER, DRY_RUN_GPS
     DRY_RUN_GPS = max(1, args.dry_run_gps)
@@ -547,56 +611,30 @@ def main():
     if w["dtype"] == "f32":
         st.B.epsilon = 1e-6          # the reference's own fp32 setting (README.md:887-888)
     step = make_step(name, w, tensors)
-    elapsed = _timed(step, args.steps, args.warmup, barrier, use_dist, device)
+    elapsed, last = _timed(step, args.steps, args.warmup, barrier, use_dist, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(name, last, args.dump_outputs)
+    del last
+    full = args.full
 
     # -- the OTHER call order of the same step, a few steps (the default order is the one the rows-under-the-matrix path
     #    accelerates; the record carries both so that rounds stay comparable) --
     other_order = None
-    if name in ("dense_f64", "sum_f32"):
+    if full and name in ("dense_f64", "sum_f32"):
         first = ORDER
         ORDER = "logpdf-first" if first == "posterior-first" else "posterior-first"
         try:
             k_other = max(2, min(args.steps, 5))
-            el = _timed(step, k_other, 1, barrier, use_dist, device)
+            el, _ = _timed(step, k_other, 1, barrier, use_dist, device)
             other_order = {"call_order": ORDER, "steps": k_other, "ms_per_step": 1e3 * el / k_other,
                            "value": k_other * (world if name != "batched_f32" else 1) / el}
         finally:
             ORDER = first
 
-    # -- live roofline of the dominant kernel: extra untimed steps under HIP-event hooks --
-    roofline = None
-    lib = _native.load()
-    import ctypes
-
-    prof_steps = 2
-    lib.gpk_prof_start()
-    for _ in range(prof_steps):
-        keep = step()
-    torch.cuda.synchronize()
-    del keep
-    ms, nl, fl = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
-    best = None
-    for code in range(PROF_CODES):    # every GEMM kernel variant: the dominant one is the one with the most time
-        lib.gpk_prof_stop(code, ctypes.byref(ms), ctypes.byref(nl), ctypes.byref(fl))
-        if nl.value > 0 and (best is None or ms.value > best[1]):
-            best = (code, ms.value, nl.value, fl.value)
+    roofline = dominant_kernel_roofline(name, w, step) if full else None
     peak = PEAK_TFLOPS[w["dtype"]]
-    if best is not None and best[1] > 0:
-        code, tms, launches, flops = best
-        achieved = flops / (tms * 1e-3) / 1e12
-        kname = _variant_name(code, w["dtype"])
-        roofline = {
-            "kernel": kname,
-            "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-            "traffic": pmc_traffic(name, w, kname)[0],
-            "traffic_source": pmc_traffic(name, w, kname)[1],
-            "launches_per_step": launches // prof_steps,
-            "avg_launch_us": tms * 1e3 / launches,
-            "algorithmic_flops_per_step": flops / prof_steps,
-            "kernel_ms_per_step": tms / prof_steps,
-        }
     # -- the peak the chip SUSTAINS on this box, measured; the nominal figure stays the one `frac` is quoted against --
-    pm = measured_peak(w["dtype"])
+    pm = measured_peak(w["dtype"]) if full else None
     if roofline is not None and pm is not None:
         roofline["peak_measured"] = pm["tflops"]
         roofline["frac_of_measured"] = roofline["achieved"] / pm["tflops"]
@@ -610,12 +648,12 @@ def main():
         whole["peak_measured"] = pm["tflops"]
         whole["frac_of_measured"] = whole["achieved"] / pm["tflops"]
     allgather = None
-    if name == "batched_f32" and use_dist and w["b"] % world == 0:
+    if full and name == "batched_f32" and use_dist and w["b"] % world == 0:
         allgather = _allgather_us(w["b"], world, device, barrier)
 
     # -- north_star: "at 1 GPU and at 2/4/8 GPUs for the batched config": configs[3] sharded over these same ranks --
     batched = None
-    if name != "batched_f32" and not args.no_batched_record and not args.n:
+    if full and name != "batched_f32" and not args.no_batched_record and not args.n:
         del step, tensors
         torch.cuda.empty_cache()
         batched = _batched_record(device, rank, world, max(2, min(args.steps, 10)), 1, barrier, use_dist)
@@ -646,7 +684,8 @@ def main():
             "roofline": roofline,
             "whole_step": whole,
             "rccl_world_size": (dist.get_world_size() if use_dist else 0),
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1 or args.n) else cpu_baseline(name),
+            "cpu_baseline": None if (not full or args.no_cpu_baseline or world > 1 or args.n) else cpu_baseline(name),
+            "full": full,
         }
         if other_order is not None:
             out["other_call_order"] = other_order

@@ -1,7 +1,7 @@
 """Samples the GPU's shader clock and socket power while a command runs (an independent
 witness for "the gap to the nominal peak is the clock the chip grants a dense MFMA stream").
 
-    python scripts/clock_trace.py OUT.json -- python bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-batched-record
+    python scripts/clock_trace.py OUT.json -- python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-batched-record
 
 Sources, first one that works: the amdsmi Python binding (gfx clock + socket power), else sysfs (pp_dpm_sclk's starred level /
 hwmon power1_average|power1_input), else `rocm-smi --showclocks --showpower --json` (slow: ~0.2 s per sample).  Ordinary-user

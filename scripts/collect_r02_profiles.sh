@@ -15,8 +15,8 @@ timeout 200 ./gpk_selftest --perf-kmat > $O/r02_native_perf_kmat.log 2>&1
 ( timeout 200 ./gpk_selftest --la-clock f64 16384 1024 0; timeout 200 ./gpk_selftest --la-clock f64 16384 1024 10 ) > $O/r02_la_clock.log 2>&1
 cd /tmp
 for w in dense_f64 sum_f32 batched_f32 sparse_f32; do
-  timeout 400 python $R/bench.py --workload $w 2>/dev/null | tail -1 > $O/r02_bench_$w.json
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline > $O/stats_$w.log 2>&1
+  timeout 400 python $R/bench.py --full --workload $w 2>/dev/null | tail -1 > $O/r02_bench_$w.json
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline > $O/stats_$w.log 2>&1
   F=$(find $O/stats_$w -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/r02_bench_${w}_kernel_stats.csv
   rm -rf $O/stats_$w
   timeout 600 python $R/scripts/collect_pmc.py $w $O/r02_pmc_$w.json > $O/r02_pmc_$w.log 2>&1

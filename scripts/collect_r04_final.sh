@@ -27,11 +27,11 @@ cd /tmp
 for w in batched_f32 dense_f64 sum_f32 sparse_f32; do
   [ $(left) -lt 150 ] && { echo "skipping $w: $(left) s left"; continue; }
   if [ "$w" = dense_f64 ]; then
-    timeout 200 python $R/bench.py --steps 20 --warmup 5 2>/dev/null | grep "^{" | tail -1 > $O/r04_bench_$w.json
+    timeout 200 python $R/bench.py --full --steps 20 --warmup 5 2>/dev/null | grep "^{" | tail -1 > $O/r04_bench_$w.json
   else
-    timeout 200 python $R/bench.py --workload $w --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/r04_bench_$w.json
+    timeout 200 python $R/bench.py --full --workload $w --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/r04_bench_$w.json
   fi
-  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/stats_$w.log 2>&1
+  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/stats_$w.log 2>&1
   F=$(find $O/stats_$w -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/r04_bench_${w}_kernel_stats.csv
   if [ "$w" = dense_f64 ]; then
     T=$(find $O/stats_$w -name "*kernel_trace.csv" | head -1); [ -n "$T" ] && python $R/scripts/dev_trace_sequence.py $T kmat 2 > $O/r04_dense_f64_kernel_sequence.txt 2>&1
@@ -48,5 +48,5 @@ cd $R/stheno_amd/csrc
 [ $(left) -gt 60 ] && timeout 50 ./gpk_selftest --perf-trsm > $O/r04_native_perf_trsm.log 2>&1
 [ $(left) -gt 80 ] && timeout 70 ./gpk_selftest --perf-la > $O/r04_native_perf_lookahead.log 2>&1
 cd /tmp
-[ $(left) -gt 60 ] && GPK_BENCH_FORCE_DIST=1 NCCL_DEBUG=WARN MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 50 python $R/bench.py --gpus 1 --workload batched_f32 --no-cpu-baseline 2>/dev/null | grep "^{" | tail -1 > $O/r04_bench_batched_f32_rccl_1rank.json
+[ $(left) -gt 60 ] && GPK_BENCH_FORCE_DIST=1 NCCL_DEBUG=WARN MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 50 python $R/bench.py --full --gpus 1 --workload batched_f32 --no-cpu-baseline 2>/dev/null | grep "^{" | tail -1 > $O/r04_bench_batched_f32_rccl_1rank.json
 echo "finished at $SECONDS s"

@@ -24,13 +24,13 @@ cd /tmp
 for w in dense_f64 sum_f32 batched_f32 sparse_f32; do
   [ $(left) -lt 200 ] && { echo "skipping $w: $(left) s left"; continue; }
   if [ "$w" = dense_f64 ]; then
-    timeout 300 python $R/bench.py --steps 20 --warmup 5 2> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_$w.json
-    timeout 200 python $R/bench.py --steps 20 --warmup 5 --order logpdf-first --no-cpu-baseline --no-batched-record 2>> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_${w}_logpdf_first.json
+    timeout 300 python $R/bench.py --full --steps 20 --warmup 5 2> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_$w.json
+    timeout 200 python $R/bench.py --full --steps 20 --warmup 5 --order logpdf-first --no-cpu-baseline --no-batched-record 2>> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_${w}_logpdf_first.json
   else
-    timeout 300 python $R/bench.py --workload $w --no-batched-record 2> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_$w.json
+    timeout 300 python $R/bench.py --full --workload $w --no-batched-record 2> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_$w.json
   fi
   [ -s $O/r05_bench_$w.json ] || echo "NO BENCH LINE for $w -- see $O/r05_bench_$w.stderr.log"
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/r05_stats_$w.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/r05_stats_$w.log 2>&1
   F=$(find $O/stats_$w -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/r05_bench_${w}_kernel_stats.csv || echo "NO KERNEL STATS for $w -- see $O/r05_stats_$w.log"
   if [ "$w" = dense_f64 ]; then
     T=$(find $O/stats_$w -name "*kernel_trace.csv" | head -1)

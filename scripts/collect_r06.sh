@@ -26,12 +26,12 @@ if want bench; then
   for w in dense_f64 sum_f32 batched_f32 sparse_f32; do
     [ $(left) -lt 200 ] && { echo "skipping $w: $(left) s left"; continue; }
     if [ "$w" = dense_f64 ]; then
-      timeout 300 python $R/bench.py --steps 20 --warmup 5 2> $O/r06_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r06_bench_$w.json
+      timeout 300 python $R/bench.py --full --steps 20 --warmup 5 2> $O/r06_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r06_bench_$w.json
     else
-      timeout 300 python $R/bench.py --workload $w --no-batched-record 2> $O/r06_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r06_bench_$w.json
+      timeout 300 python $R/bench.py --full --workload $w --no-batched-record 2> $O/r06_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r06_bench_$w.json
     fi
     [ -s $O/r06_bench_$w.json ] || echo "NO BENCH LINE for $w -- see $O/r06_bench_$w.stderr.log"
-    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/r06_stats_$w.log 2>&1
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o s -- python $R/bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/r06_stats_$w.log 2>&1
     F=$(find $O/stats_$w -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/r06_bench_${w}_kernel_stats.csv || echo "NO KERNEL STATS for $w -- see $O/r06_stats_$w.log"
     if [ "$w" = dense_f64 ]; then
       T=$(find $O/stats_$w -name "*kernel_trace.csv" | head -1)
@@ -41,8 +41,8 @@ if want bench; then
     echo "$w bench + stats done at $SECONDS s"
   done
   # an independent witness of the clock and the power under the two headline workloads, and under the bare MFMA stream
-  timeout 200 python $R/scripts/clock_trace.py $O/r06_clock_trace_dense_f64.json -- python $R/bench.py --steps 100 --warmup 5 --no-cpu-baseline --no-batched-record 2> $O/r06_clock_trace.stderr.log | cut -c1-600
-  timeout 200 python $R/scripts/clock_trace.py $O/r06_clock_trace_batched_f32.json -- python $R/bench.py --workload batched_f32 --steps 100 --warmup 5 --no-cpu-baseline 2>> $O/r06_clock_trace.stderr.log | cut -c1-600
+  timeout 200 python $R/scripts/clock_trace.py $O/r06_clock_trace_dense_f64.json -- python $R/bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --no-batched-record 2> $O/r06_clock_trace.stderr.log | cut -c1-600
+  timeout 200 python $R/scripts/clock_trace.py $O/r06_clock_trace_batched_f32.json -- python $R/bench.py --full --workload batched_f32 --steps 100 --warmup 5 --no-cpu-baseline 2>> $O/r06_clock_trace.stderr.log | cut -c1-600
   timeout 200 python $R/scripts/clock_trace.py $O/r06_clock_trace_mfma_peak.json -- python -c "
 import ctypes, torch, json, sys
 sys.path.insert(0, '$R')

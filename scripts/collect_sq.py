@@ -19,7 +19,7 @@ import csv, glob, json, os, subprocess, sys
 workload, out_path = sys.argv[1], sys.argv[2]
 extra = sys.argv[3:]
 repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-cmd = [sys.executable, os.path.join(repo, "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
        "--no-batched-record"] + extra
 mops = "SQ_INSTS_VALU_MFMA_MOPS_F64" if workload.endswith("f64") else "SQ_INSTS_VALU_MFMA_MOPS_F32"
 counters = ["SQ_BUSY_CU_CYCLES", "SQ_VALU_MFMA_BUSY_CYCLES", mops, "SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY",

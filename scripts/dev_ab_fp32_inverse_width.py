@@ -5,5 +5,5 @@ sys.path.insert(0, sys.argv[1])
 from stheno_amd import matrix
 matrix.config.potrf_lookahead_inv[torch.float32] = int(sys.argv[2])
 import bench
-sys.argv = ["bench.py", "--workload", "sum_f32", "--no-cpu-baseline", "--steps", "10", "--warmup", "2"]
+sys.argv = ["bench.py", "--full", "--workload", "sum_f32", "--no-cpu-baseline", "--steps", "10", "--warmup", "2"]
 bench.main()

@@ -12,6 +12,6 @@ timeout 120 ./gpk_selftest --perf-agg f64 16384 1024 0 4 0 1 2 3 4 > $O/perf_agg
 timeout 120 ./gpk_selftest --perf-agg f64 16384 1024 0 3 4096 1 2 4 > $O/perf_agg_f64_tail4096.log 2>&1; grep SUMMARY $O/perf_agg_f64_tail4096.log
 timeout 200 ./gpk_selftest --perf-agg f32 32768 1024 512 3 0 1 2 3 4 > $O/perf_agg_f32.log 2>&1; grep SUMMARY $O/perf_agg_f32.log
 cd /tmp
-timeout 200 python $R/bench.py --steps 20 --warmup 5 2> $O/bench_dense.err | grep "^{" | tail -1 > $O/bench_dense_f64.json; cat $O/bench_dense_f64.json
-timeout 200 python $R/bench.py --workload sum_f32 --no-batched-record --no-cpu-baseline 2> $O/bench_sum.err | grep "^{" | tail -1 > $O/bench_sum_f32.json; cat $O/bench_sum_f32.json
+timeout 200 python $R/bench.py --full --steps 20 --warmup 5 2> $O/bench_dense.err | grep "^{" | tail -1 > $O/bench_dense_f64.json; cat $O/bench_dense_f64.json
+timeout 200 python $R/bench.py --full --workload sum_f32 --no-batched-record --no-cpu-baseline 2> $O/bench_sum.err | grep "^{" | tail -1 > $O/bench_sum_f32.json; cat $O/bench_sum_f32.json
 echo "finished at $SECONDS s"

@@ -15,9 +15,9 @@ timeout 900 python -m pytest tests -m gpu -x -q --deselect tests/test_round5_evi
 cd /tmp
 for w in dense_f64 sum_f32 sparse_f32 batched_f32; do
   if [ "$w" = dense_f64 ]; then
-    timeout 300 python $R/bench.py --steps 20 --warmup 5 2> $O/bench_$w.err | grep "^{" | tail -1 > $O/bench_$w.json
+    timeout 300 python $R/bench.py --full --steps 20 --warmup 5 2> $O/bench_$w.err | grep "^{" | tail -1 > $O/bench_$w.json
   else
-    timeout 300 python $R/bench.py --workload $w --no-batched-record --no-cpu-baseline 2> $O/bench_$w.err | grep "^{" | tail -1 > $O/bench_$w.json
+    timeout 300 python $R/bench.py --full --workload $w --no-batched-record --no-cpu-baseline 2> $O/bench_$w.err | grep "^{" | tail -1 > $O/bench_$w.json
   fi
   python - <<PY
 import json

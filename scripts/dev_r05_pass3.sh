@@ -25,17 +25,17 @@ PY
 }
 for rep in 1 2; do
   for ord in posterior-first logpdf-first; do
-    timeout 300 python $R/bench.py --steps 20 --warmup 5 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_dense_$ord.err | grep "^{" | tail -1 > $O/bench_dense_${ord}_$rep.json
+    timeout 300 python $R/bench.py --full --steps 20 --warmup 5 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_dense_$ord.err | grep "^{" | tail -1 > $O/bench_dense_${ord}_$rep.json
     line $O/bench_dense_${ord}_$rep.json "dense $ord rep$rep"
   done
-  timeout 300 python $R/bench.py --steps 20 --warmup 5 --order logpdf-first --no-deferred-checks --no-cpu-baseline --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/bench_dense_nodefer_$rep.json
+  timeout 300 python $R/bench.py --full --steps 20 --warmup 5 --order logpdf-first --no-deferred-checks --no-cpu-baseline --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/bench_dense_nodefer_$rep.json
   line $O/bench_dense_nodefer_$rep.json "dense logpdf-first no-deferred rep$rep"
 done
 for ord in posterior-first logpdf-first; do
-  timeout 300 python $R/bench.py --workload sum_f32 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_sum_$ord.err | grep "^{" | tail -1 > $O/bench_sum_$ord.json
+  timeout 300 python $R/bench.py --full --workload sum_f32 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_sum_$ord.err | grep "^{" | tail -1 > $O/bench_sum_$ord.json
   line $O/bench_sum_$ord.json "sum_f32 $ord"
 done
-timeout 300 python $R/bench.py --workload sparse_f32 --no-cpu-baseline --no-batched-record 2> $O/bench_sparse.err | grep "^{" | tail -1 > $O/bench_sparse_f32.json
+timeout 300 python $R/bench.py --full --workload sparse_f32 --no-cpu-baseline --no-batched-record 2> $O/bench_sparse.err | grep "^{" | tail -1 > $O/bench_sparse_f32.json
 line $O/bench_sparse_f32.json "sparse_f32"
 timeout 600 python $R/scripts/collect_sq.py batched_f32 $O/r05_sq_batched_f32.json 2>&1 | tail -8
 echo "finished at $SECONDS s"

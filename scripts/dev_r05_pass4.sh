@@ -19,16 +19,16 @@ PY
 }
 for rep in 1 2; do
   for ord in posterior-first logpdf-first; do
-    timeout 300 python $R/bench.py --steps 20 --warmup 5 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_dense_$ord.err | grep "^{" | tail -1 > $O/bench_dense_${ord}_$rep.json
+    timeout 300 python $R/bench.py --full --steps 20 --warmup 5 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_dense_$ord.err | grep "^{" | tail -1 > $O/bench_dense_${ord}_$rep.json
     line $O/bench_dense_${ord}_$rep.json "dense $ord rep$rep"
   done
 done
 for ord in posterior-first logpdf-first; do
-  timeout 300 python $R/bench.py --workload sum_f32 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_sum_$ord.err | grep "^{" | tail -1 > $O/bench_sum_$ord.json
+  timeout 300 python $R/bench.py --full --workload sum_f32 --order $ord --no-cpu-baseline --no-batched-record 2> $O/bench_sum_$ord.err | grep "^{" | tail -1 > $O/bench_sum_$ord.json
   line $O/bench_sum_$ord.json "sum_f32 $ord"
 done
 for ord in posterior-first logpdf-first; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$ord -o s -- python $R/bench.py --order $ord --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/stats_$ord.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$ord -o s -- python $R/bench.py --full --order $ord --steps 5 --warmup 2 --no-cpu-baseline --no-batched-record > $O/stats_$ord.log 2>&1
   F=$(find $O/stats_$ord -name "*kernel_stats.csv" | head -1); [ -n "$F" ] && cp $F $O/r05_dense_${ord}_kernel_stats.csv
   T=$(find $O/stats_$ord -name "*kernel_trace.csv" | head -1); [ -n "$T" ] && python $R/scripts/dev_trace_sequence.py $T kmat 2 > $O/r05_dense_${ord}_kernel_sequence.txt 2>&1
   rm -rf $O/stats_$ord

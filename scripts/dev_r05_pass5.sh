@@ -33,7 +33,7 @@ except Exception as e:
 PY
 }
 for rep in 1 2; do
-  timeout 300 python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/ab_pf_$rep.json; line $O/ab_pf_$rep.json "posterior-first rep$rep"
-  timeout 300 python $R/bench.py --steps 20 --warmup 5 --deferred-checks --no-cpu-baseline --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/ab_pfd_$rep.json; line $O/ab_pfd_$rep.json "posterior-first deferred rep$rep"
+  timeout 300 python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/ab_pf_$rep.json; line $O/ab_pf_$rep.json "posterior-first rep$rep"
+  timeout 300 python $R/bench.py --full --steps 20 --warmup 5 --deferred-checks --no-cpu-baseline --no-batched-record 2>/dev/null | grep "^{" | tail -1 > $O/ab_pfd_$rep.json; line $O/ab_pfd_$rep.json "posterior-first deferred rep$rep"
 done
 echo "finished at $SECONDS s"

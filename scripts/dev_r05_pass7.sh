@@ -19,8 +19,8 @@ except Exception as e:
 PY
 }
 for rep in 1 2; do
-  timeout 200 python $R/bench.py --workload batched_f32 --no-cpu-baseline 2> $O/bench_batched.err | grep "^{" | tail -1 > $O/ab_batched_fused_$rep.json; line $O/ab_batched_fused_$rep.json "batched (release: fused) rep$rep"
-  GPK_DEV=1 GPK_TUNE=53=0 timeout 200 python $R/bench.py --workload batched_f32 --no-cpu-baseline 2>> $O/bench_batched.err | grep "^{" | tail -1 > $O/ab_batched_unfused_$rep.json; line $O/ab_batched_unfused_$rep.json "batched (dev, knob 53 = 0: kmat launch + potrf) rep$rep"
-  GPK_DEV=1 timeout 200 python $R/bench.py --workload batched_f32 --no-cpu-baseline 2>> $O/bench_batched.err | grep "^{" | tail -1 > $O/ab_batched_devfused_$rep.json; line $O/ab_batched_devfused_$rep.json "batched (dev, fused) rep$rep"
+  timeout 200 python $R/bench.py --full --workload batched_f32 --no-cpu-baseline 2> $O/bench_batched.err | grep "^{" | tail -1 > $O/ab_batched_fused_$rep.json; line $O/ab_batched_fused_$rep.json "batched (release: fused) rep$rep"
+  GPK_DEV=1 GPK_TUNE=53=0 timeout 200 python $R/bench.py --full --workload batched_f32 --no-cpu-baseline 2>> $O/bench_batched.err | grep "^{" | tail -1 > $O/ab_batched_unfused_$rep.json; line $O/ab_batched_unfused_$rep.json "batched (dev, knob 53 = 0: kmat launch + potrf) rep$rep"
+  GPK_DEV=1 timeout 200 python $R/bench.py --full --workload batched_f32 --no-cpu-baseline 2>> $O/bench_batched.err | grep "^{" | tail -1 > $O/ab_batched_devfused_$rep.json; line $O/ab_batched_devfused_$rep.json "batched (dev, fused) rep$rep"
 done
 echo "finished at $SECONDS s"

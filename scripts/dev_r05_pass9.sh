@@ -13,7 +13,7 @@ timeout 120 ./gpk_selftest --perf-pipe 2>&1 | grep -E "pipe=1" | head -24 | tee 
 timeout 60 ./gpk_selftest --batched 512 2>&1 | head -3
 timeout 100 ./gpk_selftest --perf-rows f64 16384 2048 1024 0 3 2>&1 | tail -4
 cd /tmp
-timeout 300 python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep "^{" | python -c "
+timeout 300 python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep "^{" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('dense', round(d['ms_per_step'],3), 'ms', round(d['value'],3), 'evals/s; batched', round(d['batched']['ms_per_step'],3))"
 echo "finished at $SECONDS s"

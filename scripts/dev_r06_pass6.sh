@@ -15,7 +15,7 @@ done
 cd $R
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py tests/test_round5_concurrency.py tests/test_gpu_fuzz.py -m gpu -q -x 2>&1 | tail -5
 cd /tmp
-timeout 300 python $R/bench.py --workload batched_f32 --no-cpu-baseline 2> $O/bench_batched.stderr.log | grep "^{" | tail -1 > $O/bench_batched_f32.json
+timeout 300 python $R/bench.py --full --workload batched_f32 --no-cpu-baseline 2> $O/bench_batched.stderr.log | grep "^{" | tail -1 > $O/bench_batched_f32.json
 python -c "
 import json; d=json.load(open('$O/bench_batched_f32.json')); print(d['value'], d['ms_per_step'], d['roofline'], d['whole_step'])"
 echo "finished at $SECONDS s"

@@ -10,7 +10,7 @@ tail -3 $O/r05_pytest_gpu.log
 grep -h "SUMMARY\|FAIL" $O/r05_selftest.log $O/r05_selftest_release.log | head
 cd /tmp
 for w in dense_f64 sum_f32 batched_f32 sparse_f32; do
-  timeout 300 python $R/bench.py --workload $w --no-batched-record 2> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_$w.json
+  timeout 300 python $R/bench.py --full --workload $w --no-batched-record 2> $O/r05_bench_$w.stderr.log | grep "^{" | tail -1 > $O/r05_bench_$w.json
   python -c "
 import json; d=json.load(open('$O/r05_bench_$w.json')); r=d['roofline']; print('$w', round(d['value'],3), d['unit'], round(d['ms_per_step'],3), 'ms', r['kernel'][:40], round(r['frac'],4), 'whole', round(d['whole_step']['frac'],4))"
 done

@@ -53,3 +53,55 @@ def test_rank_count_mismatch_is_refused():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-dist"], capture_output=True, text=True,
                          timeout=300, env=dict(os.environ, **env), cwd=ROOT)
     assert res.returncode != 0 and "launcher started 1 ranks" in (res.stderr + res.stdout)
+
+
+def _run_on_gpu(*flags):
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    at = res.stdout.rfind('{"metric"')          # (the device libraries may print to stdout too)
+    assert at >= 0, res.stdout[-2000:]
+    return json.loads(res.stdout[at:].splitlines()[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """A plain run (no ``--full``) carries the headline and nothing measured beside it; ``--dump-outputs`` writes the last timed
+    step's log-density, posterior mean and variance in fp64, which agree with the oracle on the same seeded inputs."""
+    import numpy as np
+
+    from bench import NOISE, make_inputs
+    from oracle import gp_oracle as O
+
+    n = 2048
+    out = _run_on_gpu("--n", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert out["full"] is False and out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "f64"
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-9 * out["value"]
+    assert out["roofline"] is None and out["cpu_baseline"] is None
+    assert not {"batched", "other_call_order", "allgather_us"} & set(out)
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("logpdf", "mean", "var")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["logpdf"].size == 1 and got["mean"].shape == (2048,) and got["var"].shape == (2048,)
+    _, t = make_inputs("dense_f64", "cpu", n_override=n)
+    x, y, xs = (t[k].numpy() for k in ("x", "y", "xs"))
+    terms = [("eq", 1.0, 1.0)]
+    ref_lp = O.gp_logpdf(terms, x, NOISE, y)
+    ref_mean, _, ref_var = O.gp_posterior(terms, x, NOISE, y, xs, full_cov=False)
+    assert abs(float(got["logpdf"]) - ref_lp) <= 1e-6 * abs(ref_lp)
+    assert np.max(np.abs(got["mean"] - ref_mean)) <= 1e-6 * np.max(np.abs(ref_mean))
+    assert np.max(np.abs(got["var"] - ref_var)) <= 1e-6 * np.max(np.abs(ref_var))
+
+
+@pytest.mark.gpu
+def test_batched_workload_dumps_its_fp32_log_densities(tmp_path):
+    import numpy as np
+
+    from bench import NOISE, make_inputs
+    from oracle import gp_oracle as O
+
+    out = _run_on_gpu("--workload", "batched_f32", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert out["full"] is False and out["steps"] == 2 and out["unit"] == "GPs/s" and out["ms_per_step"] > 0
+    lp = np.load(tmp_path / "logpdf.npy")
+    assert lp.dtype == np.float32 and lp.shape == (512,) and np.isfinite(lp).all()
+    _, t = make_inputs("batched_f32", "cpu")
+    ref = O.gp_logpdf_batched([("eq", 1.0, 1.0)], t["x"][:2].double().numpy(), NOISE, t["y"][:2].double().numpy(), eps=1e-6)
+    assert np.max(np.abs(lp[:2] - ref) / np.abs(ref)) < 1e-3, (lp[:2], ref)

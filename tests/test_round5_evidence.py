@@ -167,8 +167,8 @@ def test_bench_batched_workload_through_a_one_rank_rccl_group():
         port = sk.getsockname()[1]
     env = dict(os.environ, GPK_BENCH_FORCE_DIST="1", NCCL_DEBUG="WARN", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0",
                WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "batched_f32", "--no-cpu-baseline",
-                        "--steps", "3", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "batched_f32", "--full",
+                        "--no-cpu-baseline", "--steps", "3", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     try:
         os.makedirs(OUT_DIR, exist_ok=True)
         with open(os.path.join(OUT_DIR, "r05_bench_batched_f32_rccl_1rank.stderr.log"), "w") as fh:
