@@ -210,6 +210,22 @@ int gpk_trsv_lower(int dtype, const void* l, int64_t n, int64_t ld, int64_t sl, 
                    int sb, void* b, int nrhs, int64_t ldb, int64_t sb_stride, void* tmp, int64_t batch,
                    void* stream);
 
+/* X = L^{-T} B, many right-hand sides, OUT OF PLACE like gpk_trsm_lower_to (`b` is used up as workspace, x: ldx >= nrhs): the same
+ * recursive blocked solve run bottom-up -- X2 = L22^{-T} B2, B1 -= L21^T X2 (ONE GEMM reading L21 where it is, K x M), X1 = L11^{-T} B1;
+ * the leaves multiply by the transposes of the same merged sb x sb inverses (dinv_sb as for gpk_trsm_lower).
+ * Replaces the `B.solve(L^T, .)` (LAPACK trsm, transposed) inside the reference's autograd through mlkernels.PosteriorMean /
+ * PosteriorKernel (observations.py:148-168): the backward of the posterior mean and marginal variances. */
+int gpk_trsm_lower_t(int dtype, const void* l, int64_t n, int64_t ld, int64_t sl, const void* dinv_sb,
+                     int sb, void* b, int64_t nrhs, int64_t ldb, int64_t sb_stride, void* x, int64_t ldx,
+                     int64_t sx_stride, int64_t batch, void* stream);
+
+/* B <- L^{-T} B, nrhs <= 8: bottom-up sweep over the sb-blocks, two launches per block (transposed GEMVs: L read by block rows,
+ * HBM-bound like gpk_trsv_lower).  tmp: batch * sb * nrhs elements.  Replaces the single-column transposed solves of the same
+ * backward (`K^{-1} (y - m)` and `L^{-T} (V g)`). */
+int gpk_trsv_lower_t(int dtype, const void* l, int64_t n, int64_t ld, int64_t sl, const void* dinv_sb,
+                     int sb, void* b, int nrhs, int64_t ldb, int64_t sb_stride, void* tmp, int64_t batch,
+                     void* stream);
+
 /* C = alpha * op(A) op(B)^T-style contraction + beta * C on MFMA:
  *   C[m][n] = alpha * sum_k a(m,k) b(n,k) + beta * C[m][n]
  * a_kmajor != 0: A stored M x K (k contiguous); else stored K x M.  Same for B (N x K / K x N).

@@ -67,6 +67,16 @@ SIGNATURES = {
         [_c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_int, _c_ptr, _c_int, _c_i64, _c_i64, _c_ptr,
          _c_i64, _c_ptr],
     ),
+    "gpk_trsm_lower_t": (
+        _c_int,
+        [_c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64,
+         _c_i64, _c_i64, _c_ptr],
+    ),
+    "gpk_trsv_lower_t": (
+        _c_int,
+        [_c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_int, _c_ptr, _c_int, _c_i64, _c_i64, _c_ptr,
+         _c_i64, _c_ptr],
+    ),
     "gpk_gemm": (
         _c_int,
         [_c_int, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_dbl, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64,

@@ -21,7 +21,7 @@ import torch
 from . import ops
 from .matrix import LOG_2_PI, Chol, config
 
-__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo"]
+__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals"]
 
 
 def _cotangent(be, kinv_lower, alpha, g):
@@ -442,3 +442,144 @@ def sparse_elbo(kernel, x, z, noise_vec, r, method):
     as_t = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
     params = [as_t(v) for _, v, _ in tt] + [as_t(s) for _, _, s in tt]
     return _SparseELBO.apply(x, z, r, noise_vec, {"vfe": 1.0, "dtc": 0.0, "fitc": -1.0}[method], kinds, *params)
+
+
+# ---------------------------------------------------------------------------------------------
+# Posterior marginals of an exact posterior of ONE process, f | (f(x, noise), y) evaluated at test inputs xs: the latent mean
+# part and the variance reduction, differentiable w.r.t. the kernel variances / length scales, the noise, r = y - m(x), the
+# inputs x and the test inputs xs (observations.py:148-168 through lab/torch in the reference).
+#
+# K = k(x, x) + noise + eps I = L L^T,  V = L^{-1} k(x, xs) (N x N*),  w = L^{-1} r,  alpha = L^{-T} w = K^{-1} r,
+# B = L^{-T} V = K^{-1} k(x, xs).  Outputs: mu = V^T w (the mean minus m(xs)) and s_j = |V_j|^2 (k(xs_j, xs_j) minus the marginal
+# variance); the caller adds m(xs) and k(xs, xs) in torch.  With the cotangents gm of mu and gs of s (gs = -g_var):
+#     beta         = B gm                    (gs == 0: L^{-T} (V gm), one single-column back-substitution, no N x N* solve)
+#     dL/dk(x, xs) = alpha gm^T + 2 B diag(gs)                                    (N x N*)
+#     dL/dK        = -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T)        (N x N, symmetric; its diagonal: d/dnoise)
+#     dL/dr        = beta
+# The cross cotangent is reduced by gpk_kmat_vjp_dense on (x, xs): the rank-1 part rides in its w / b operands, 2 diag(gs) in its
+# colscale; d/dxs takes the same reduction on (xs, x) over the explicit transpose.  dL/dK is reduced by gpk_kmat_vjp in its own form
+# 1/2 (A diag(g) A^T - sum(g) S) with S = B diag(gs) B^T (ONE lower SYRK on the MFMA GEMM), A = [alpha + beta, alpha - beta, 0],
+# g = [-1/2, 1/2, 2] (the rank-2 part as a difference of squares); d/dx through K takes the explicit symmetric cotangent
+# (gpk_kmat_vjp_dense, x 2, as in the log-density).  The one new operation is the back-substitution with the transposed factor,
+# gpk_trsm_lower_t / gpk_trsv_lower_t: N^2 N* flops for B against N^3/3 for an explicit inverse.
+# ---------------------------------------------------------------------------------------------
+class _PosteriorMarginals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, xs, r, noise_vec, run, kinds, *params):
+        """``run()`` -> ``(chol, w, v, mu, s)``: the plain HIP path of the posterior (``kernels._posterior_parts``: the factor a
+        preceding log-density left, or the one whose factorisation carried the cross-covariance as rows under the matrix); ``v`` is
+        ``L^{-1} k(x, xs)`` (N, N*) or its transpose as a ``WhitenedT``.  ``x`` / ``xs``: the inputs the fused kernels see (divided by
+        per-dimension length scales); ``r`` (N, 1) or None (marginal variances only: ``mu`` comes back as zeros)."""
+        chol, w, v, mu, s = run()
+        nt = len(kinds)
+        variances, scales = params[:nt], params[nt:]
+        ctx.terms = ops.KTerms([(k, float(vv), float(sc)) for k, vv, sc in zip(kinds, variances, scales)])
+        ctx.chol, ctx.w, ctx.v, ctx.x, ctx.xs = chol, w, v, x, xs
+        ctx.nt, ctx.has_noise, ctx.has_r = nt, noise_vec is not None, r is not None
+        ctx.param_meta = [(p.device, p.dtype) for p in params]
+        ctx.values = ([float(vv) for vv in variances], [float(sc) for sc in scales])
+        ctx.set_materialize_grads(False)
+        if mu is None:
+            mu = torch.zeros_like(s)
+        return mu, s
+
+    @staticmethod
+    def backward(ctx, g_mu, g_s):
+        be = ops.get_backend()
+        chol, v, x, xs, terms, nt = ctx.chol, ctx.v, ctx.x, ctx.xs, ctx.terms, ctx.nt
+        n, ns = x.shape[0], xs.shape[0]
+        dt, dev = x.dtype, x.device
+        gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
+        gs = g_s.to(dt).contiguous() if g_s is not None else None
+        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
+            gs = None
+        need_x, need_xs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if gm is None and gs is None:
+            return (None,) * (6 + 2 * nt)
+        transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
+        alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
+        bm = beta = None
+        if gs is not None:
+            # B = L^{-T} V: the N x N* back-substitution (its right-hand side is a private copy: the solve uses it up)
+            bm = chol.solve_t_(v.plain() if transposed else be.copy(v))
+            if gm is not None:
+                beta = be.gemv(bm, gm[:, None])[:, 0]
+        elif gm is not None:
+            vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[:, None])[:, 0]
+            beta = chol.solve_t(vg[:, None])[:, 0]
+
+        def zeros(rows, cols):          # an all-zero operand read through a zero row stride (no rows x cols buffer)
+            return torch.zeros((1, cols), dtype=dt, device=dev).expand(rows, cols)
+
+        # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs)
+        cs = 2.0 * gs if gs is not None else None
+        S, _, grad_x = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
+                                         want_gradx=need_x)
+        grad_xs = None
+        if need_xs:
+            if x.shape[-1] > 8:
+                raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
+                                          "are implemented for at most 8 input dimensions")
+            if bm is not None:
+                g_t = be.copy(bm)
+                be.scale_cols_(g_t, cs)
+                g_t = g_t.t().contiguous()                               # (N*, N): 2 diag(gs) B^T, explicit
+            else:
+                g_t = zeros(ns, n)
+            _, _, grad_xs = be.kmat_vjp_dense(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
+            del g_t
+        # through K: -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T) = 1/2 (A diag(g) A^T - sum(g) S)
+        cols, g = [], []
+        if gm is not None:
+            cols += [alpha + beta, alpha - beta]
+            g += [-0.5, 0.5]
+        if bm is not None:
+            bs = be.copy(bm)
+            be.scale_cols_(bs, gs)
+            kinv = be.gemm(bs, bm, a_kmajor=True, b_kmajor=True, lower_only=True)      # S = B diag(gs) B^T (lower triangle)
+            del bs, bm
+            cols.append(torch.zeros_like(x[:, 0]))
+            g.append(2.0)
+        else:
+            kinv = zeros(n, n)
+        A = torch.stack(cols, dim=1)
+        S_k, _, diag_g = be.kmat_vjp(terms, x, kinv, A, g)
+        S = S + S_k
+        if need_x:
+            if kinv.stride(0) == 0:
+                kinv = torch.zeros((n, n), dtype=dt, device=dev)
+            grad_x = grad_x + _grad_inputs(be, terms, x, _cotangent(be, kinv, A, g))
+        variances, scales = ctx.values
+        grads = []
+        for t in range(nt):
+            dev_t, dt_t = ctx.param_meta[t]
+            grads.append(S[t, 0].to(device=dev_t, dtype=dt_t))
+        for t in range(nt):
+            dev_t, dt_t = ctx.param_meta[nt + t]
+            grads.append((-2.0 * variances[t] / scales[t] * S[t, 1]).to(device=dev_t, dtype=dt_t))
+        grad_r = beta[:, None] if (beta is not None and ctx.needs_input_grad[2]) else None
+        grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[3]) else None
+        return (grad_x, grad_xs, grad_r, grad_noise, None, None, *grads)
+
+
+def kdiag_terms(tensor_terms, x):
+    """``k(x_i, x_i)`` (N,) of a sum of primitives as a differentiable torch expression (O(N D)): stationary terms are their variance,
+    a linear term ``v |x_i|^2 / s^2``."""
+    out = None
+    for kind, v, s in tensor_terms:
+        if kind == "linear":
+            t = v * (x * x).sum(-1) / (s * s)
+        else:
+            t = v * torch.ones(x.shape[:-1], dtype=x.dtype, device=x.device)
+        out = t if out is None else out + t
+    return out
+
+
+def posterior_marginals(kernel, x, xs, r, noise_vec, run):
+    """Differentiable ``(mu, s)`` of ``_PosteriorMarginals`` for a sum of primitives ``kernel`` evaluated on ``x`` / ``xs`` (already
+    divided by per-dimension length scales, so torch carries those)."""
+    tt = kernel.tensor_terms()
+    kinds = tuple(k for k, _, _ in tt)
+    as_t = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
+    params = [as_t(v) for _, v, _ in tt] + [as_t(s) for _, _, s in tt]
+    return _PosteriorMarginals.apply(x, xs, r, noise_vec, run, kinds, *params)

@@ -39,7 +39,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 100; }
+int gpk_version(void) { return 101; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -147,6 +147,21 @@ int gpk_trsv_lower(int dtype, const void* l, int64_t n, int64_t ld, int64_t sl, 
                    void* stream) {
     D1(dtype, gpk_trsv_launch<T>((const T*)l, n, ld, sl, (const T*)dinv_sb, sb, (T*)b, nrhs, ldb, sb_stride,
                                  (T*)tmp, batch, (hipStream_t)stream));
+}
+
+int gpk_trsm_lower_t(int dtype, const void* l, int64_t n, int64_t ld, int64_t sl, const void* dinv_sb,
+                     int sb, void* b, int64_t nrhs, int64_t ldb, int64_t sb_stride, void* x, int64_t ldx, int64_t sx_stride,
+                     int64_t batch, void* stream) {
+    if (x == nullptr) return GPK_ERR_ARG(12);
+    D1(dtype, gpk_trsm_t_launch<T>((const T*)l, n, ld, sl, (const T*)dinv_sb, sb, (T*)b, nrhs, ldb, sb_stride, (T*)x, ldx, sx_stride,
+                                   batch, (hipStream_t)stream));
+}
+
+int gpk_trsv_lower_t(int dtype, const void* l, int64_t n, int64_t ld, int64_t sl, const void* dinv_sb,
+                     int sb, void* b, int nrhs, int64_t ldb, int64_t sb_stride, void* tmp, int64_t batch,
+                     void* stream) {
+    D1(dtype, gpk_trsv_t_launch<T>((const T*)l, n, ld, sl, (const T*)dinv_sb, sb, (T*)b, nrhs, ldb, sb_stride,
+                                   (T*)tmp, batch, (hipStream_t)stream));
 }
 
 int gpk_gemm(int dtype, int a_kmajor, int b_kmajor, int64_t m, int64_t n, int64_t k, double alpha,

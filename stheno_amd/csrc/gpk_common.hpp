@@ -219,6 +219,12 @@ template <typename T>
 int gpk_trsv_launch(const T* L, int64_t n, int64_t ld, int64_t sL, const T* dinv_sb, int sb, T* B,
                     int nrhs, int64_t ldb, int64_t sB, T* tmp, int64_t batch, hipStream_t stream);
 template <typename T>
+int gpk_trsm_t_launch(const T* L, int64_t n, int64_t ld, int64_t sL, const T* dinv_sb, int sb, T* B,
+                      int64_t nrhs, int64_t ldb, int64_t sB, T* X, int64_t ldx, int64_t sX, int64_t batch, hipStream_t stream);
+template <typename T>
+int gpk_trsv_t_launch(const T* L, int64_t n, int64_t ld, int64_t sL, const T* dinv_sb, int sb, T* B,
+                      int nrhs, int64_t ldb, int64_t sB, T* tmp, int64_t batch, hipStream_t stream);
+template <typename T>
 int gpk_logdet_launch(const T* L, int64_t n, int64_t ld, int64_t sL, int64_t batch, T* out,
                       hipStream_t stream);
 int64_t gpk_colreduce_nchunks_impl(int64_t rows);

@@ -778,7 +778,198 @@ int gpk_trtri_launch(const T* L, int64_t n, int64_t ld, const T* dinv_sb, int sb
     return GPK_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Solves with the TRANSPOSED factor, X = L^{-T} B (the backward of the posterior mean / marginal variances).
+// Bottom-up, the mirror of the forward solves: the transposed diagonal blocks are the transposes of the same merged inverses,
+// the off-diagonal blocks are read where they are (no transposed copy of L).
+// ---------------------------------------------------------------------------
+
+// Transposed GEMV with a few right-hand sides:
+//   y[j][c] = beta * y[j][c] + alpha * sum_i A[i][j] x[i][c],   j in [0, M), i in [i0(j), K)
+// plus an optional copy  ycopy[i][c] = x[i][c], i in [0, K)  (writes a solved block back while the rows above are updated).
+// tri: A is lower triangular (A[i][j] = 0 for i < j): a column tile starts at its own first row.
+// A workgroup owns 64 columns (one per lane: the rows of A are read as coalesced 64-column segments); its four waves take every
+// fourth row and are added up in LDS in a fixed order (no atomics: the same bits on every run).  HBM-bound: A is read once.
+template <typename T>
+struct GemvTArgs {
+    const T* A;
+    int64_t lda, sA;
+    const T* x;
+    int64_t ldx, sx;
+    T* y;
+    int64_t ldy, sy;
+    T* ycopy;          // nullable; stride sy per batch entry, ldy
+    int M, K, nrhs, tri;
+    T alpha, beta;
+};
+
+template <typename T, int NR>
+__global__ __launch_bounds__(256) void gemv_t_kernel(GemvTArgs<T> p) {
+    __shared__ T red[4][64][NR];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t b = blockIdx.y;
+    const T* __restrict__ A = p.A + b * p.sA;
+    const T* __restrict__ x = p.x + b * p.sx;
+    T* __restrict__ y = p.y + b * p.sy;
+
+    if (p.ycopy != nullptr && blockIdx.x == 0) {
+        T* __restrict__ yc = p.ycopy + b * p.sy;
+        for (int idx = tid; idx < p.K * p.nrhs; idx += 256) {
+            const int i = idx / p.nrhs, c = idx % p.nrhs;
+            yc[(int64_t)i * p.ldy + c] = x[(int64_t)i * p.ldx + c];
+        }
+    }
+    const int c0 = blockIdx.x * 64;
+    const int j = c0 + lane;
+    const bool live = j < p.M;
+    T acc[NR];
+#pragma unroll
+    for (int c = 0; c < NR; ++c) acc[c] = T(0);
+    const int i0 = p.tri ? c0 : 0;
+    if (live) {
+        const T* __restrict__ col = A + j;
+        int i = i0 + wave;
+        // four rows of this wave in flight per step
+        for (; i + 12 < p.K; i += 16) {
+            T av[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) av[u] = col[(int64_t)(i + 4 * u) * p.lda];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int c = 0; c < NR; ++c)
+                    if (c < p.nrhs) acc[c] += av[u] * x[(int64_t)(i + 4 * u) * p.ldx + c];
+        }
+        for (; i < p.K; i += 4) {
+            const T av = col[(int64_t)i * p.lda];
+#pragma unroll
+            for (int c = 0; c < NR; ++c)
+                if (c < p.nrhs) acc[c] += av * x[(int64_t)i * p.ldx + c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NR; ++c) red[wave][lane][c] = acc[c];
+    __syncthreads();
+    if (wave == 0 && live) {
+#pragma unroll
+        for (int c = 0; c < NR; ++c) {
+            if (c < p.nrhs) {
+                const T s = (red[0][lane][c] + red[1][lane][c]) + (red[2][lane][c] + red[3][lane][c]);
+                T* yp = y + (int64_t)j * p.ldy + c;
+                T r = p.alpha * s;
+                if (p.beta != T(0)) r += p.beta * (*yp);
+                *yp = r;
+            }
+        }
+    }
+}
+
+template <typename T>
+int gemv_t_launch(int64_t M, int64_t K, int nrhs, T alpha, const T* A, int64_t lda, int64_t sA, const T* x, int64_t ldx, int64_t sx,
+                  T beta, T* y, int64_t ldy, int64_t sy, T* ycopy, int tri, int64_t batch, hipStream_t stream) {
+    if (nrhs > 8 || nrhs < 1) return GPK_ERR_ARG(3);
+    if (M > INT32_MAX || K > INT32_MAX) return GPK_ERR_ARG(1);
+    if (M <= 0 && ycopy == nullptr) return GPK_OK;
+    if (batch > 65535) return GPK_ERR_ARG(17);
+    GemvTArgs<T> g;
+    g.A = A; g.lda = lda; g.sA = sA;
+    g.x = x; g.ldx = ldx; g.sx = sx;
+    g.y = y; g.ldy = ldy; g.sy = sy;
+    g.ycopy = ycopy;
+    g.M = (int)(M > 0 ? M : 0); g.K = (int)K; g.nrhs = nrhs; g.tri = tri;
+    g.alpha = alpha; g.beta = beta;
+    int64_t gx = gpk_cdiv(g.M, 64);
+    if (gx < 1) gx = 1;
+    dim3 grid((unsigned)gx, (unsigned)batch);
+    if (nrhs == 1)
+        hipLaunchKernelGGL((gemv_t_kernel<T, 1>), grid, dim3(256), 0, stream, g);
+    else if (nrhs == 2)
+        hipLaunchKernelGGL((gemv_t_kernel<T, 2>), grid, dim3(256), 0, stream, g);
+    else if (nrhs <= 4)
+        hipLaunchKernelGGL((gemv_t_kernel<T, 4>), grid, dim3(256), 0, stream, g);
+    else
+        hipLaunchKernelGGL((gemv_t_kernel<T, 8>), grid, dim3(256), 0, stream, g);
+    GPK_CHECK_LAUNCH();
+    return GPK_OK;
+}
+
+// B <- L^{-T} B, nrhs <= 8: bottom-up sweep, one launch pair per sb-block (no cross-workgroup hand-off).  Block q:
+//   tmp = inv(L_qq)^T b_q;   b_q = tmp;   b[0:r0] -= L[q rows, 0:r0]^T tmp
+// reads L by block rows (contiguous rows), every element of the lower triangle once.  tmp: [batch][sb][nrhs].
+template <typename T>
+int gpk_trsv_t_launch(const T* L, int64_t n, int64_t ld, int64_t sL, const T* dinv_sb, int sb, T* B,
+                      int nrhs, int64_t ldb, int64_t sB, T* tmp, int64_t batch, hipStream_t stream) {
+    if (n <= 0 || nrhs <= 0 || batch <= 0) return GPK_OK;
+    if (!gpk_valid_sb(sb)) return GPK_ERR_ARG(6);
+    if (nrhs > 8) return GPK_ERR_ARG(8);
+    if (batch > 65535) return GPK_ERR_ARG(12);
+    if (tmp == nullptr) return GPK_ERR_ARG(11);
+    const int nsb = (int)gpk_cdiv(n, sb);
+    const int64_t per = (int64_t)sb * sb, ssb = (int64_t)nsb * per;
+    const int64_t st_tmp = (int64_t)sb * nrhs;
+    for (int q = nsb - 1; q >= 0; --q) {
+        const int64_t r0 = (int64_t)q * sb;
+        const int64_t rq = (n - r0 < sb) ? n - r0 : sb;
+        int st = gemv_t_launch<T>(rq, rq, nrhs, T(1), dinv_sb + q * per, sb, ssb, B + r0 * ldb, ldb, sB, T(0), tmp, nrhs, st_tmp,
+                                  (T*)nullptr, 1, batch, stream);
+        if (st) return st;
+        st = gemv_t_launch<T>(r0, rq, nrhs, T(-1), L + r0 * ld, ld, sL, tmp, nrhs, st_tmp, T(1), B, ldb, sB, B + r0 * ldb, 0, batch,
+                              stream);
+        if (st) return st;
+    }
+    return GPK_OK;
+}
+
+// X = L^{-T} B, many right-hand sides, out of place (B is used up as workspace): the recursive blocked solve of gpk_trsm_launch
+// run bottom-up --
+//   solve(q0, q1):  one block:  X_q = inv(L_qq)^T B_q                        (GEMM reading the merged inverse K x M: its transpose;
+//                                                                              zero for k < m, so the k loop starts at the tile row)
+//                   else:       solve(m, q1);  B[q0:m] -= L[m:q1, q0:m]^T X[m:q1]  (ONE GEMM, A read K x M);  solve(q0, m)
+template <typename T>
+int trsm_t_rec(const TrsmCtx<T>& c, int q0, int q1) {
+    const int64_t r0 = (int64_t)q0 * c.sb;
+    if (q1 - q0 == 1) {
+        const int64_t rq = (c.n - r0 < c.sb) ? c.n - r0 : c.sb;
+        return gpk_gemm_launch<T>(false, false, rq, c.nrhs, rq, T(1), c.dinv + q0 * c.per, c.sb, c.ssb, c.B + r0 * c.ldb, c.ldb, c.sB, T(0),
+                                  c.X + r0 * c.ldx, c.ldx, c.sX, c.batch, 2, c.stream);
+    }
+    int h = 1;
+    while (2 * h < q1 - q0) h *= 2;
+    const int m = q0 + h;
+    int st = trsm_t_rec<T>(c, m, q1);
+    if (st) return st;
+    const int64_t rm = (int64_t)m * c.sb;
+    const int64_t r1 = ((int64_t)q1 * c.sb < c.n) ? (int64_t)q1 * c.sb : c.n;
+    st = gpk_gemm_launch<T>(false, false, rm - r0, c.nrhs, r1 - rm, T(-1), c.L + rm * c.ld + r0, c.ld, c.sL, c.X + rm * c.ldx, c.ldx, c.sX,
+                            T(1), c.B + r0 * c.ldb, c.ldb, c.sB, c.batch, 0, c.stream);
+    if (st) return st;
+    return trsm_t_rec<T>(c, q0, m);
+}
+
+template <typename T>
+int gpk_trsm_t_launch(const T* L, int64_t n, int64_t ld, int64_t sL, const T* dinv_sb, int sb, T* B,
+                      int64_t nrhs, int64_t ldb, int64_t sB, T* X, int64_t ldx, int64_t sX, int64_t batch, hipStream_t stream) {
+    if (n <= 0 || nrhs <= 0 || batch <= 0) return GPK_OK;
+    if (!gpk_valid_sb(sb)) return GPK_ERR_ARG(6);
+    if (X == nullptr) return GPK_ERR_ARG(12);
+    if (ldx < nrhs) return GPK_ERR_ARG(13);
+    const int nsb = (int)gpk_cdiv(n, sb);
+    TrsmCtx<T> c;
+    c.L = L; c.n = n; c.ld = ld; c.sL = sL;
+    c.dinv = dinv_sb; c.sb = sb; c.per = (int64_t)sb * sb; c.ssb = (int64_t)nsb * c.per;
+    c.B = B; c.nrhs = nrhs; c.ldb = ldb; c.sB = sB;
+    c.X = X; c.ldx = ldx; c.sX = sX;
+    c.tmp = nullptr; c.st_tmp = 0;
+    c.batch = batch; c.stream = stream;
+    return trsm_t_rec<T>(c, 0, nsb);
+}
+
 #define GPK_INST(T)                                                                                 \
+    template int gpk_trsv_t_launch<T>(const T*, int64_t, int64_t, int64_t, const T*, int, T*, int, int64_t, int64_t, T*, int64_t,  \
+                                      hipStream_t);                                                 \
+    template int gpk_trsm_t_launch<T>(const T*, int64_t, int64_t, int64_t, const T*, int, T*, int64_t, int64_t, int64_t, T*,       \
+                                      int64_t, int64_t, int64_t, hipStream_t);                      \
     template int gpk_trtri_launch<T>(const T*, int64_t, int64_t, const T*, int, T*, int64_t, T*, hipStream_t); \
     template int gpk_trsv_step_launch<T>(const T*, int64_t, int64_t, const T*, int64_t, int64_t, T*, T*, T*, hipStream_t);  \
     template int gpk_trsv_batch_step_launch<T>(const T*, int64_t, int64_t, int64_t, const T*, int64_t, T*, int64_t, T*, int64_t, int, hipStream_t);  \

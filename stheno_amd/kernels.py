@@ -829,9 +829,10 @@ class PosteriorKernel(Kernel):
     """``k_ij(x, y) - k_zi(z, x)^T K_z^{-1} k_zj(z, y)`` (mlkernels.PosteriorKernel;
     constructed at ``observations.py:148-154,256-261``)."""
 
-    def __init__(self, k_ij, k_zi, k_zj, z, K_z, own_cross=False):
+    def __init__(self, k_ij, k_zi, k_zj, z, K_z, own_cross=False, exact=False):
         self.k_ij, self.k_zi, self.k_zj, self.z, self.K_z = k_ij, k_zi, k_zj, z, K_z
         self.own_cross = own_cross       # see _whiten
+        self.exact = exact               # exact conditioning on observations of the process itself (see _learnable_marginals)
 
     def num_outputs(self, x):
         return self.k_ij.num_outputs(x)
@@ -856,6 +857,9 @@ class PosteriorKernel(Kernel):
 
     def elwise(self, x, y=None, *, cache=None):
         x = uprank(x)
+        got = _learnable_marginals(None, self, x, cache)
+        if got is not None:
+            return got[1]
         out = self.k_ij.elwise(x)
         vx = _whiten(cache, self.K_z, self.k_zi, self.z, x, self.own_cross)
         if self.k_zi is self.k_zj:
@@ -907,17 +911,20 @@ class PosteriorMean(Mean):
     """``m_i(x) + k_zi(z, x)^T K_z^{-1} (y - m_z(z))`` (mlkernels.PosteriorMean;
     ``observations.py:161-168,270-277``), evaluated as ``(L^{-1} k_zx)^T (L^{-1} (y - m_z(z)))``."""
 
-    def __init__(self, m_i, m_z, k_zi, z, K_z, y, own_cross=False):
+    def __init__(self, m_i, m_z, k_zi, z, K_z, y, own_cross=False, exact=False):
         self.m_i, self.m_z, self.k_zi, self.z, self.K_z, self.y = m_i, m_z, k_zi, z, K_z, y
         self.own_cross = own_cross       # see _whiten
+        self.exact = exact               # see PosteriorKernel
         self._w = None
         self._r = None
+        self._r_detached = False         # the residual was formed under torch.no_grad() (cut off from a learnable mean / y)
 
     def _residual(self):
         if self._r is None:
             y = uprank(self.y)
             # (a zero mean: the residual IS the data -- nobody below writes into it)
             self._r = (y, y if (isinstance(self.m_z, ZeroMean) and torch.is_tensor(y) and not y.requires_grad) else y - self.m_z(self.z))
+            self._r_detached = not torch.is_grad_enabled()
         return self._r
 
     def _whitened_residual(self):
@@ -941,6 +948,9 @@ class PosteriorMean(Mean):
 
     def __call__(self, x, cache=None):
         x = uprank(x)
+        got = _learnable_marginals(self, None, x, cache)
+        if got is not None:
+            return got[0]
         rhs = None
         if self._w is None and self.own_cross and hasattr(self.K_z, "can_factor_with_rows") and x.dim() == 2:
             y, r = self._residual()
@@ -959,6 +969,92 @@ class PosteriorMean(Mean):
             v = v.plain()
         dot, _ = ops.get_backend().colreduce(v, w, want_dot=True, want_ss=False)
         return self.m_i(x) + dot[..., None]
+
+
+def _posterior_parts(pm, K_z, k, z, x, cache, own_cross):
+    """The plain HIP path of the posterior marginals, unchanged (``PosteriorMean.__call__`` / ``PosteriorKernel.elwise``): returns
+    ``(chol, w, v, mu, s)`` -- the factor, ``w = L^{-1} r`` (None without a mean), ``v = L^{-1} k(z, x)`` (or ``WhitenedT``),
+    ``mu = v^T w`` and ``s = |v_j|^2`` (N*,), the latter two from one pass over ``v``."""
+    rhs = None
+    if pm is not None and pm._w is None and own_cross and hasattr(K_z, "can_factor_with_rows"):
+        _, r = pm._residual()
+        if r.dim() == 2 and r.shape[-1] == 1 and not r.requires_grad:
+            rhs = (r, pm._took)
+    v = _whiten(cache, K_z, k, z, x, own_cross, rhs)
+    w = pm._whitened_residual() if pm is not None else None
+    be = ops.get_backend()
+    if isinstance(v, WhitenedT):
+        mu, s = be.rowreduce(v.zt, w, want_dot=w is not None, want_ss=True)
+    else:
+        mu = be.colreduce(v, w, want_dot=True, want_ss=False)[0] if w is not None else None
+        _, s = be.colreduce(v, want_ss=True)
+    return K_z.chol(), w, v, mu, s
+
+
+def _learnable_marginals(pm, pk, x, cache):
+    """Posterior mean / marginal variances of an EXACT posterior of one process under learnable quantities, through
+    ``autograd._PosteriorMarginals``: ``(mean column or None, marginal-variance column or None)`` for the posterior mean ``pm`` and /
+    or the posterior kernel ``pk`` at the test inputs ``x``.  None when nothing learnable is behind them, when grad is off, or when the
+    call is outside that path (pseudo-point posteriors, several processes, chained conditioning, batched inputs, a kernel that is no
+    scaled sum of primitives, dense noise): the plain path then runs exactly as before."""
+    if not torch.is_grad_enabled():
+        return None
+    src = pm if pm is not None else pk
+    if not getattr(src, "exact", False):
+        return None
+    K_z, k, z = src.K_z, src.k_zi, src.z
+    if pk is not None and not (pk.exact and pk.K_z is K_z and pk.z is z and pk.k_zi is k and pk.k_zj is k and pk.k_ij is k):
+        return None
+    from .matrix import KernelDense
+
+    if not isinstance(K_z, KernelDense) or K_z.kernel is not k:
+        return None
+    if not (torch.is_tensor(x) and torch.is_tensor(z) and x.dim() == 2 and z.dim() == 2 and x.shape[-1] == z.shape[-1]
+            and x.dtype == z.dtype and x.device == z.device):
+        return None
+    noise_vec = K_z.differentiable_noise()
+    if noise_vec is NotImplemented or (noise_vec is not None and noise_vec.dim() != 1):
+        return None
+    view = k.input_scaled_view()
+    if view is None:
+        return None
+    kern, scales = view
+    tt = kern.tensor_terms()
+    if not tt:
+        return None
+    from . import autograd as _ag
+
+    r = None
+    if pm is not None:
+        y, r = pm._residual()
+        if r.dim() != 2 or r.shape[-1] != 1:
+            return None
+        if pm._r_detached and not r.requires_grad:        # (formed under no_grad: form it again inside the graph)
+            r = y - pm.m_z(z)
+    learnable = (_ag.kernel_requires_grad(k) or x.requires_grad or z.requires_grad
+                 or (noise_vec is not None and noise_vec.requires_grad) or (r is not None and r.requires_grad))
+    if not learnable:
+        return None
+    sc = None if scales is None else scales.to(dtype=z.dtype, device=z.device)
+    zin = z if sc is None else z / sc
+    xin = x if sc is None else x / sc
+    if (zin.requires_grad or xin.requires_grad) and x.shape[-1] > 8:
+        raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
+                                  "are implemented for at most 8 input dimensions")
+    xd = x.detach()                  # (the plain path sees values only: the rows path stays open, one whitening serves mean and variance)
+    own_cross = src.own_cross
+
+    def run():
+        return _posterior_parts(pm, K_z, k, z, xd, cache, own_cross)
+
+    mu, s = _ag.posterior_marginals(kern, zin, xin, r, noise_vec, run)
+    mean = pm.m_i(x) + mu[..., None] if pm is not None else None
+    vd = None
+    if pk is not None:
+        # the value of k(x, x) from the fused launch (the plain path's bits), its gradient from the same sum written in torch
+        kt = _ag.kdiag_terms(tt, xin)
+        vd = (k.elwise(xd) + (kt - kt.detach())[..., None]) - s[..., None]
+    return mean, vd
 
 
 # ---------------------------------------------------------------------------
@@ -993,6 +1089,10 @@ def mean_var_diag(mean, kernel, x):
     cache = {}
     x = uprank(x)
     with deferred_checks():          # (see mean_var)
+        if isinstance(mean, PosteriorMean) and isinstance(kernel, PosteriorKernel):
+            got = _learnable_marginals(mean, kernel, x, cache)       # (under learnable quantities: ONE autograd node for both)
+            if got is not None:
+                return got
         m = _call_mean(mean, x, cache)
         vd = kernel.elwise(x, cache=cache) if _accepts_cache(kernel) else kernel.elwise(x)
     return m, vd

@@ -432,6 +432,21 @@ class Chol:
             out = self._refined(b.clone(memory_format=torch.contiguous_format), out)
         return out
 
+    def solve_t_(self, b):
+        """``L^{-T} b`` with the transposed factor (``b``: (..., n, nrhs), unit inner stride; used up: take the RETURN value) -- the
+        backward of the posterior marginals (``autograd._PosteriorMarginals``).  The merged inverses are those of :meth:`_blocks`.
+        No refinement step: ``config.refine_solves`` / ``wants_refinement`` apply to the forward solves only, the backward takes the
+        factor as it is."""
+        if b.shape[-2] != self.n:
+            raise ValueError(f"right-hand side has {b.shape[-2]} rows, the factor has order {self.n}")
+        sb, dsb = self._blocks(b.shape[-1])
+        return ops.get_backend().tri_solve_t_(self.l, dsb, sb, b)
+
+    def solve_t(self, b):
+        """``L^{-T} b`` as a new tensor (see :meth:`solve_t_`)."""
+        lb, bb = tuple(self.l.shape[:-2]), tuple(b.shape[:-2])
+        return self.solve_t_(b.expand((lb or bb) + tuple(b.shape[-2:])).clone(memory_format=torch.contiguous_format))
+
     def iqf_diag(self, b, source=None):
         """Column-wise ``|L^{-1} b|^2``: (..., nrhs).  ``source``: see :meth:`solve_residual`."""
         v = self.solve_residual(b, source)

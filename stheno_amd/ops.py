@@ -354,6 +354,35 @@ class HipBackend:
         self._st(code, "gpk_trsm_lower_to")
         return x
 
+    @_on_operand_device
+    def tri_solve_t_(self, l, dinv_sb, sb, b):
+        """``L^{-T} b`` with the TRANSPOSED factor (``gpk_trsv_lower_t`` for up to 8 columns, ``gpk_trsm_lower_t`` above), the mirror of
+        :meth:`tri_solve_`: ``b`` (..., n, nrhs), unit inner stride, is OVERWRITTEN (with the solution for up to 8 columns, used up as
+        workspace otherwise): use the return value."""
+        l3, _ = _as3(l)
+        b3, _ = _as3(b)
+        if b3.data_ptr() != b.data_ptr():
+            raise ValueError("tri_solve_t_ needs a right-hand side with unit inner stride")
+        self._check(l3, b3, dinv_sb)
+        B, n, _ = l3.shape
+        nrhs = b3.shape[2]
+        if b3.shape[0] != B or b3.shape[1] != n:
+            raise ValueError("right-hand side does not match the factor")
+        if n == 0 or nrhs == 0:
+            return b
+        if nrhs <= 8:
+            tmp = torch.empty((B * sb * nrhs + 16,), dtype=b.dtype, device=b.device)
+            code = self.lib.gpk_trsv_lower_t(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
+                                             self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(tmp), B, self._stream())
+            self._st(code, "gpk_trsv_lower_t")
+            return b
+        x = torch.empty(b.shape, dtype=b.dtype, device=b.device)
+        x3, _ = _as3(x)
+        code = self.lib.gpk_trsm_lower_t(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
+                                         self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(x3), _ld(x3), _bs(x3), B, self._stream())
+        self._st(code, "gpk_trsm_lower_t")
+        return x
+
     # -- products ------------------------------------------------------------
     @_on_operand_device
     def trtri(self, l, dinv_sb, sb):
