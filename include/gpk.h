@@ -126,9 +126,10 @@ int gpk_potrf(int dtype, void* a, int64_t n, int64_t ld, int64_t sa, int64_t bat
  * The helper stream is forked from / joined to `stream` with events; under stream capture it joins the capture. */
 /* gpk_potrf with ONE right-hand side per matrix solved along (round 6): `b` holds batch vectors of n entries (unit stride, sb elements
  * apart), overwritten by L^{-1} b -- what gpk_trsv_lower(l, ..., sb = 128, nrhs = 1) would compute behind the factorisation.
- * Batches that take the mixed-phase steps (fp32, >= 64 aligned matrices) run each 128-column step's share of the sweep on a side
- * stream as soon as that block column is final, beside the MFMA-bound launches of the next step: the sweep's HBM traffic (the factor
- * read once: 4.3 GB and 0.75 ms for 512 x 2048^2 fp32) hides under the factorisation.  Every other shape factorises, then sweeps.
+ * Batches that take the mixed-phase steps (fp32, >= 64 aligned matrices) do the sweep inside those steps: the diagonal-block launch
+ * of each 128-column step turns that block of b into inv(L_jj) b_j, and every solve tile of the step subtracts its 128 x 128 tile of
+ * L times that block from its own 128 entries of b, reading back the tile it has just stored -- no separate pass over the factor.
+ * Every other shape factorises, then sweeps with gpk_trsv_lower (sb = 128) on `stream`.
  * `tmp`: batch * 128 + GPK_TRSV_CTRL_ELEMS elements; dinv as for gpk_potrf (required).
  * Replaces `B.cholesky` + the solve inside `B.iqf_diag(K, y - m)`: stheno/random.py:272-279 (batched: tests/model/test_cases.py:134-176). */
 int gpk_potrf_rhs(int dtype, void* a, int64_t n, int64_t ld, int64_t sa, int64_t batch, void* dinv, int* info, int nbo, void* b, int64_t sb,
@@ -201,8 +202,7 @@ int gpk_trsm_lower_to(int dtype, const void* l, int64_t n, int64_t ld, int64_t s
                       int64_t sx_stride, int64_t batch, void* stream);
 
 /* B <- L^{-1} B, nrhs <= 8 (GEMV sweep, HBM-bound).  tmp: batch * sb * nrhs + GPK_TRSV_CTRL_ELEMS elements (16-byte aligned;
- * the extra elements hold the control words of the single-launch sweep -- one right-hand side of one factor runs as ONE resident
- * launch whose workgroups meet at grid barriers; the call zeroes them).
+ * the extra elements are reserved: they held the control words of a single-launch sweep that has been removed).
  * Replaces the solve inside `B.iqf_diag(var, y - mean)`: stheno/random.py:276,
  * stheno/model/observations.py:335. */
 #define GPK_TRSV_CTRL_ELEMS 16
@@ -387,10 +387,8 @@ int gpk_mfma_peak(int dtype, double min_ms, int waves_per_simd, double* tflops, 
  * (`gpk_selftest --set KEY VALUE`).  key 1: use 64x64 GEMM tiles below this many 128-tiles; 6: look-ahead overlaps while the
  * trailing matrix has at least this many rows; 7: 0 = look-ahead algorithm on one stream, 1 = with the helper stream; 8: the
  * persistent update takes 64x64 tiles below this many 128-tiles; 9: gpk_potrf_la finishes the last this-many rows with the plain
- * algorithm (0 = 6144); 10: panel GEMM of gpk_potrf_la as 0 = plain launch, 1 / 2 = persistent (paired tiles); 11: strip written
- * last; 12: 1 = row-band kernel-matrix kernel, 0 = one tile per workgroup; 17: 1 = one-workgroup-per-matrix TRSV for batches of
- * small factors; 18: 1 = the CUs reserved for the look-ahead chain rejoin the trailing update once the chain is done;
- * 20: gpk_tune_tile_prof stamps only the v-th persistent launch since this knob was set (-1 = every launch); 31: quarter tiles for
+ * algorithm (0 = 6144); 12: 1 = row-band kernel-matrix kernel, 0 = one tile per workgroup; 17: 1 = one-workgroup-per-matrix TRSV
+ * for batches of small factors; 20: gpk_tune_tile_prof stamps only the v-th persistent launch since this knob was set (-1 = every launch); 31: quarter tiles for
  * the last partial round of a 128-tile GEMM launch; 32: fused panel-step kernel (batched / fallback path); 34: compact 1-D grid for
  * lower-triangle kernel matrices; 36: triangular-operand fragment skipping in panel solves; 37: 1 = one pipelined launch per panel
  * for single matrices, 0 = diagonal-block kernel + panel-step kernel per 128 columns (the batched path's steps); 38: the rest of a
@@ -398,11 +396,17 @@ int gpk_mfma_peak(int dtype, double min_ms, int waves_per_simd, double* tflops, 
  * third of the CUs); 40 / 41: the look-ahead's update of the next diagonal block is the first segment of the trailing update while
  * that has at least (40) rows and the outer block is at most (41) wide; 42: small products with a lower-triangular A (the leaves of
  * the recursive solve) as pairs of 32-row tiles with equal K per workgroup; 45: batched 128-tile GEMM launches as a 1-D grid with all
- * tiles of a matrix on one XCD; 53: batched factorisations take the mixed-phase steps (0 = lockstep launches, 1 = fp32, 2 = fp64 too);
- * 54: ... from this many matrices on; 55: tasks between a matrix's solves and its update tiles in the queue order; 56: bit 0 = update
- * tiles do not pull their C tile into the L2 before they wait, bit 2 = solve tiles publish behind an agent-scope release; 57: fp32
- * batches of more matrices than CUs take the diagonal-block kernel compiled for two workgroups per CU.  (Removed in round 4 with the code they selected: 2 / 4 /
- * 13 -- XCD super-tile, row-pair and column-major tile orders -- and 30, the 256-thread diagonal-block kernel of rounds 1-2.)
+ * tiles of a matrix on one XCD; 47: gpk_potrf_la aggregates its trailing updates -- a column block is brought up to date every
+ * this-many outer steps (1 = every step); 48: ... only while the trailing matrix has at least this many rows; 51: fp64 kernel
+ * matrices with a square root (Matern) take the row-band kernel too; 52: panel width of the pipelined plain factorisation of one
+ * matrix above n = 4096; 53: batched fp32 factorisations take the mixed-phase steps (0 = lockstep launches, 1 = mixed-phase; fp64
+ * always takes the lockstep launches); 54: ... from this many matrices on; 55: tasks between a matrix's solves and its update tiles
+ * in the queue order; 57: fp32 batches of more matrices than CUs take the diagonal-block kernel compiled for two workgroups per CU.
+ * (Removed in round 4 with the code they selected: 2 / 4 / 13 -- XCD super-tile, row-pair and column-major tile orders -- and 30,
+ * the 256-thread diagonal-block kernel of rounds 1-2.  Removed after rounds 5 and 6, measured slower or flat: 10 / 11 / 18 -- the
+ * persistent panel GEMM of gpk_potrf_la, the strip's place in the trailing update, the reserved CUs' rejoin switch -- 49 / 50, the
+ * single-launch sweep of gpk_trsv_lower, 56 and 60, development switches and the left-looking update of the mixed-phase steps, and
+ * 58 / 59, chunked task claims of the persistent update; 53 lost its fp64 value 2.)
  * gpk_tune_diag_prof: device buffer (32 int64 per diagonal block, or NULL) for cycle / wall-clock stamps of the diagonal-block
  * kernel and of the pipelined panel's chain and critical tasks (read by `gpk_selftest --diagprof`). */
 void gpk_tune(int key, int64_t value);

@@ -2,7 +2,7 @@
 scripts/collect_pmc.py (`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, `--kernel-trace` only; FETCH_SIZE doubled for gfx950) around a native
 binary -- A/B runs of the self-test's timing modes with a knob set.
 
-    python $REPO/scripts/pmc_native.py OUT.json -- ./gpk_selftest --set 58 1 --perf-rows f64 16384 2048 1024 0 2
+    python $REPO/scripts/pmc_native.py OUT.json -- ./gpk_selftest --set 47 1 --perf-rows f64 16384 2048 1024 0 2
 """
 import csv, glob, json, os, subprocess, sys
 

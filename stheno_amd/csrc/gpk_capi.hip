@@ -23,7 +23,7 @@ static int update2(const gpk_update_t* upd, int nupd, double alpha, void* ctrl, 
     GpkSeg<T> seg[2];
     for (int i = 0; i < nupd; ++i)
         seg[i] = GpkSeg<T>{upd[i].m, upd[i].n, upd[i].k, (const T*)upd[i].a, upd[i].lda, (const T*)upd[i].b, upd[i].ldb,
-                           (const T*)upd[i].cin, upd[i].ldcin, (T*)upd[i].c, upd[i].ldc, upd[i].lower_only, 0};
+                           (const T*)upd[i].cin, upd[i].ldcin, (T*)upd[i].c, upd[i].ldc, upd[i].lower_only};
     return gpk_gemm_persist_launch<T>(seg, nupd, (T)alpha, (unsigned*)ctrl, reserve, stream);
 }
 

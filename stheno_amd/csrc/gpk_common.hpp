@@ -147,7 +147,6 @@ struct GpkSeg {
     const T* Cin; int64_t ldcin;
     T* C; int64_t ldc;
     int lower_only;
-    int tri_b;      // B (N x K) is lower triangular: k stops at the column tile's last column (2: pair column tiles c, n-1-c)
     int signal;     // every finished tile of this segment is announced: ctrl[2] += 1 behind an agent-scope release (somebody polls it)
     // Round 5 (aggregated trailing updates of the look-ahead Cholesky): a square lower-only segment restricted to COLUMN GROUPS --
     // group g = columns [g grp, (g + 1) grp) and the rows from g grp down; bit g of colmask set = the group is part of the segment
@@ -264,9 +263,6 @@ int gpk_gemv_launch(int64_t M, int64_t K, int nrhs, T alpha, const T* A, int64_t
 template <typename T>
 int gpk_trsv_step_launch(const T* W, int64_t ldw, int64_t rq, const T* Lbelow, int64_t ld, int64_t nbelow, T* bq, T* bbelow, T* tmp,
                          hipStream_t stream);
-template <typename T>
-int gpk_trsv_batch_step_launch(const T* L, int64_t n, int64_t ld, int64_t sL, const T* dinv, int64_t sD, T* B, int64_t sB, T* tmp,
-                               int64_t batch, int q, hipStream_t stream);
 // gpk_potrf + one right-hand side per matrix solved along (gpk_potrf_rhs in gpk.h)
 template <typename T>
 int gpk_potrf_rhs_launch(T* A, int64_t n, int64_t ld, int64_t batch, int64_t bstride, T* dinv, int* info, int nbo, T* B, int64_t sB, T* tmp,

@@ -184,7 +184,6 @@ struct PersistArgs {
     unsigned* ctrl;
     int reserve;
     int max_leave;
-    int chunks;               // tasks are claimed in chunks of 64 per XCD (gpk_claim_task): ctrl[8 + x] = XCD x's counter, ctrl[16 + 4 x ..] its slots
     unsigned rkeys[8];
     long long* prof;          // development aid: 8 slots (6 stamps) for each of the first 8 tiles of every workgroup (nullable)
 };
@@ -199,12 +198,6 @@ __device__ __forceinline__ void persist_body(const PersistArgs<T>& p, char* smem
     typedef __attribute__((address_space(3))) volatile int lds_word_t;
     lds_word_t& s_tile = *(lds_word_t*)(uint32_t)(uintptr_t)(smem + TS * 128);
     const int tid = threadIdx.x;
-    unsigned xcc0;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc0));
-    xcc0 &= 7u;
-    unsigned* const cl_ctr = p.chunks ? &p.ctrl[8 + xcc0] : &p.ctrl[0];         // what a claim increments (gpk_claim_task)
-    unsigned* const ch_ctr = p.chunks ? &p.ctrl[0] : nullptr;
-    unsigned* const ch_slots = p.chunks ? &p.ctrl[16 + 4 * xcc0] : nullptr;
     if (p.reserve) {
         if (tid == 0) {
             unsigned xcc, hw;
@@ -228,7 +221,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs<T>& p, char* smem
     // tile drain while the next one starts (a __syncthreads() here waited 20-35 us for them, profiles/r04_gemm_checks_tileprof_1.log).
     auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     auto claim_now = [&]() -> int {
-        if (tid == 0) s_tile = gpk_claim_task(cl_ctr, ch_ctr, ch_slots);
+        if (tid == 0) s_tile = gpk_claim_task(&p.ctrl[0]);
         lds_barrier();
         const int v = __builtin_amdgcn_readfirstlane(s_tile);     // uniform by construction; tell the compiler (scalar loads of the segment)
         lds_barrier();
@@ -251,6 +244,8 @@ __device__ __forceinline__ void persist_body(const PersistArgs<T>& p, char* smem
         if (g.tri_k_lo_b && g.pair_cols) {
             // B lower triangular in k: column tile c runs c + 1 blocks of k.  One task = the tiles c and
             // tiles_n - 1 - c of one tile row, tiles_n + 1 blocks together whatever c is: equal tasks.
+            // (No launcher sets pair_cols any more.  The branch stays: without it the compiler schedules the tile body differently
+            // and the fp64 128-tile kernels spill VGPRs -- 36 and 421 -- where they spill nothing today.)
             const int half = g.tiles_n >> 1;
             k.ti = tl / half;
             k.tj = tl - k.ti * half;
@@ -302,7 +297,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs<T>& p, char* smem
 #pragma unroll 1
             for (int r = 0; r < k.reps; ++r)     // ONE call site: a second inlined copy of the tile body costs registers
                 gemm_tile<T, TS, true, true, EDGE, 1, NW, false, 1>(g, k.ti, (k.reps == 2 && r == 0) ? g.tiles_n - 1 - k.tj : k.tj, 0, 0, smem, pr,
-                                                                    (r == k.reps - 1) ? pf_c : nullptr, pf_ld, (r == k.reps - 1) ? cl_ctr : nullptr, &nxt, ch_ctr, ch_slots);
+                                                                    (r == k.reps - 1) ? pf_c : nullptr, pf_ld, (r == k.reps - 1) ? &p.ctrl[0] : nullptr, &nxt);
             if (p.sig[k.sgi]) {                  // somebody outside this launch waits for the tiles of this segment (the look-ahead's next chain)
                 gpk_barrier_stores_done();     // every wave's stores of the tile are out
                 if (tid == 0) {
@@ -312,7 +307,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs<T>& p, char* smem
                 }
             }
         }
-        if (!ok && tid == 0) nxt = gpk_claim_task(cl_ctr, ch_ctr, ch_slots);      // (no full tile body ran: a quarter tile of the last round, an empty task)
+        if (!ok && tid == 0) nxt = gpk_claim_task(&p.ctrl[0]);      // (no full tile body ran: a quarter tile of the last round, an empty task)
         if (tid == 0) s_tile = nxt;
         lds_barrier();
         t = tn;
@@ -391,8 +386,6 @@ namespace {
 long long* g_tile_prof = nullptr;       // development aid (gpk_tune_tile_prof)
 int64_t g_tile_prof_only = -1;          // tuning knob (gpk_tune(20, v)): stamp only the v-th persistent launch since the knob was set (-1: every one)
 int64_t g_tile_prof_count = 0;
-GPK_KNOB(int, g_persist_chunks, 0);              // tuning knob (gpk_tune(58, v)): the persistent update hands its tiles out in chunks of 64 per XCD (gpk_claim_task)
-GPK_KNOB(int64_t, g_persist_chunks_min, 2048);   // tuning knob (gpk_tune(59, v)): ... from this many tiles on
 GPK_KNOB(int64_t, g_persist_small_below, 512);   // tuning knob (gpk_tune(8, v)): the persistent update takes 64x64 tiles below this many 128-tiles
 int g_cu_count[64] = {0};
 int device_cus() {
@@ -413,8 +406,6 @@ void gpk_set_tile_prof(long long* dev_buf) { g_tile_prof = dev_buf; }
 void gpk_tune_gemm(int key, int64_t value) {
     if (key == 1) GPK_KNOB_SET(g_small_tile_below = value;);
     if (key == 8) GPK_KNOB_SET(g_persist_small_below = value;);
-    if (key == 58) GPK_KNOB_SET(g_persist_chunks = (int)value;);
-    if (key == 59) GPK_KNOB_SET(g_persist_chunks_min = value;);
     if (key == 31) GPK_KNOB_SET(g_split_tail = (int)value;);
     if (key == 36) GPK_KNOB_SET(g_trib = (int)value;);
     if (key == 42) GPK_KNOB_SET(g_trilo_pairs = (int)value;);
@@ -777,7 +768,7 @@ int gpk_gemm_persist_launch(const GpkSeg<T>* segs, int nseg, T alpha, unsigned* 
         if (q.ldc >= GPK_C_LD_MAX || q.ldcin >= GPK_C_LD_MAX) return GPK_ERR_ARG(1);
         if (q.colmask != 0) {        // column groups of a square lower-only problem
             // (M > N: rows below the square part -- the look-ahead Cholesky carries the rows of K(x*, x) under the matrix it factorises)
-            if (!q.lower_only || q.M < q.N || q.tri_b || q.grp < 128 || q.grp % 128 != 0) return GPK_ERR_ARG(1);
+            if (!q.lower_only || q.M < q.N || q.grp < 128 || q.grp % 128 != 0) return GPK_ERR_ARG(1);
             t128 += striped_tiles(q.M, q.N, 128, q.grp, q.colmask, nullptr);
             continue;
         }
@@ -806,15 +797,13 @@ int gpk_gemm_persist_launch(const GpkSeg<T>* segs, int nseg, T alpha, unsigned* 
         g.lower_only = q.lower_only ? 1 : 0;
         g.tri_k = g.tri_k_lo = 0;
         g.colscale = nullptr; g.colss = nullptr; g.ldss = 0; g.xcd_batch = 0; g.xcd_tiles = 0;
-        g.tri_k_lo_b = q.tri_b ? 1 : 0;
+        g.tri_k_lo_b = 0; g.pair_cols = 0;
         const bool aligned = ((uintptr_t)q.A % 16 == 0) && ((uintptr_t)q.B % 16 == 0) && (q.lda % VEC == 0) &&
                              (q.ldb % VEC == 0);
         g.vec_ok = aligned ? 1 : 0;
         edge = edge || !aligned || (q.M % ts) || (q.N % ts) || (q.K % BK) || q.lda >= GPK_PIPE_LD_MAX || q.ldb >= GPK_PIPE_LD_MAX;
         const bool tri = g.lower_only && g.tiles_m == g.tiles_n;
         int64_t nt = tri ? (int64_t)g.tiles_m * (g.tiles_m + 1) / 2 : (int64_t)g.tiles_m * g.tiles_n;
-        g.pair_cols = (q.tri_b == 2 && !g.lower_only && g.tiles_n >= 2 && g.tiles_n % 2 == 0) ? 1 : 0;
-        if (g.pair_cols) nt = (int64_t)g.tiles_m * (g.tiles_n / 2);
         g.colmask = q.colmask; g.grp_tiles = q.colmask != 0 ? (int)(q.grp / ts) : 0;
         double area = 0;            // elements of C the segment updates (striped segments)
         if (q.colmask != 0) nt = striped_tiles(q.M, q.N, ts, q.grp, q.colmask, &area);
@@ -823,7 +812,7 @@ int gpk_gemm_persist_launch(const GpkSeg<T>* segs, int nseg, T alpha, unsigned* 
         pa.sig[live] = q.signal ? 1 : 0;
         if (q.signal && saved != nullptr) saved->signal_tiles += (int)nt;
         total += nt;
-        flops += q.colmask != 0 ? 2.0 * area * (double)q.K : (q.lower_only || q.tri_b ? 1.0 : 2.0) * (double)q.M * (double)q.N * (double)q.K;
+        flops += q.colmask != 0 ? 2.0 * area * (double)q.K : (q.lower_only ? 1.0 : 2.0) * (double)q.M * (double)q.N * (double)q.K;
         ++live;
     }
     if (total > INT32_MAX / 2) return GPK_ERR_ARG(1);
@@ -834,7 +823,6 @@ int gpk_gemm_persist_launch(const GpkSeg<T>* segs, int nseg, T alpha, unsigned* 
     pa.ntasks = (int)total;
     pa.split_from = INT32_MAX;
     pa.ctrl = ctrl;
-    pa.chunks = (g_persist_chunks && total >= g_persist_chunks_min) ? 1 : 0;
     pa.prof = nullptr;
     if (g_tile_prof != nullptr) {
         if (g_tile_prof_only < 0 || g_tile_prof_count == g_tile_prof_only) pa.prof = g_tile_prof;
@@ -860,11 +848,9 @@ int gpk_gemm_persist_launch(const GpkSeg<T>* segs, int nseg, T alpha, unsigned* 
         }
     }
     if (g_split_tail && ts == 128 && total > gridx) {        // the last, partial round as quarter tiles (see gpk_gemm_launch2)
-        bool plain = true;
-        for (int i = 0; i < live; ++i) plain = plain && !pa.seg[i].pair_cols && !pa.seg[i].tri_k_lo_b;
         const int64_t workers = gridx - pa.max_leave;
         const int64_t rem = total % workers;
-        if (plain && workers > 0 && rem > 0 && 2 * rem <= workers) {
+        if (workers > 0 && rem > 0 && 2 * rem <= workers) {
             pa.split_from = (int)(total - rem);
             pa.ntasks = (int)(total + 3 * rem);
         }

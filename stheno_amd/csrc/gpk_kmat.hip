@@ -66,9 +66,6 @@ template <>
 __device__ __forceinline__ double gpk_exp<double>(double x) { return gpk_exp_neg(x); }   // every argument on this path is <= 0
 template <>
 __device__ __forceinline__ float gpk_exp<float>(float x) { return expf(x); }
-#ifndef GPK_KMAT_R4_MATH
-#define GPK_KMAT_R4_MATH 0       // 1: round 4's fp64 exp (degree-13 polynomial) and sqrt (two Goldschmidt steps), for `make ab`
-#endif
 template <typename T>
 __device__ __forceinline__ T gpk_sqrtk(T x);
 // sqrt of a squared distance times a positive constant (x >= 0, often exactly 0 on the diagonal): the hardware rsq estimate
@@ -85,11 +82,6 @@ __device__ __forceinline__ double gpk_sqrtk<double>(double x) {
     double e = fma(-h, g, 0.5);
     g = fma(g, e, g);
     h = fma(h, e, h);
-#if GPK_KMAT_R4_MATH
-    e = fma(-h, g, 0.5);
-    g = fma(g, e, g);
-    h = fma(h, e, h);
-#endif
     return fma(fma(-g, g, xc), h, g);
 }
 template <>
@@ -340,7 +332,7 @@ __device__ __forceinline__ double gpk_exp_neg_tab(double a, const double* tab) {
     u = fma(u, r, 1.0);
     return ldexp(fma(t, u * r, t), ni >> 7);
 }
-__device__ __forceinline__ double gpk_exp_neg_t(double a, const double* tab) { return GPK_KMAT_R4_MATH ? gpk_exp_neg(a) : gpk_exp_neg_tab(a, tab); }
+__device__ __forceinline__ double gpk_exp_neg_t(double a, const double* tab) { return gpk_exp_neg_tab(a, tab); }
 __device__ __forceinline__ float gpk_exp_neg_t(float a, const float*) { return gpk_exp_neg(a); }
 
 template <typename T, int PROG>
@@ -372,7 +364,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     __shared__ T xs[TM * DC];
     __shared__ __attribute__((aligned(16))) T ys[2][DC * TNP];   // Y tile, dimension-major: ys[j][c]
     constexpr bool ETAB = sizeof(T) == 8 && PROG != PROG_GENERIC;  // fp64: exp through the 2^(j/128) table (gpk_exp_neg_tab)
-    constexpr bool PK32 = sizeof(T) == 4 && PROG != PROG_GENERIC && !GPK_KMAT_R4_MATH;   // fp32: two values per instruction
+    constexpr bool PK32 = sizeof(T) == 4 && PROG != PROG_GENERIC;   // fp32: two values per instruction
     __shared__ T etab[ETAB ? 128 : 1];
 
     const int tid = threadIdx.x, lane = tid & 63;

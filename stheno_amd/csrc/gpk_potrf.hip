@@ -965,7 +965,6 @@ struct BatchStepArgs {
     int tn, tm;      // 128-column tiles of the updated region; 128-row tiles below block jn (= solves per matrix)
     int nU;          // update tiles per matrix
     int lag;
-    int opts;        // development (knob 56): 1 = an update tile does not pull its C tile into the L2 before it waits, 4 = solve tiles publish behind an agent-scope release
     T* rhs;          // round 6 (gpk_potrf_rhs): one right-hand side per matrix (nullable); block jn of it holds inv(L_jj) b_j (the diagonal-block kernel)
     int64_t srhs;
 };
@@ -1012,10 +1011,6 @@ __global__ __launch_bounds__(256, 2) void batch_mix_kernel(BatchStepArgs<T> p) {
         gemm_tile<T, 128, true, true, false, 1, 4, true>(g, r, 0, m, 0, smem);
         gpk_barrier_stores_done();            // every wave's stores of the tile are acknowledged
         if (tid == 0) {
-            if (p.opts & 4) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
             __hip_atomic_fetch_add(batch_ctrl(p, m), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned seen = __hip_atomic_fetch_or(home, mybit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | mybit;
             if (seen & (seen - 1u)) atomicExch(p.info + qx, -2);
@@ -1071,7 +1066,7 @@ __global__ __launch_bounds__(256, 2) void batch_mix_kernel(BatchStepArgs<T> p) {
         first_look = __hip_atomic_load(batch_ctrl(p, m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_or(home, mybit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (result unused: no wait)
     }
-    if (!(p.opts & 1)) {
+    {
         // the C tile does not depend on the solves: pull it into the L2 while thread 0 looks at the counter (one dword of every 128-byte line)
         constexpr int LPR = 128 * (int)sizeof(T) / 128;
         const T* ct = g.Cin + (int64_t)m * p.bstride + (int64_t)ti * GPK_DB * p.ld + (int64_t)tj * GPK_DB;
@@ -1340,10 +1335,9 @@ int potrf_panel_any(const PanelCtx<T>& x, int64_t c0, int64_t w) {
 // block that receives cycle-counter stamps of the diag kernel's phases.
 void gpk_set_diag_prof(long long* dev_buf) { g_diag_prof = dev_buf; }
 
-GPK_KNOB(int, g_batch_mixed, 1);             // tuning knob (gpk_tune(53, v)): batches of aligned matrices take the mixed-phase steps (1: fp32 only -- the fp64 kernel, two tile bodies at 256 registers, spills; 2: fp64 too)
+GPK_KNOB(int, g_batch_mixed, 1);             // tuning knob (gpk_tune(53, v)): batches of aligned fp32 matrices take the mixed-phase steps (0: the lockstep launches;
+                                             // fp64 always takes those: its kernel, two tile bodies at 256 registers, spills)
 GPK_KNOB(int64_t, g_batch_mixed_min, 64);    // tuning knob (gpk_tune(54, v)): ... from this many matrices on
-GPK_KNOB(int, g_batch_left, 0);              // tuning knob (gpk_tune(60, v)): the mixed-phase steps update left-looking inside an outer panel (see potrf_batched_mixed)
-GPK_KNOB(int, g_batch_opts, 0);              // tuning knob (gpk_tune(56, v)): development switches of batch_mix_kernel (BatchStepArgs::opts)
 GPK_KNOB(int, g_batch_lag, 96);              // tuning knob (gpk_tune(55, v)): tasks between a matrix's solves and its update tiles, at least (32 / 96 / 256 / 512: 14.70 / 14.51 / 14.60 / 14.69 ms)
 
 // A stream created with a CU mask (hipExtStreamCreateWithCUMask) may not see every XCD, and the mixed-phase steps rest on block L
@@ -1409,11 +1403,6 @@ static int potrf_batched_mixed(T* A, int64_t n, int64_t ld, int64_t batch, int64
         const int jl = jn % npb;                          // block jn inside its outer panel
         if (jl == npb - 1) {                              // the panel is complete: its rank-nbo update of everything behind it
             p.K = nbo; p.tn = p.tm;
-        } else if (g_batch_left) {
-            // LEFT-LOOKING inside the outer panel: only the NEXT block column, with every column of the panel solved so far (128 (jl + 1)
-            // deep) -- tm tiles per step instead of the halving's tm / 2 tm - 1 / tm tiles at depths 128 / 256 / 128: the same flops in
-            // fewer, deeper visits of the panel's C tiles (a visit costs ~16 us whatever its depth)
-            p.K = GPK_DB * (jl + 1); p.tn = 1;
         } else {
             int z = 0;
             while ((jl >> z) & 1) ++z;                    // trailing ones: the halving level that block closes
@@ -1422,7 +1411,6 @@ static int potrf_batched_mixed(T* A, int64_t n, int64_t ld, int64_t batch, int64
         }
         p.nU = p.tm;
         for (int ti = 1; ti < p.tm; ++ti) p.nU += (ti < p.tn - 1) ? ti : p.tn - 1;
-        p.opts = g_batch_opts;
         p.lag = (g_batch_lag + p.tm + p.nU - 1) / (p.tm + p.nU);
         const int per_xcd = (int)((batch + 7) / 8);
         if (p.lag > per_xcd) p.lag = per_xcd;
@@ -1457,11 +1445,13 @@ static int potrf_plain(T* A, int64_t n, int64_t ld, int64_t batch, int64_t bstri
     const int64_t nblk = gpk_cdiv(n, GPK_DB);
     const int64_t dstride = nblk * GPK_DB * GPK_DB;
 
-    // batches of aligned matrices: one mixed-phase launch per 128-column step instead of lockstep launches per phase
-    if (g_batch_mixed && batch >= g_batch_mixed_min && rows == n && dinv != nullptr && n % GPK_DB == 0 && n >= 4 * GPK_DB && nbo <= n &&
-        (sizeof(T) == 4 || g_batch_mixed >= 2) && n <= 64 * 1024 && stream_has_all_cus(stream) && ld % Traits<T>::VEC == 0 && bstride % Traits<T>::VEC == 0 && (uintptr_t)A % 16 == 0 &&
-        (uintptr_t)dinv % 16 == 0 && ld < GPK_PIPE_LD_MAX && batch <= INT32_MAX / 8)
-        return potrf_batched_mixed<T>(A, n, ld, batch, bstride, dinv, dstride, info, nbo, info_base, stream, rhs_ride);
+    // batches of aligned fp32 matrices: one mixed-phase launch per 128-column step instead of lockstep launches per phase
+    if constexpr (sizeof(T) == 4) {
+        if (g_batch_mixed && batch >= g_batch_mixed_min && rows == n && dinv != nullptr && n % GPK_DB == 0 && n >= 4 * GPK_DB && nbo <= n &&
+            n <= 64 * 1024 && stream_has_all_cus(stream) && ld % Traits<T>::VEC == 0 && bstride % Traits<T>::VEC == 0 && (uintptr_t)A % 16 == 0 &&
+            (uintptr_t)dinv % 16 == 0 && ld < GPK_PIPE_LD_MAX && batch <= INT32_MAX / 8)
+            return potrf_batched_mixed<T>(A, n, ld, batch, bstride, dinv, dstride, info, nbo, info_base, stream, rhs_ride);
+    }
 
     PanelCtx<T> ctx{A, n, ld, batch, bstride, dinv, dstride, info, stream, info_base};
     ctx.rows = rows;
@@ -1545,9 +1535,6 @@ LaDevice g_la_dev[64];
 GPK_KNOB(int64_t, g_la_min_rows, 2048);     // tuning knob (gpk_tune(6, v)): overlap while the trailing matrix has >= this many rows
 GPK_KNOB(int64_t, g_la_tail_rows, 0);       // tuning knob (gpk_tune(9, v)): the last this-many rows (and matrices up to this order) take the plain path;
                                   // 0 = 6144 (with the pipelined plain panels: fp64 N = 16384 26.6 ms at 6144, 27.6 at 4096, 27.0 at 8192; fp32 nb = 512 N = 16384 15.5 / 15.7)
-GPK_KNOB(int, g_la_ps_mode, 0);             // tuning knob (gpk_tune(10, v)): panel GEMM as 0 = plain launch, 1 = persistent, 2 = persistent with paired column tiles
-GPK_KNOB(int, g_la_strip_last, 1);          // tuning knob (gpk_tune(11, v))
-GPK_KNOB(int, g_la_rejoin, 1);              // tuning knob (gpk_tune(18, v)): reserved CUs rejoin the trailing update after the chain
 GPK_KNOB(int, g_la_mode, 1);                // tuning knob (gpk_tune(7, v)): 0 = same algorithm on one stream (no overlap), 1 = overlap
 GPK_KNOB(int64_t, g_la_fuse_diag_rows, 9216);   // tuning knob (gpk_tune(40, v)): the update of the next diagonal block rides in the trailing update while that has >= this many rows (0: never)
 GPK_KNOB(int, g_la_fuse_diag_nb, 512);          // tuning knob (gpk_tune(41, v)): ... and only for outer blocks up to this width
@@ -1619,9 +1606,6 @@ void gpk_tune_potrf(int key, int64_t value) {
     if (key == 6) GPK_KNOB_SET(g_la_min_rows = value;);
     if (key == 7) GPK_KNOB_SET(g_la_mode = (int)value;);
     if (key == 9) GPK_KNOB_SET(g_la_tail_rows = value;);
-    if (key == 10) GPK_KNOB_SET(g_la_ps_mode = (int)value;);
-    if (key == 18) GPK_KNOB_SET(g_la_rejoin = (int)value;);
-    if (key == 11) GPK_KNOB_SET(g_la_strip_last = (int)value;);
     if (key == 32) GPK_KNOB_SET(g_fused_step = (int)value;);
     if (key == 37) GPK_KNOB_SET(g_pipe = (int)value;);
     if (key == 40) GPK_KNOB_SET(g_la_fuse_diag_rows = value;);
@@ -1632,20 +1616,12 @@ void gpk_tune_potrf(int key, int64_t value) {
     if (key == 53) GPK_KNOB_SET(g_batch_mixed = (int)value;);
     if (key == 54) GPK_KNOB_SET(g_batch_mixed_min = value;);
     if (key == 55) GPK_KNOB_SET(g_batch_lag = (int)value;);
-    if (key == 56) GPK_KNOB_SET(g_batch_opts = (int)value;);
-    if (key == 60) GPK_KNOB_SET(g_batch_left = (int)value;);
     if (key == 57) GPK_KNOB_SET(g_diag_two_per_cu = (int)value;);
     if (key == 38) GPK_KNOB_SET(g_pipe_fill = (int)value;);
     if (key == 39) GPK_KNOB_SET(g_pipe_panel_wgs = (int)value;);
 }
 
 #define GPK_LA_PAD 16
-#ifndef GPK_LA_CTRL_PINGPONG
-#define GPK_LA_CTRL_PINGPONG 0       // 1: the next step's control words zeroed on the helper stream instead of by a memset on the main stream in front of every
-                                     // fork (`make ab ABFLAGS=-DGPK_LA_CTRL_PINGPONG=1`).  Measured flat on one box (fp64 N = 16384 + 2048 rows 33.11 against
-                                     // 33.16 ms, fp32 N = 32768 101.45 against 101.56: the memset sits in a dependent-launch gap that is there anyway): OFF
-                                     // (profiles/r06_ab_control_words_pingpong.log)
-#endif
 int64_t gpk_potrf_la_ws_elems_impl(int64_t n, int nb) {
     return (n > nb ? n : nb) * (int64_t)(nb + GPK_LA_PAD) + (int64_t)nb * nb / 4 + 16 + 128 + nb;   // panel, merge scratch, 128 elements >= two sets of control words, one block of the right-hand side
 }
@@ -1707,13 +1683,11 @@ static int potrf_la_body(LaDevice* dev, T* A, int64_t n, int64_t ld, T* dinv128,
     const int64_t Rall = rows;           // rows of the buffer (>= n), the right-hand side among them
     const int64_t R = rhs ? rows - GPK_ROWS_RHS_STRIP : rows;     // ... the rows the look-ahead's GEMMs carry
     T* bvec = rhs ? A + R * ld : nullptr;
-    // 128 elements reserved: TWO sets of control words.  Step j's persistent update (and the helper's rejoin launch) count in set j & 1;
-    // the other set is zeroed on the HELPER stream during the step (nobody uses it then: its last users were joined before the fork), so
-    // that the next step finds its counters at zero without a memset -- one launch and one dependent-launch gap less on the main
-    // stream per outer step.  Launches of a step in front of its fork (rare: a change of aggregation policy) count in the other set.
+    // 128 elements reserved: TWO sets of control words.  Step j's persistent update (and the helper's rejoin launch) count in set j & 1,
+    // the step's other persistent launches (the last step's, and in front of the fork at a change of aggregation policy) in the other.
+    // (Zeroing the next step's set on the helper stream instead of by a memset in front of every fork measured flat: removed --
+    // profiles/r06_ab_control_words_pingpong.log.)
     unsigned* const ctrl_sets[2] = {reinterpret_cast<unsigned*>(ws), reinterpret_cast<unsigned*>(ws) + GPK_PERSIST_CTRL_WORDS};
-    unsigned* ctrl = ctrl_sets[0];
-    bool next_set_zeroed = false;        // the set of the step about to run has been zeroed by the previous step's helper-stream memset
     // n x nb, leading dimension nb + 16: with a power-of-two pitch the rows of a tile sit on a few memory channels and
     // the panel GEMM, which streams this buffer once, crawls (measured 2x)
     const int64_t ldt = nb + GPK_LA_PAD;
@@ -1802,7 +1776,7 @@ static int potrf_la_body(LaDevice* dev, T* A, int64_t n, int64_t ld, T* dinv128,
             const int64_t kc = c_first * nb, ka = (int64_t)cg.from * nb;
             const T* P = A + kc * ld + ka;
             const uint64_t every = (nblk - c_first >= 64) ? ~(uint64_t)0 : (((uint64_t)1 << (nblk - c_first)) - 1);
-            return GpkSeg<T>{R - kc, n - kc, k1 - ka, P, ld, P, ld, A + kc * ld + kc, ld, A + kc * ld + kc, ld, 1, 0, 0,
+            return GpkSeg<T>{R - kc, n - kc, k1 - ka, P, ld, P, ld, A + kc * ld + kc, ld, A + kc * ld + kc, ld, 1, 0,
                              (cg.mask == every && R == n) ? 0 : cg.mask, nb};
         };
         std::vector<ColGroup> groups;
@@ -1810,9 +1784,7 @@ static int potrf_la_body(LaDevice* dev, T* A, int64_t n, int64_t ld, T* dinv128,
             const int64_t k0 = j * nb, k1 = k0 + nb;
             const int64_t k2 = (k1 + nb < n) ? k1 + nb : n;
             unsigned* const ctrl_step = ctrl_sets[j & 1];       // this step's persistent update / rejoin
-            ctrl = ctrl_sets[(j + 1) & 1];                      // every other launch of the step (they zero it themselves)
-            const bool step_set_zeroed = next_set_zeroed;
-            next_set_zeroed = false;
+            unsigned* const ctrl = ctrl_sets[(j + 1) & 1];      // every other launch of the step (they zero it themselves)
             // solve(j): rows k1.. of panel j  (k clipped to W's triangle)
             if (sb < nb) {
                 // the explicit inverses are sb wide (fp32: the error of the posterior mean grows with the width of an explicit inverse): block
@@ -1827,12 +1799,9 @@ static int potrf_la_body(LaDevice* dev, T* A, int64_t n, int64_t ld, T* dinv128,
                         st = gpk_gemm_launch<T>(true, true, R - k1, sb, sb, T(1), Tp + k1 * ldt + c, ldt, 0, dinv_big + (k0 / sb + i) * per, sb, 0, T(0),
                                                 A + k1 * ld + k0 + c, ld, 0, 1, 8, stream);
                 }
-            } else if (g_la_ps_mode == 0) {
+            } else {
                 st = gpk_gemm_launch<T>(true, true, R - k1, nb, nb, T(1), Tp + k1 * ldt, ldt, 0, dinv_big + j * per, nb, 0, T(0),
                                         A + k1 * ld + k0, ld, 0, 1, 8, stream);
-            } else {
-                GpkSeg<T> ps{R - k1, nb, nb, Tp + k1 * ldt, ldt, dinv_big + j * per, nb, nullptr, 0, A + k1 * ld + k0, ld, 0, g_la_ps_mode};
-                st = gpk_gemm_persist_launch<T>(&ps, 1, T(1), ctrl, 0, stream);
             }
             if (st) return st;
             st = rhs_panel(j);
@@ -1888,8 +1857,7 @@ static int potrf_la_body(LaDevice* dev, T* A, int64_t n, int64_t ld, T* dinv128,
                 e_join = la_event(*dev, ev++);
                 if (e_fork == nullptr || e_join == nullptr) return GPK_ERR_LAUNCH;
                 // the tile counter is zeroed BEFORE the fork: the helper stream's rejoin launch reads it, so it must be ordered behind
-                // (by the previous step's helper-stream memset, joined since; the first overlapped step zeroes its own)
-                if (!step_set_zeroed && hipMemsetAsync(ctrl_step, 0, GPK_PERSIST_CTRL_WORDS * sizeof(unsigned), stream) != hipSuccess) return GPK_ERR_LAUNCH;
+                if (hipMemsetAsync(ctrl_step, 0, GPK_PERSIST_CTRL_WORDS * sizeof(unsigned), stream) != hipSuccess) return GPK_ERR_LAUNCH;
                 if (hipEventRecord(e_fork, stream) != hipSuccess) return GPK_ERR_LAUNCH;
             } else {
                 st = la_chain<T>(A, n, ld, dinv128, dinv_big, nb, sb, tmp, info, j + 1, stream);
@@ -1907,26 +1875,19 @@ static int potrf_la_body(LaDevice* dev, T* A, int64_t n, int64_t ld, T* dinv128,
                     const T* P2 = A + k2 * ld + ka1;
                     GpkSeg<T> seg[GPK_PERSIST_MAX_SEG];
                     int ns = 0;
-                    if (fuse_diag) seg[ns++] = GpkSeg<T>{k2 - k1, k2 - k1, kd1, P1, ld, P1, ld, A + k1 * ld + k1, ld, A + k1 * ld + k1, ld, 1, 0, 1};
-                    const GpkSeg<T> strip{R - k2, k2 - k1, kd1, P2, ld, P1, ld, A + k2 * ld + k1, ld, Tp + k2 * ldt, ldt, 0, 0};
-                    // the strip is what the next panel GEMM streams: written last, it is still in the Infinity Cache
-                    if (!g_la_strip_last) seg[ns++] = strip;
+                    if (fuse_diag) seg[ns++] = GpkSeg<T>{k2 - k1, k2 - k1, kd1, P1, ld, P1, ld, A + k1 * ld + k1, ld, A + k1 * ld + k1, ld, 1, 1};
+                    const GpkSeg<T> strip{R - k2, k2 - k1, kd1, P2, ld, P1, ld, A + k2 * ld + k1, ld, Tp + k2 * ldt, ldt, 0};
                     for (const ColGroup& cg : groups) seg[ns++] = col_segment(cg, j + 2, k1);
-                    if (g_la_strip_last) seg[ns++] = strip;
+                    seg[ns++] = strip;      // the strip is what the next panel GEMM streams: written last, it is still in the Infinity Cache
                     const int s2 = gpk_gemm_persist_launch<T>(seg, ns, T(-1), ctrl_step, overlap ? 1 : 0, stream, &saved, overlap);
                     if (s2) return s2;
                 }
                 if (overlap) {
                     if (hipStreamWaitEvent(dev->aux, e_fork, 0) != hipSuccess) return GPK_ERR_LAUNCH;
-                    // the NEXT step's set (free since the join in front of this fork), off the main stream
-                    if (GPK_LA_CTRL_PINGPONG) {
-                        if (hipMemsetAsync(ctrl, 0, GPK_PERSIST_CTRL_WORDS * sizeof(unsigned), dev->aux) != hipSuccess) return GPK_ERR_LAUNCH;
-                        next_set_zeroed = true;
-                    }
                     const int s2 = fuse_diag ? la_chain<T>(A, n, ld, dinv128, dinv_big, nb, sb, tmp, info, j + 1, dev->aux, 8, ctrl_step + 2, (unsigned)saved.signal_tiles)
                                              : la_chain<T>(A, n, ld, dinv128, dinv_big, nb, sb, tmp, info, j + 1, dev->aux, 8);
                     if (s2) return s2;
-                    if (g_la_rejoin && saved.valid)         // chain done: the reserved CUs take tiles of the update that is still running
+                    if (saved.valid)         // chain done: the reserved CUs take tiles of the update that is still running
                         return gpk_gemm_persist_rejoin<T>(&saved, dev->aux);
                 }
                 return GPK_OK;

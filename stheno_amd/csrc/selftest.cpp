@@ -545,18 +545,13 @@ static void test_potrf_case(int n, int batch, int nbo, int nrhs_small, int nrhs_
 }
 template <typename T>
 static void test_potrf() {
-    // the single-launch sweep for one right-hand side (trsv_sweep_kernel): orders from 2048 take it by default; ragged last blocks,
-    // every block width it serves, and (dev build) small orders with the threshold lowered
-    gpk_tune(49, 1);           // (off by default since it measured slower than the per-block sweep: profiles/r05_ab_trsv_sweep.log)
+    // the single-column sweep of one factor: ragged last blocks, every merged block width
     test_potrf_case<T>(2500, 1, 0, 1, 0, 512);
     test_potrf_case<T>(4500, 1, 0, 1, 0, 1024);
     test_potrf_case<T>(2304, 1, 0, 1, 0, 256);
     test_potrf_case<T>(4096, 1, 0, 1, 0, 2048);
-    gpk_tune(50, 0);
     test_potrf_case<T>(700, 1, 0, 1, 0, 256);
     test_potrf_case<T>(1664, 1, 256, 1, 0, 512);
-    gpk_tune(50, 2048);
-    gpk_tune(49, 0);
     test_potrf_case<T>(10, 1, 0, 1, 3, 128);
     test_potrf_case<T>(100, 3, 0, 2, 0, 128);
     test_potrf_case<T>(128, 1, 0, 1, 130, 128);
@@ -569,15 +564,13 @@ static void test_potrf() {
     test_potrf_case<T>(1664, 1, 256, 1, 300, 256);
     test_potrf_case<T>(700, 70, 256, 1, 0, 128);     // larger batch, ragged
     test_potrf_case<T>(512, 64, 128, 2, 0, 128);
-    // the mixed-phase batched steps (batch >= 64, orders that are multiples of 128 from 512 on; fp32 by default, knob 53 = 2: fp64 too):
+    // the mixed-phase batched steps (fp32, batch >= 64, orders that are multiples of 128 from 512 on; fp64: the lockstep launches):
     // every halving level, a partial last outer panel, batches that do not divide by the 8 queues
-    gpk_tune(53, 2);
     test_potrf_case<T>(1024, 64, 256, 1, 0, 128);
     test_potrf_case<T>(640, 67, 256, 1, 0, 128);
     test_potrf_case<T>(1536, 65, 512, 1, 0, 128);
     test_potrf_case<T>(2048, 72, 0, 1, 0, 128);
     test_potrf_case<T>(1152, 64, 1024, 1, 0, 128);
-    gpk_tune(53, 1);
 }
 
 
@@ -2016,26 +2009,13 @@ static void perf_trsv(int n, std::vector<int> sbs) {
     for (int sb : sbs) {
         Dev<T> dsb((size_t)((n + sb - 1) / sb) * sb * sb), tmpm((size_t)((n + sb - 1) / sb) * sb * sb / 4 + 16), tmp((size_t)sb + GPK_TRSV_CTRL_ELEMS);
         gpk_trtri_merge(DT<T>::v, K.p, n, n, 0, 1, dinv.p, sb, dsb.p, tmpm.p, nullptr);
-        std::vector<T> ref;
-        for (int sweep = 0; sweep < 2; ++sweep) {
-            gpk_tune(49, sweep);
-            for (int rep = 0; rep < 4; ++rep) {
-                y.up(hy);
-                tm.start();
-                gpk_trsv_lower(DT<T>::v, K.p, n, n, 0, dsb.p, sb, y.p, 1, 1, 0, tmp.p, 1, nullptr);
-                const float ms = tm.stop();
-                if (rep) printf("PERFTRSV %s n=%d sb=%d %s  %.3f ms  %.2f TB/s\n", DT<T>::name(), n, sb, sweep ? "one launch  " : "per-block   ", ms,
-                                0.5 * n * (double)n * sizeof(T) / ms * 1e-9);
-            }
-            auto got = y.down();
-            if (!sweep) ref = got;
-            else {
-                double num = 0, den = 0;
-                for (int i = 0; i < n; ++i) { num = std::max(num, std::fabs((double)got[i] - (double)ref[i])); den = std::max(den, std::fabs((double)ref[i])); }
-                printf("PERFTRSV %s n=%d sb=%d one launch vs per-block: max rel diff %.3e\n", DT<T>::name(), n, sb, num / den);
-            }
+        for (int rep = 0; rep < 4; ++rep) {
+            y.up(hy);
+            tm.start();
+            gpk_trsv_lower(DT<T>::v, K.p, n, n, 0, dsb.p, sb, y.p, 1, 1, 0, tmp.p, 1, nullptr);
+            const float ms = tm.stop();
+            if (rep) printf("PERFTRSV %s n=%d sb=%d per-block   %.3f ms  %.2f TB/s\n", DT<T>::name(), n, sb, ms, 0.5 * n * (double)n * sizeof(T) / ms * 1e-9);
         }
-        gpk_tune(49, 1);
     }
 }
 

@@ -218,7 +218,8 @@ class HipBackend:
     @_on_operand_device
     def potrf_(self, a, nbo=0, lookahead_nb=0, lookahead_sb=0, rhs=None):
         """In-place lower Cholesky of ``a`` (..., n, n).  ``rhs`` (plain path only): a contiguous (B, n) tensor, one right-hand side per
-        matrix, overwritten by ``L^{-1} rhs`` (``gpk_potrf_rhs``: for large fp32 batches the sweep runs beside the factorisation).
+        matrix, overwritten by ``L^{-1} rhs`` (``gpk_potrf_rhs``: batches that take the mixed-phase steps -- fp32, 64 or more aligned
+        matrices -- solve it inside the steps' solve tiles; every other shape sweeps with ``gpk_trsv_lower`` behind the factorisation).
         Returns ``(dinv, info)``, or
         ``(dinv, info, dinv_sb)`` when ``lookahead_nb`` (256 ... 4096) selects the look-ahead
         factorisation of ONE large matrix: ``dinv_sb`` are the inverses of the ``sb x sb`` diagonal
@@ -255,7 +256,7 @@ class HipBackend:
             code = self.lib.gpk_potrf_rhs(_dtype_id(a3), self._ptr(a3), n, _ld(a3), _bs(a3), B, self._ptr(dinv), self._ptr(info), int(nbo),
                                           self._ptr(rhs), n, self._ptr(tmp), self._stream())
             self._st(code, "gpk_potrf_rhs")
-            # (`tmp` is released here: the caching allocator hands it to later work of THIS stream only, which the side stream has joined)
+            # (`tmp` is released here: the caching allocator hands it to later work of THIS stream only)
             return dinv, info
         code = self.lib.gpk_potrf(_dtype_id(a3), self._ptr(a3), n, _ld(a3), _bs(a3), B, self._ptr(dinv),
                                   self._ptr(info), int(nbo), self._stream())
@@ -267,7 +268,8 @@ class HipBackend:
         """In-place lower Cholesky of the leading ``n x n`` of ``a`` (rows, n), rows > n, carrying the rows under it through the
         factorisation (``gpk_potrf_rows``): they come out as ``a[n:] L^{-T}``.  ``n`` a multiple of 128.  Returns ``(dinv, info, dinv_sb or None)``.
         ``rhs_row``: the last 64 rows are a strip whose first row is ONE right-hand side, the rest zero padding (``gpk_potrf_rows_rhs``,
-        ``GPK_ROWS_RHS``: same result, ``L^{-1} b`` in that row, computed by matrix-vector products beside the look-ahead's trailing updates).  ``tail_inverses=False``: the merged inverses of the
+        ``GPK_ROWS_RHS``: same result, ``L^{-1} b`` in that row; through the look-ahead steps it is computed by matrix-vector products on the
+        helper stream's CUs beside the trailing updates, through the plain tail -- and without the look-ahead -- it is a row like the others).  ``tail_inverses=False``: the merged inverses of the
         look-ahead's plain tail are not computed -- ``dinv_sb`` comes back as ``None`` (incomplete), callers merge on demand."""
         if a.dim() != 2 or a.stride(-1) != 1 or a.shape[0] <= a.shape[1] or a.shape[1] % 128 != 0:
             raise ValueError("potrf_rows_ takes one (rows, n) matrix with rows > n, n a multiple of 128 and unit inner stride")
@@ -340,7 +342,7 @@ class HipBackend:
         if n == 0 or nrhs == 0:
             return b
         if nrhs <= 8:
-            tmp = torch.empty((B * sb * nrhs + 16,), dtype=b.dtype, device=b.device)     # (+ GPK_TRSV_CTRL_ELEMS: the single-launch sweep's control words)
+            tmp = torch.empty((B * sb * nrhs + 16,), dtype=b.dtype, device=b.device)     # (+ GPK_TRSV_CTRL_ELEMS: reserved)
             code = self.lib.gpk_trsv_lower(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
                                            self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(tmp), B, self._stream())
             self._st(code, "gpk_trsv_lower")
