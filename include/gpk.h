@@ -13,7 +13,7 @@
  *  - `batch` independent problems are laid out with a stride `s*` in ELEMENTS
  *    (stheno's batched computation: README.md:744-766, random.py:261,274).
  *  - Every pointer named x/y/a/b/l/out/... is a DEVICE pointer owned by the
- *    caller; term descriptors (`kinds`, `variances`, `inv_ls`) are HOST arrays.
+ *    caller; term descriptors (`kinds`, `variances`, `inv_ls`, and `shapes` of the `_s` entries) are HOST arrays.
  *  - `dtype`: GPK_F32 or GPK_F64; all device buffers of a call share it.
  *  - `stream` is a hipStream_t passed as void*.  Calls only ENQUEUE work: no
  *    device allocation, no free, no host synchronisation, no retained pointers.
@@ -40,13 +40,14 @@ extern "C" {
 #define GPK_OK 0
 #define GPK_ERR_LAUNCH (-100)
 
-/* kernel term kinds; one term = variance * kappa(dist(x, y) * inv_ls) */
+/* kernel term kinds; one term = variance * kappa(dist(x, y) * inv_ls)   (GPK_K_RQ: kappa also takes a shape parameter) */
 #define GPK_K_EQ 0        /* exp(-r^2/2)                        mlkernels.EQ        */
 #define GPK_K_MATERN12 1  /* exp(-r)                            mlkernels.Exp       */
 #define GPK_K_MATERN32 2  /* (1+sqrt3 r) exp(-sqrt3 r)          mlkernels.Matern32  */
 #define GPK_K_MATERN52 3  /* (1+sqrt5 r+5r^2/3) exp(-sqrt5 r)   mlkernels.Matern52  */
 #define GPK_K_LINEAR 4    /* <x, y>                             mlkernels.Linear    */
 #define GPK_K_CONST 5     /* 1                                  mlkernels.OneKernel */
+#define GPK_K_RQ 6        /* (1 + r^2/(2 alpha))^(-alpha)       mlkernels.RQ(alpha): one SHAPE parameter, see gpk_kmat_s */
 #define GPK_MAX_TERMS 8
 
 #define GPK_GEMM_LOWER 1
@@ -84,11 +85,27 @@ int gpk_kmat(int dtype, const int* kinds, const double* variances, const double*
              int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
              void* stream);
 
+/* The same with one SHAPE parameter per term (version 102): `shapes` is a host array like `inv_ls`, read for the kinds that have a
+ * shape -- GPK_K_RQ: alpha > 0 -- and ignored for the others; NULL: no term has one.  gpk_kmat IS gpk_kmat_s(shapes = NULL): with
+ * `kinds` free of GPK_K_RQ both write the same bits; gpk_kmat with a GPK_K_RQ term returns -1 (no alpha was given), gpk_kmat_s with a
+ * non-positive alpha -5.  RQ is evaluated as exp(-alpha log1p(q / (2 alpha))), q = r^2 / scale^2: a single RQ term has a row-band
+ * program of its own next to EQ / Matern; within ~2.5 eps (1 + alpha log1p(q / (2 alpha))) of the exactly rounded value
+ * (csrc/selftest.cpp, `--rq`).  Replaces mlkernels `pairwise` of `RQ(alpha)` and of sums with it. */
+int gpk_kmat_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+               const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
+               int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
+               int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
+               void* stream);
+
 /* Kernel diagonal  out[i] = k(x_i, x_i).  Replaces mlkernels `elwise`:
  * stheno/model/fdd.py:66, stheno/model/observations.py:304. */
 int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
               const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
               int64_t batch, void* stream);
+/* ... with the shape parameters of gpk_kmat_s (an RQ term contributes its variance on the diagonal, whatever alpha). */
+int gpk_kdiag_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
+                int64_t batch, void* stream);
 
 /* Number of elements of the `dinv` workspace gpk_potrf needs per batch entry. */
 int64_t gpk_dinv_elems(int64_t n);
@@ -342,6 +359,14 @@ int64_t gpk_kmat_vjp_blocks(int64_t n);
 int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, int nterms, const void* x, int64_t n,
                  int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
                  const double* g, void* partial, void* diag_g, void* stream);
+/* The same with shape parameters (gpk_kmat_s): one more sum per term, S3_t = sum_ij G_ij d kappa_t / d shape_t (0 for kinds without a
+ * shape), and a row layout of its own --
+ *   partial[b][3t] = S1_t,  partial[b][3t+1] = S2_t,  partial[b][3t+2] = S3_t,  partial[b][3*GPK_MAX_TERMS] = trace(G)
+ *   (row stride 3*GPK_MAX_TERMS + 1; sum over b).  d logpdf / d alpha_t = v_t S3_t.
+ * RQ, with u = q / (2 alpha): kappa' q = -(q / 2) kappa / (1 + u),  d kappa / d alpha = kappa (u / (1 + u) - log1p(u)). */
+int gpk_kmat_vjp_s(int dtype, const int* kinds, const double* inv_ls, const double* shapes, int nterms, const void* x, int64_t n,
+                   int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
+                   const double* g, void* partial, void* diag_g, void* stream);
 
 /* Kernel VJP with an explicit cotangent (gradient of the pseudo-point ELBO w.r.t. kernel
  * hyper-parameters, observation noise and inducing inputs: the learning loop that
@@ -359,6 +384,12 @@ int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, con
                        const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream);
+/* ... with shape parameters: partial[wg][3t .. 3t+2] = S1_t, S2_t, S3_t as for gpk_kmat_vjp_s (row stride 3*GPK_MAX_TERMS + 1; the
+ * last element of a row is unused), colsum / gradx as above (RQ: dK/dx through kappa' = -kappa / (2 (1 + u))). */
+int gpk_kmat_vjp_dense_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                         const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
+                         const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
+                         void* partial, void* colsum, void* gradx, void* stream);
 
 /* Measurement hooks (bench.py's live roofline figure).  Between gpk_prof_start and
  * gpk_prof_stop every MFMA GEMM launch of this process is bracketed by HIP events on its

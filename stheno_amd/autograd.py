@@ -24,6 +24,43 @@ from .matrix import LOG_2_PI, Chol, config
 __all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals"]
 
 
+# Hyper-parameters travel through the autograd functions as one flat list of scalar tensors: the variances, then the scales and --
+# only when a term has a shape parameter (RQ's alpha) -- one more entry per term behind them (a constant 0 for the kinds without).
+def _as_t(v):
+    return v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+
+
+def _pack(tt, shapes):
+    """``(kinds, params)`` of tensor terms and their shapes (``Kernel.tensor_terms()`` / ``tensor_shapes()``)."""
+    kinds = tuple(k for k, _, _ in tt)
+    params = [_as_t(v) for _, v, _ in tt] + [_as_t(s) for _, _, s in tt]
+    if shapes is not None and any(a is not None for a in shapes):
+        params += [_as_t(0.0 if a is None else a) for a in shapes]
+    return kinds, params
+
+
+def _unpack(kinds, params):
+    """``(terms, values)``: the host descriptor for the fused kernels and the parameters' values
+    ``(variances, scales, alphas or None)`` as floats."""
+    nt = len(kinds)
+    variances = [float(v) for v in params[:nt]]
+    scales = [float(v) for v in params[nt:2 * nt]]
+    alphas = [float(v) for v in params[2 * nt:3 * nt]] if len(params) > 2 * nt else None
+    shapes = None if alphas is None else [a if k in ops._SHAPED else None for k, a in zip(kinds, alphas)]
+    return ops.KTerms(list(zip(kinds, variances, scales)), shapes), (variances, scales, alphas)
+
+
+def _param_grads(kinds, values, S, meta, wgt=1.0):
+    """Gradients for the flat parameter list from the per-term sums ``S`` (nt, 2 or 3): d/dv_t = S1_t, d/dl_t = -2 v_t S2_t / l_t,
+    d/dalpha_t = v_t S3_t (None for the kinds without a shape)."""
+    variances, scales, alphas = values
+    nt = len(kinds)
+    gr = [wgt * S[t, 0] for t in range(nt)] + [wgt * -2.0 * variances[t] / scales[t] * S[t, 1] for t in range(nt)]
+    if alphas is not None:
+        gr += [(wgt * variances[t] * S[t, 2]) if kinds[t] in ops._SHAPED else None for t in range(nt)]
+    return [None if g_ is None else g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(gr, meta)]
+
+
 def _cotangent(be, kinv_lower, alpha, g):
     """``G = d logpdf / dK = 1/2 (alpha diag(g) alpha^T - sum(g) K^{-1})`` as an explicit symmetric (n, n) matrix, formed in the
     buffer of the lower triangle of ``K^{-1}`` (consumed): ``alpha = K^{-1} r`` (n, C), ``g`` the C output cotangents."""
@@ -44,12 +81,11 @@ def _grad_inputs(be, terms, x, G):
 class _GPLogpdf(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, r, noise_vec, noise_mat, kinds, *params):
-        """``params`` = variances then scales (scalar tensors, any device); ``noise_vec`` (n,)
+        """``params`` = variances, scales (and shape parameters: ``_pack``; scalar tensors, any device); ``noise_vec`` (n,)
         or None; ``noise_mat`` (n, n) dense noise covariance or None; ``r = y - mean`` (n, C).  Returns (C,)."""
         be = ops.get_backend()
         nt = len(kinds)
-        variances, scales = params[:nt], params[nt:]
-        terms = ops.KTerms([(k, float(v), float(s)) for k, v, s in zip(kinds, variances, scales)])
+        terms, values = _unpack(kinds, params)
         n, C = r.shape
         k = be.kmat(terms, x, None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
         if noise_mat is not None:
@@ -62,7 +98,7 @@ class _GPLogpdf(torch.autograd.Function):
         ctx.nt, ctx.has_noise = nt, noise_vec is not None
         ctx.has_noise_mat = noise_mat is not None
         ctx.param_meta = [(p.device, p.dtype) for p in params]
-        ctx.values = ([float(v) for v in variances], [float(s) for s in scales])
+        ctx.values, ctx.kinds = values, kinds
         return out
 
     @staticmethod
@@ -78,14 +114,7 @@ class _GPLogpdf(torch.autograd.Function):
         kinv = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)   # N^3/3 flops
         alpha = torch.stack([be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(C)], dim=1)
         S, trace_g, diag_g = be.kmat_vjp(terms, x, kinv, alpha, g)
-        variances, scales = ctx.values
-        grads = []
-        for t in range(nt):                                       # d/d variance_t
-            dev, dt = ctx.param_meta[t]
-            grads.append(S[t, 0].to(device=dev, dtype=dt))
-        for t in range(nt):                                       # d/d scale_t
-            dev, dt = ctx.param_meta[nt + t]
-            grads.append((-2.0 * variances[t] / scales[t] * S[t, 1]).to(device=dev, dtype=dt))
+        grads = _param_grads(ctx.kinds, ctx.values, S, ctx.param_meta)
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype))
         grad_noise = diag_g if ctx.has_noise else None
         grad_x = grad_nm = None
@@ -108,8 +137,7 @@ class _GPLogpdfBatched(torch.autograd.Function):
     def forward(ctx, x, r, noise_vec, kinds, *params):
         be = ops.get_backend()
         nt = len(kinds)
-        variances, scales = params[:nt], params[nt:]
-        terms = ops.KTerms([(k, float(v), float(s)) for k, v, s in zip(kinds, variances, scales)])
+        terms, values = _unpack(kinds, params)
         n = r.shape[-2]
         k = be.kmat(terms, x, None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
         chol = Chol.factor_(k)
@@ -119,7 +147,7 @@ class _GPLogpdfBatched(torch.autograd.Function):
         ctx.chol, ctx.w, ctx.x, ctx.terms = chol, w, x, terms
         ctx.nt, ctx.has_noise = nt, noise_vec is not None
         ctx.param_meta = [(p.device, p.dtype) for p in params]
-        ctx.values = ([float(v) for v in variances], [float(s) for s in scales])
+        ctx.values, ctx.kinds = values, kinds
         return out
 
     @staticmethod
@@ -145,14 +173,7 @@ class _GPLogpdfBatched(torch.autograd.Function):
                 grad_noise[b] = diag_g
             if grad_x is not None:
                 grad_x[b] = _grad_inputs(be, terms, x[b], _cotangent(be, kinv, alpha, [g_host[b]]))
-        variances, scales = ctx.values
-        grads = []
-        for t in range(nt):
-            dev, dt = ctx.param_meta[t]
-            grads.append(S_tot[t, 0].to(device=dev, dtype=dt))
-        for t in range(nt):
-            dev, dt = ctx.param_meta[nt + t]
-            grads.append((-2.0 * variances[t] / scales[t] * S_tot[t, 1]).to(device=dev, dtype=dt))
+        grads = _param_grads(ctx.kinds, ctx.values, S_tot, ctx.param_meta)
         return (grad_x, grad_r, grad_noise, None, *grads)
 
 
@@ -162,8 +183,9 @@ class _JointLogpdf(torch.autograd.Function):
     ``kernels[p_i, p_j](x_i, x_j)``, every block a sum of primitives.  Forward = the plain HIP path (blocks written into one
     buffer, factorised in place).  Backward: the explicit cotangent ``G = 1/2 (alpha diag(g) alpha^T - sum(g) K^{-1})`` once, then one
     ``gpk_kmat_vjp_dense`` pass per block of the lower block triangle over its view of ``G`` (off-diagonal blocks count twice: ``G`` and
-    the block matrix are symmetric).  ``layout`` = [(i, j, number of terms)], ``params`` = the variances then scales of block
-    after block: autograd carries them back to the user's leaves through whatever kernel algebra produced them."""
+    the block matrix are symmetric).  ``layout`` = [(i, j, number of terms, number of parameters)], ``params`` = the variances, scales
+    (and shape parameters, for a block that has any: ``_pack``) of block after block: autograd carries them back to the user's
+    leaves through whatever kernel algebra produced them."""
 
     @staticmethod
     def forward(ctx, r, noise_vec, build, parts, layout, kinds, *params):
@@ -193,19 +215,13 @@ class _JointLogpdf(torch.autograd.Function):
         for _, xi in ctx.parts:
             offs.append(offs[-1] + xi.shape[0])
         grads, pos, kpos = [None] * len(ctx.values), 0, 0
-        for (i, j, nt) in ctx.layout:
-            vals = ctx.values[pos: pos + 2 * nt]
-            variances, scales = vals[:nt], vals[nt:]
-            terms = ops.KTerms([(kd, v, sc) for kd, v, sc in zip(ctx.kinds[kpos: kpos + nt], variances, scales)])
+        for (i, j, nt, npar) in ctx.layout:
+            kinds = ctx.kinds[kpos: kpos + nt]
+            terms, values = _unpack(kinds, ctx.values[pos: pos + npar])
             gb = G[offs[i]: offs[i + 1], offs[j]: offs[j + 1]]
             S, _, _ = be.kmat_vjp_dense(terms, ctx.parts[i][1], ctx.parts[j][1], gb)
-            wgt = 1.0 if i == j else 2.0
-            for t in range(nt):
-                dev, dt = ctx.param_meta[pos + t]
-                grads[pos + t] = (wgt * S[t, 0]).to(device=dev, dtype=dt)
-                dev, dt = ctx.param_meta[pos + nt + t]
-                grads[pos + nt + t] = (wgt * -2.0 * variances[t] / scales[t] * S[t, 1]).to(device=dev, dtype=dt)
-            pos += 2 * nt
+            grads[pos: pos + npar] = _param_grads(kinds, values, S, ctx.param_meta[pos: pos + npar], 1.0 if i == j else 2.0)
+            pos += npar
             kpos += nt
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype)) if ctx.needs_input_grad[0] else None
         grad_noise = torch.diagonal(G).clone() if ctx.has_noise else None
@@ -222,16 +238,16 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
     if any(xi.requires_grad for _, xi in parts):
         return None                                   # d/dx through the block matrix: not covered (the caller refuses)
     layout, kinds, variances_scales = [], [], []
-    as_t = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
     for i, (pi, _) in enumerate(parts):
         for j in range(i + 1):
             kern = kernels[pi] if i == j else kernels[pi, parts[j][0]]
             tt = kern.tensor_terms() if hasattr(kern, "tensor_terms") else None
             if tt is None:
                 return None
-            layout.append((i, j, len(tt)))
-            kinds.extend(k for k, _, _ in tt)
-            variances_scales.extend([as_t(v) for _, v, _ in tt] + [as_t(sc) for _, _, sc in tt])
+            kd, pr = _pack(tt, kern.tensor_shapes() if hasattr(kern, "tensor_shapes") else None)
+            layout.append((i, j, len(tt), len(pr)))
+            kinds.extend(kd)
+            variances_scales.extend(pr)
     if not torch.is_grad_enabled() or not (any(p.requires_grad for p in variances_scales) or r.requires_grad
                                             or (noise_vec is not None and noise_vec.requires_grad)):
         return None
@@ -242,9 +258,16 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
     return _JointLogpdf.apply(r, noise_vec, build, parts, tuple(layout), tuple(kinds), *variances_scales)
 
 
-def needs_grad(tensor_terms, noise_vec, r, x=None, noise_mat=None):
+def _any_shape_grad(shapes):
+    return shapes is not None and any(torch.is_tensor(a) and a.requires_grad for a in shapes)
+
+
+def needs_grad(tensor_terms, noise_vec, r, x=None, noise_mat=None, shapes=None):
+    """``shapes``: the shape parameters beside ``tensor_terms`` (``Kernel.tensor_shapes()``), learnable like the scales."""
     if not torch.is_grad_enabled():
         return False
+    if _any_shape_grad(shapes):
+        return True
     if x is not None and torch.is_tensor(x) and x.requires_grad:
         return True
     if noise_mat is not None and noise_mat.requires_grad:
@@ -264,7 +287,7 @@ def kernel_requires_grad(kernel, _depth=0):
         return False
     tt = kernel.tensor_terms() if isinstance(kernel, _k.Kernel) else None
     if tt is not None:
-        return any((torch.is_tensor(v) and v.requires_grad) or (torch.is_tensor(s) and s.requires_grad) for _, v, s in tt)
+        return _any_shape_grad(kernel.tensor_shapes()) or any((torch.is_tensor(v) and v.requires_grad) or (torch.is_tensor(s) and s.requires_grad) for _, v, s in tt)
     if isinstance(kernel, _k.MultiOutputKernel):
         ks = kernel.kernels
         return any(kernel_requires_grad(ks[p], _depth + 1) for p in kernel.pids)
@@ -278,10 +301,7 @@ def kernel_requires_grad(kernel, _depth=0):
 
 def gp_logpdf(kernel, x, noise_vec, r, noise_mat=None):
     """Differentiable log-density of ``r = y - m(x)`` under ``N(0, k(x) + diag(noise_vec) + noise_mat + eps I)``."""
-    tt = kernel.tensor_terms()
-    kinds = tuple(k for k, _, _ in tt)
-    as_t = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
-    params = [as_t(v) for _, v, _ in tt] + [as_t(s) for _, _, s in tt]
+    kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
     if x.dim() == 3:
         return _GPLogpdfBatched.apply(x, r, noise_vec, kinds, *params)
     return _GPLogpdf.apply(x, r, noise_vec, noise_mat, kinds, *params)
@@ -311,8 +331,7 @@ class _SparseELBO(torch.autograd.Function):
 
         be = ops.get_backend()
         nt = len(kinds)
-        variances, scales = params[:nt], params[nt:]
-        terms = ops.KTerms([(k, float(v), float(s)) for k, v, s in zip(kinds, variances, scales)])
+        terms, values = _unpack(kinds, params)
         n, m = x.shape[0], z.shape[0]
         d = noise_vec.detach()
         v = be.kmat(terms, z, x)                                               # K_zx
@@ -340,7 +359,7 @@ class _SparseELBO(torch.autograd.Function):
         ctx.saved = dict(x=x, z=z, r=r, d=d, s=s, v=v, q=q, corr=corr, a=a, u=u, chol_z=chol_z, chol_a=chol_a,
                          terms=terms, tau=tau, nt=nt, fitc=fitc)
         ctx.param_meta = [(p_.device, p_.dtype) for p_ in params]
-        ctx.values = ([float(v_) for v_ in variances], [float(s_) for s_ in scales])
+        ctx.values = values
         ctx.kinds = kinds
         return elbo
 
@@ -399,7 +418,7 @@ class _SparseELBO(torch.autograd.Function):
         S = s_k + s_kz
         # through k(x_j, x_j) (VFE: trace term; FITC: the effective noise): stationary terms are constant there
         g_kd = g_d if fitc else -0.5 * tau / d
-        variances, scales = ctx.values
+        variances, scales, alphas = ctx.values
         go = grad_out.to(x.dtype)
         grads_v, grads_s = [], []
         for t in range(nt):
@@ -414,7 +433,9 @@ class _SparseELBO(torch.autograd.Function):
                     gv = gv + g_kd.sum()
             grads_v.append(gv * go)
             grads_s.append(gs * go)
-        grads = [g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(grads_v + grads_s, ctx.param_meta)]
+        # (shape parameters: through the kernel matrices only -- every stationary kind is 1 on the diagonal, whatever its shape)
+        grads_a = [] if alphas is None else [(variances[t] * S[t, 2] * go) if ctx.kinds[t] in ops._SHAPED else None for t in range(nt)]
+        grads = [None if g_ is None else g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(grads_v + grads_s + grads_a, ctx.param_meta)]
         grad_z = (gz_k + 2.0 * gz_kz) * go if need_z else None
         grad_x = gx_k * go if need_x else None
         grad_r = (-b * go)[:, None] if ctx.needs_input_grad[2] else None
@@ -422,9 +443,11 @@ class _SparseELBO(torch.autograd.Function):
         return (grad_x, grad_z, grad_r, grad_noise, None, None, *grads)
 
 
-def elbo_needs_grad(tensor_terms, noise_vec, z, r, x=None):
+def elbo_needs_grad(tensor_terms, noise_vec, z, r, x=None, shapes=None):
     if not torch.is_grad_enabled():
         return False
+    if _any_shape_grad(shapes):
+        return True
     if x is not None and torch.is_tensor(x) and x.requires_grad:
         return True
     for _, v, s in tensor_terms:
@@ -437,10 +460,7 @@ def sparse_elbo(kernel, x, z, noise_vec, r, method):
     """Differentiable VFE / FITC / DTC bound for ``r = y - m(x)`` with inducing inputs ``z``."""
     if method not in ("vfe", "fitc", "dtc"):
         raise ValueError(f'Invalid approximation method "{method}".')
-    tt = kernel.tensor_terms()
-    kinds = tuple(k for k, _, _ in tt)
-    as_t = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
-    params = [as_t(v) for _, v, _ in tt] + [as_t(s) for _, _, s in tt]
+    kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
     return _SparseELBO.apply(x, z, r, noise_vec, {"vfe": 1.0, "dtc": 0.0, "fitc": -1.0}[method], kinds, *params)
 
 
@@ -472,12 +492,11 @@ class _PosteriorMarginals(torch.autograd.Function):
         per-dimension length scales); ``r`` (N, 1) or None (marginal variances only: ``mu`` comes back as zeros)."""
         chol, w, v, mu, s = run()
         nt = len(kinds)
-        variances, scales = params[:nt], params[nt:]
-        ctx.terms = ops.KTerms([(k, float(vv), float(sc)) for k, vv, sc in zip(kinds, variances, scales)])
+        ctx.terms, ctx.values = _unpack(kinds, params)
+        ctx.kinds = kinds
         ctx.chol, ctx.w, ctx.v, ctx.x, ctx.xs = chol, w, v, x, xs
         ctx.nt, ctx.has_noise, ctx.has_r = nt, noise_vec is not None, r is not None
         ctx.param_meta = [(p.device, p.dtype) for p in params]
-        ctx.values = ([float(vv) for vv in variances], [float(sc) for sc in scales])
         ctx.set_materialize_grads(False)
         if mu is None:
             mu = torch.zeros_like(s)
@@ -495,7 +514,7 @@ class _PosteriorMarginals(torch.autograd.Function):
             gs = None
         need_x, need_xs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if gm is None and gs is None:
-            return (None,) * (6 + 2 * nt)
+            return (None,) * (6 + len(ctx.param_meta))
         transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
         alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
         bm = beta = None
@@ -549,14 +568,7 @@ class _PosteriorMarginals(torch.autograd.Function):
             if kinv.stride(0) == 0:
                 kinv = torch.zeros((n, n), dtype=dt, device=dev)
             grad_x = grad_x + _grad_inputs(be, terms, x, _cotangent(be, kinv, A, g))
-        variances, scales = ctx.values
-        grads = []
-        for t in range(nt):
-            dev_t, dt_t = ctx.param_meta[t]
-            grads.append(S[t, 0].to(device=dev_t, dtype=dt_t))
-        for t in range(nt):
-            dev_t, dt_t = ctx.param_meta[nt + t]
-            grads.append((-2.0 * variances[t] / scales[t] * S[t, 1]).to(device=dev_t, dtype=dt_t))
+        grads = _param_grads(ctx.kinds, ctx.values, S, ctx.param_meta)
         grad_r = beta[:, None] if (beta is not None and ctx.needs_input_grad[2]) else None
         grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[3]) else None
         return (grad_x, grad_xs, grad_r, grad_noise, None, None, *grads)
@@ -578,8 +590,5 @@ def kdiag_terms(tensor_terms, x):
 def posterior_marginals(kernel, x, xs, r, noise_vec, run):
     """Differentiable ``(mu, s)`` of ``_PosteriorMarginals`` for a sum of primitives ``kernel`` evaluated on ``x`` / ``xs`` (already
     divided by per-dimension length scales, so torch carries those)."""
-    tt = kernel.tensor_terms()
-    kinds = tuple(k for k, _, _ in tt)
-    as_t = lambda v: v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
-    params = [as_t(v) for _, v, _ in tt] + [as_t(s) for _, _, s in tt]
+    kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
     return _PosteriorMarginals.apply(x, xs, r, noise_vec, run, kinds, *params)

@@ -244,11 +244,11 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
                     const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
-                    hipStream_t stream);
+                    hipStream_t stream, const double* shapes = nullptr);
 template <typename T>
 int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
                      const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
-                     int64_t batch, hipStream_t stream);
+                     int64_t batch, hipStream_t stream, const double* shapes = nullptr);
 template <typename T>
 int gpk_scale_cols_launch(T* V, int64_t rows, int64_t cols, int64_t ld, int64_t sV, const T* s, int64_t ss,
                           int64_t batch, hipStream_t stream);
@@ -278,6 +278,16 @@ template <typename T>
 int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, int nterms, const T* X, int64_t n, int64_t ldx,
                         int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
                         T* partial, T* diag_g, hipStream_t stream);
+// the entries with shape parameters (gpk_kmat_vjp_s / gpk_kmat_vjp_dense_s): partial rows of 3 * GPK_MAX_TERMS + 1 elements
+template <typename T>
+int gpk_kmat_vjp_s_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
+                          int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
+                          T* partial, T* diag_g, hipStream_t stream);
+template <typename T>
+int gpk_kmat_vjp_dense_s_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                                const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                                const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
+                                T* colsum, T* gradx, hipStream_t stream);
 void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk);
 template <typename T>
 int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,

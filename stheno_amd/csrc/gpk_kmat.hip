@@ -16,7 +16,7 @@
 // direct differences (no |a|^2 + |b|^2 - 2ab cancellation).
 #include "gpk_common.hpp"
 
-enum { GPK_K_EQ = 0, GPK_K_MATERN12 = 1, GPK_K_MATERN32 = 2, GPK_K_MATERN52 = 3, GPK_K_LINEAR = 4, GPK_K_CONST = 5 };
+enum { GPK_K_EQ = 0, GPK_K_MATERN12 = 1, GPK_K_MATERN32 = 2, GPK_K_MATERN52 = 3, GPK_K_LINEAR = 4, GPK_K_CONST = 5, GPK_K_RQ = 6 };
 
 GPK_KNOB(int, g_kmat_compact, 1);   // tuning knob (gpk_tune(34, v)): 1-D compact grid for the lower triangle of a square matrix
 GPK_KNOB(int, g_kmat_band, 1);      // tuning knob (gpk_tune(12, v)): 1 = row-band kernel, 0 = the one-tile-per-workgroup kernel
@@ -57,6 +57,10 @@ struct KmatArgs {
     int nbands;       // row-band kernel: number of row bands (TM rows each)
     int compact;      // row-band kernel, lower triangle of one square matrix: a 1-D grid of exactly the (row band, column chunk) pairs on or
                       // below the diagonal -- `compact` = row bands per column chunk; 0 = the plain 2-D grid
+    // shape parameters (GPK_K_RQ: alpha, and 1 / (2 alpha)).  Behind everything else: the programs that have none read the same
+    // argument offsets as before and compile to the code they compiled to without these two arrays.
+    T shape[GPK_MAX_TERMS];
+    T hshape[GPK_MAX_TERMS];
 };
 
 __device__ __forceinline__ double gpk_exp_neg(double a);     // (below) branch-free fp64 exp of a non-positive argument
@@ -87,7 +91,17 @@ __device__ __forceinline__ double gpk_sqrtk<double>(double x) {
 template <>
 __device__ __forceinline__ float gpk_sqrtk<float>(float x) { return sqrtf(x); }
 
+// log(1 + u), u >= 0 (rational quadratic: u = q / (2 alpha)); the library routines keep full relative accuracy for small u
 template <typename T>
+__device__ __forceinline__ T gpk_log1p(T u);
+template <>
+__device__ __forceinline__ double gpk_log1p<double>(double u) { return log1p(u); }
+template <>
+__device__ __forceinline__ float gpk_log1p<float>(float u) { return log1pf(u); }
+
+// RQ: the term table may hold rational-quadratic terms (a launch with shape parameters).  A template parameter, not one more branch
+// of the kind switch: the table program of kernels WITHOUT such a term stays the code it was (the logarithm costs ~25 registers).
+template <typename T, bool RQ>
 __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
     T val = T(0);
     for (int t = 0; t < p.nterms; ++t) {
@@ -106,6 +120,9 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
             k = (T(1) + s + s * s * T(1.0 / 3.0)) * gpk_exp<T>(-s);
         } else if (kind == GPK_K_LINEAR) {
             k = dot * p.terms[t].ils2;
+        } else if (RQ && kind == GPK_K_RQ) {
+            // (1 + u)^(-alpha), u = q / (2 alpha), as exp(-alpha log1p(u)): the exponent is <= 0 like every other on this path
+            k = gpk_exp<T>(-p.shape[t] * gpk_log1p<T>(q * p.hshape[t]));
         } else {
             k = T(1);
         }
@@ -114,7 +131,7 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
     return val;
 }
 
-template <typename T, bool DOT, int DC>
+template <typename T, bool DOT, int DC, bool RQ>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
     constexpr int VEC = Traits<T>::VEC;
@@ -184,7 +201,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             const int col = colb + v;
-            T val = eval_terms<T>(p, r2[r][v], dt[r][v]);
+            T val = eval_terms<T, RQ>(p, r2[r][v], dt[r][v]);
             if (p.symmetric && col == row) {
                 val += p.diag_add;
                 if (p.diag_vec != nullptr) val += p.diag_vec[b * p.sDiag + row];
@@ -222,7 +239,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
 //    or EQ + Linear -- instead of a per-element loop over a term table with a kind switch; fp32 EQ is one
 //    multiply + v_exp_f32 (exp2 of a pre-scaled argument, <= 2 ulp) instead of the library expf.
 // ---------------------------------------------------------------------------
-enum { PROG_GENERIC = -1, PROG_EQ = 0, PROG_M12 = 1, PROG_M32 = 2, PROG_M52 = 3, PROG_EQ_LINEAR = 6 };
+enum { PROG_GENERIC_RQ = -2, PROG_GENERIC = -1, PROG_EQ = 0, PROG_M12 = 1, PROG_M32 = 2, PROG_M52 = 3, PROG_EQ_LINEAR = 6, PROG_RQ = 7 };
 
 // exp(a), a <= 0, through v_exp_f32 (2^x) at libm accuracy: the product a * log2(e) is formed with its rounding error
 // (two FMAs), split into an integer and a fraction in [-0.5, 0.5], and only the fraction (plus the error) goes through the
@@ -337,10 +354,12 @@ __device__ __forceinline__ float gpk_exp_neg_t(float a, const float*) { return g
 
 template <typename T, int PROG>
 __device__ __forceinline__ T eval_prog(const KmatArgs<T>& p, T r2, T dot, const T* etab) {
-    if (PROG == PROG_GENERIC) return eval_terms<T>(p, r2, dot);
+    if (PROG == PROG_GENERIC) return eval_terms<T, false>(p, r2, dot);
+    if (PROG == PROG_GENERIC_RQ) return eval_terms<T, true>(p, r2, dot);
     const T v0 = p.terms[0].variance, c0 = p.terms[0].ils2;
     if (PROG == PROG_EQ) return v0 * gpk_exp_neg_t(T(-0.5) * c0 * r2, etab);
     if (PROG == PROG_EQ_LINEAR) return v0 * gpk_exp_neg_t(T(-0.5) * c0 * r2, etab) + p.terms[1].variance * p.terms[1].ils2 * dot;
+    if (PROG == PROG_RQ) return v0 * gpk_exp_neg_t(-p.shape[0] * gpk_log1p<T>(r2 * (c0 * p.hshape[0])), etab);    // (c0 / (2 alpha): uniform)
     // (the constants below are uniform: formed once per workgroup.  3 c0 r2 for (3 c0) r2 and v0 + v0 s + (v0 / 3) s^2 in Horner form
     // move a value by an ulp or two against the literal formula -- the price of 1 + 2 operations less per element)
     if (PROG == PROG_M12) return v0 * gpk_exp_neg_t(-gpk_sqrtk<T>(r2 * c0), etab);
@@ -363,8 +382,9 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     constexpr int YL = (TN * DC + 255) / 256;   // Y elements each thread stages per column tile
     __shared__ T xs[TM * DC];
     __shared__ __attribute__((aligned(16))) T ys[2][DC * TNP];   // Y tile, dimension-major: ys[j][c]
-    constexpr bool ETAB = sizeof(T) == 8 && PROG != PROG_GENERIC;  // fp64: exp through the 2^(j/128) table (gpk_exp_neg_tab)
-    constexpr bool PK32 = sizeof(T) == 4 && PROG != PROG_GENERIC;   // fp32: two values per instruction
+    constexpr bool TABLE = PROG == PROG_GENERIC || PROG == PROG_GENERIC_RQ;   // the term-table programs
+    constexpr bool ETAB = sizeof(T) == 8 && !TABLE;  // fp64: exp through the 2^(j/128) table (gpk_exp_neg_tab)
+    constexpr bool PK32 = sizeof(T) == 4 && !TABLE;   // fp32: two values per instruction
     __shared__ T etab[ETAB ? 128 : 1];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -471,6 +491,12 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         const float ca = -0.5f * c0;
                         k = gpk_exp_neg_pk(acc[h] * gpk_f2{ca, ca}) * vv;
                         if (PROG == PROG_EQ_LINEAR) k = __builtin_elementwise_fma(dot[h], gpk_f2{vl, vl}, k);
+                    } else if (PROG == PROG_RQ) {
+                        // exp(-alpha log1p(u)): the logarithm has no packed form, the scaling and the exponential do
+                        const float cu = c0 * (float)p.hshape[0], na = -(float)p.shape[0];
+                        const gpk_f2 u = acc[h] * gpk_f2{cu, cu};
+                        const gpk_f2 lg = {log1pf(u.x), log1pf(u.y)};
+                        k = gpk_exp_neg_pk(lg * gpk_f2{na, na}) * vv;
                     } else {
                         // Matern: sqrt straight from v_sqrt_f32 (1 ulp; the library sqrtf spends ~10 more instructions on rescaling
                         // denormal arguments, i.e. distances below 1e-19, and on the last half ulp)
@@ -554,7 +580,7 @@ __global__ __launch_bounds__(256) void kdiag_kernel(KdiagArgs<T> p) {
     T nrm = T(0);
     for (int j = 0; j < p.d; ++j) nrm += x[j] * x[j];
     T val = T(0);
-    for (int t = 0; t < p.nterms; ++t)
+    for (int t = 0; t < p.nterms; ++t)      // (every stationary kind is 1 at distance 0 -- GPK_K_RQ too, whatever its alpha)
         val += p.terms[t].variance * (p.terms[t].kind == GPK_K_LINEAR ? nrm * p.terms[t].ils2 : T(1));
     p.out[b * p.sO + i] = val;
 }
@@ -567,7 +593,7 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
                     const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
-                    hipStream_t stream) {
+                    hipStream_t stream, const double* shapes) {
     if (n <= 0 || m <= 0 || batch <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
     if (n > INT32_MAX || m > INT32_MAX || batch > 65535) return GPK_ERR_ARG(6);
@@ -580,11 +606,22 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     a.nterms = nterms;
     a.need_dot = 0;
     for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_CONST) return GPK_ERR_ARG(1);
+        if (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_RQ) return GPK_ERR_ARG(1);
         a.terms[t].kind = kinds[t];
         a.terms[t].variance = (T)variances[t];
         a.terms[t].ils2 = (T)(inv_ls[t] * inv_ls[t]);
         if (kinds[t] == GPK_K_LINEAR) a.need_dot = 1;
+    }
+    bool has_rq = false;
+    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+        a.shape[t] = a.hshape[t] = T(0);
+        if (t < nterms && kinds[t] == GPK_K_RQ) {
+            has_rq = true;
+            if (shapes == nullptr) return GPK_ERR_ARG(1);          // an RQ term through an entry that carries no alpha
+            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
+            a.shape[t] = (T)shapes[t];
+            a.hshape[t] = (T)(0.5 / shapes[t]);
+        }
     }
     a.diag_add = (T)diag_add;
     a.symmetric = symmetric; a.lower_only = lower_only; a.accumulate = accumulate;
@@ -595,9 +632,10 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     int prog = PROG_GENERIC;
     if (nterms == 1 && kinds[0] >= GPK_K_EQ && kinds[0] <= GPK_K_MATERN52) prog = kinds[0];
     if (nterms == 2 && kinds[0] == GPK_K_EQ && kinds[1] == GPK_K_LINEAR) prog = PROG_EQ_LINEAR;
+    if (nterms == 1 && kinds[0] == GPK_K_RQ) prog = PROG_RQ;
     // (round 2, with the library sqrt + exp: the one-tile kernel was 15 % faster for fp64 kernels with a square root -- 0.53 vs 0.62 ms at
     // N = 16384 -- and kept them; round 5: with the branch-free exp of round 3 and the rsq-based sqrt above, knob 51 decides)
-    const bool band_ok = sizeof(T) == 4 || prog == PROG_EQ || prog == PROG_EQ_LINEAR || g_kmat_band_f64_sqrt;
+    const bool band_ok = sizeof(T) == 4 || prog == PROG_EQ || prog == PROG_EQ_LINEAR || prog == PROG_RQ || g_kmat_band_f64_sqrt;
     if (d <= 8 && g_kmat_band && band_ok) {
         const int64_t tiles_x = gpk_cdiv(m, 64 * VEC);
         int ct = CT_MAX;
@@ -631,8 +669,12 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
             case PROG_M32: GPK_BAND_DC(PROG_M32, false); break;
             case PROG_M52: GPK_BAND_DC(PROG_M52, false); break;
             case PROG_EQ_LINEAR: GPK_BAND_DC(PROG_EQ_LINEAR, true); break;
+            case PROG_RQ: GPK_BAND_DC(PROG_RQ, false); break;
             default:
-                if (a.need_dot) GPK_BAND_DC(PROG_GENERIC, true);
+                if (has_rq) {
+                    if (a.need_dot) GPK_BAND_DC(PROG_GENERIC_RQ, true);
+                    else GPK_BAND_DC(PROG_GENERIC_RQ, false);
+                } else if (a.need_dot) GPK_BAND_DC(PROG_GENERIC, true);
                 else GPK_BAND_DC(PROG_GENERIC, false);
         }
 #undef GPK_BAND_DC
@@ -641,12 +683,16 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
         return GPK_OK;
     }
     dim3 grid((unsigned)gpk_cdiv(m, 64 * VEC), (unsigned)gy, (unsigned)batch);
-#define GPK_KMAT_LAUNCH(DCV)                                                                     \
-    do {                                                                                         \
-        if (a.need_dot)                                                                          \
-            hipLaunchKernelGGL((kmat_kernel<T, true, DCV>), grid, dim3(256), 0, stream, a);      \
-        else                                                                                     \
-            hipLaunchKernelGGL((kmat_kernel<T, false, DCV>), grid, dim3(256), 0, stream, a);     \
+#define GPK_KMAT_LAUNCH(DCV)                                                                            \
+    do {                                                                                                \
+        if (has_rq && a.need_dot)                                                                       \
+            hipLaunchKernelGGL((kmat_kernel<T, true, DCV, true>), grid, dim3(256), 0, stream, a);       \
+        else if (has_rq)                                                                                \
+            hipLaunchKernelGGL((kmat_kernel<T, false, DCV, true>), grid, dim3(256), 0, stream, a);      \
+        else if (a.need_dot)                                                                            \
+            hipLaunchKernelGGL((kmat_kernel<T, true, DCV, false>), grid, dim3(256), 0, stream, a);      \
+        else                                                                                            \
+            hipLaunchKernelGGL((kmat_kernel<T, false, DCV, false>), grid, dim3(256), 0, stream, a);     \
     } while (0)
     if (d <= 1)
         GPK_KMAT_LAUNCH(1);
@@ -664,9 +710,14 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
 template <typename T>
 int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
                      const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
-                     int64_t batch, hipStream_t stream) {
+                     int64_t batch, hipStream_t stream, const double* shapes) {
     if (n <= 0 || batch <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
+    for (int t = 0; t < nterms; ++t)
+        if (kinds[t] == GPK_K_RQ) {
+            if (shapes == nullptr) return GPK_ERR_ARG(1);
+            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
+        }
     KdiagArgs<T> a;
     a.X = X; a.out = out; a.ldx = ldx; a.sX = sX; a.sO = sO;
     a.n = (int)n; a.d = d; a.nterms = nterms;
@@ -685,8 +736,8 @@ int gpk_kdiag_launch(const int* kinds, const double* variances, const double* in
     template int gpk_kmat_launch<T>(const int*, const double*, const double*, int, const T*, int64_t, \
                                     int64_t, int64_t, const T*, int64_t, int64_t, int64_t, int, T*,   \
                                     int64_t, int64_t, int64_t, int, int, double, const T*, int64_t,   \
-                                    int, hipStream_t);                                                \
+                                    int, hipStream_t, const double*);                                 \
     template int gpk_kdiag_launch<T>(const int*, const double*, const double*, int, const T*, int64_t, \
-                                     int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t);
+                                     int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t, const double*);
 GPK_INST(double)
 GPK_INST(float)

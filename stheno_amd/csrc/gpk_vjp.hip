@@ -9,9 +9,13 @@
 // entries count twice): pairwise distances are recomputed from x, G is never stored.
 // HBM-bound: reads N^2/2 elements once.  Output: per-workgroup partial sums
 // [nblocks][2 T + 1] (S1_t, S2_t, trace(G)) -- summed by the caller -- and diag(G).
+//
+// Kinds with a SHAPE parameter (rational quadratic: alpha) go through the `_s` entries: the same kernels instantiated with SH = true,
+// which know VK_RQ and carry a third sum per term, S3_t = sum_ij G_ij d kappa_t / d alpha_t, in partial rows of 3 T + 1 elements.
+// The SH = false instantiations are what the entries without shapes launch: the code they have always been.
 #include "gpk_common.hpp"
 
-enum { VK_EQ = 0, VK_MATERN12 = 1, VK_MATERN32 = 2, VK_MATERN52 = 3, VK_LINEAR = 4, VK_CONST = 5 };
+enum { VK_EQ = 0, VK_MATERN12 = 1, VK_MATERN32 = 2, VK_MATERN52 = 3, VK_LINEAR = 4, VK_CONST = 5, VK_RQ = 6 };
 
 namespace {
 
@@ -32,6 +36,7 @@ struct VjpArgs {
     T ils2[GPK_MAX_TERMS];
     T g[VMAXC];
     T s;
+    T shape[GPK_MAX_TERMS];    // (SH only; behind everything else)
 };
 
 template <typename T>
@@ -75,7 +80,27 @@ __device__ __forceinline__ void kappa_and_dq(int kind, T q, T& k, T& dkq) {
 }
 
 template <typename T>
+__device__ __forceinline__ T vlog1p(T x);
+template <>
+__device__ __forceinline__ double vlog1p<double>(double x) { return log1p(x); }
+template <>
+__device__ __forceinline__ float vlog1p<float>(float x) { return log1pf(x); }
+
+// rational quadratic kappa = (1 + u)^(-alpha), u = q / (2 alpha):  kappa' = -kappa / (2 (1 + u)),  kappa' q,
+// d kappa / d alpha = kappa (u / (1 + u) - log1p(u))
+template <typename T>
+__device__ __forceinline__ void kappa_rq(T q, T a, T& k, T& dkq, T& dk, T& da) {
+    const T u = q * (T(0.5) / a);
+    const T lg = vlog1p<T>(u), ri = T(1) / (T(1) + u);
+    k = vexp<T>(-a * lg);
+    dk = T(-0.5) * k * ri;
+    dkq = dk * q;
+    da = k * (u * ri - lg);
+}
+
+template <typename T, bool SH>
 __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
+    constexpr int NS = SH ? 3 : 2;      // sums per term
     __shared__ T xi[VT * VDC], xj[VT * VDC], ai[VT * VMAXC], aj[VT * VMAXC];
     __shared__ T red[4 * (2 * GPK_MAX_TERMS + 1)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -151,9 +176,9 @@ __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
         }
     }
     // per term: two block-wide sums (no per-thread accumulator array -> no scratch)
-    T* out = p.partial + (int64_t)bid * (2 * GPK_MAX_TERMS + 1);
+    T* out = p.partial + (int64_t)bid * (NS * GPK_MAX_TERMS + 1);
     for (int t = 0; t <= p.nterms; ++t) {
-        T s1 = T(0), s2 = T(0);
+        T s1 = T(0), s2 = T(0), s3 = T(0);
         if (t < p.nterms) {
             const int kind = p.kind[t];
             const T ils2 = p.ils2[t];
@@ -163,7 +188,13 @@ __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
                 for (int v = 0; v < 4; ++v) {
                     const T q = (kind == VK_LINEAR ? dt[u][v] : r2[u][v]) * ils2;
                     T k, dkq;
-                    kappa_and_dq<T>(kind, q, k, dkq);
+                    if (SH && kind == VK_RQ) {
+                        T dk, da;
+                        kappa_rq<T>(q, p.shape[t], k, dkq, dk, da);
+                        s3 += Gw[u][v] * da;
+                    } else {
+                        kappa_and_dq<T>(kind, q, k, dkq);
+                    }
                     s1 += Gw[u][v] * k;
                     s2 += Gw[u][v] * dkq;
                 }
@@ -174,20 +205,23 @@ __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
         for (int o = 32; o > 0; o >>= 1) {
             s1 += __shfl_xor(s1, o, 64);
             s2 += __shfl_xor(s2, o, 64);
+            if (SH) s3 += __shfl_xor(s3, o, 64);
         }
         __syncthreads();
         if (lane == 0) {
             red[wave * 2] = s1;
             red[wave * 2 + 1] = s2;
+            if (SH) red[8 + wave] = s3;
         }
         __syncthreads();
         if (tid == 0) {
             const T a1 = red[0] + red[2] + red[4] + red[6], a2 = red[1] + red[3] + red[5] + red[7];
             if (t < p.nterms) {
-                out[2 * t] = a1;
-                out[2 * t + 1] = a2;
+                out[NS * t] = a1;
+                out[NS * t + 1] = a2;
+                if (SH) out[NS * t + 2] = red[8] + red[9] + red[10] + red[11];
             } else {
-                out[2 * GPK_MAX_TERMS] = a1;
+                out[NS * GPK_MAX_TERMS] = a1;
             }
         }
     }
@@ -214,6 +248,7 @@ struct VjpDenseArgs {
     int n, m, d, nterms, tiles_per_chunk, ctiles, nchunks;
     int kind[GPK_MAX_TERMS];
     T ils2[GPK_MAX_TERMS], var[GPK_MAX_TERMS];
+    T shape[GPK_MAX_TERMS];    // (SH only; behind everything else)
 };
 
 // kappa(q), kappa'(q) q and kappa'(q)   (kappa' of exp(-sqrt(q)) is singular at 0: reported as 0)
@@ -249,20 +284,25 @@ __device__ __forceinline__ void kappa_all(int kind, T q, T& k, T& dkq, T& dk) {
     }
 }
 
-template <typename T>
+template <typename T, bool SH>
 __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) {
+    constexpr int NS = SH ? 3 : 2;      // sums per term
     __shared__ T xi[DT * VDC], yj[DT * VDC];
     __shared__ T csred[16 * DT];
-    __shared__ T red[4 * 2 * GPK_MAX_TERMS];
+    __shared__ T red[4 * NS * GPK_MAX_TERMS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ty = tid >> 4, tx = tid & 15;     // 16 x 16 threads, 4 x 4 elements each
     const int rt = blockIdx.x, chunk = blockIdx.y;
     const int i0 = rt * DT;
     const bool want_gx = p.gradx != nullptr;     // launcher guarantees d <= VDC then
 
-    T s1[GPK_MAX_TERMS], s2[GPK_MAX_TERMS];
+    T s1[GPK_MAX_TERMS], s2[GPK_MAX_TERMS], s3[SH ? GPK_MAX_TERMS : 1];
 #pragma unroll
     for (int t = 0; t < GPK_MAX_TERMS; ++t) s1[t] = s2[t] = T(0);
+    if (SH) {
+#pragma unroll
+        for (int t = 0; t < GPK_MAX_TERMS; ++t) s3[SH ? t : 0] = T(0);
+    }
     T gx[4][VDC];
 #pragma unroll
     for (int u = 0; u < 4; ++u)
@@ -340,7 +380,13 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
                     for (int v = 0; v < 4; ++v) {
                         const T q = (kind == VK_LINEAR ? dt[u][v] : r2[u][v]) * ils2;
                         T k, dkq, dk;
-                        kappa_all<T>(kind, q, k, dkq, dk);
+                        if (SH && kind == VK_RQ) {
+                            T da;
+                            kappa_rq<T>(q, p.shape[t], k, dkq, dk, da);
+                            s3[SH ? t : 0] += Ge[u][v] * da;
+                        } else {
+                            kappa_all<T>(kind, q, k, dkq, dk);
+                        }
                         s1[t] += Ge[u][v] * k;
                         s2[t] += Ge[u][v] * dkq;
                         kfull[u][v] += var * k;
@@ -391,27 +437,29 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
     }
 
     // per-term sums of the whole workgroup
-    T* out = p.partial + ((int64_t)rt * p.nchunks + chunk) * (2 * GPK_MAX_TERMS + 1);
+    T* out = p.partial + ((int64_t)rt * p.nchunks + chunk) * (NS * GPK_MAX_TERMS + 1);
 #pragma unroll
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             s1[t] += __shfl_xor(s1[t], o, 64);
             s2[t] += __shfl_xor(s2[t], o, 64);
+            if (SH) s3[SH ? t : 0] += __shfl_xor(s3[SH ? t : 0], o, 64);
         }
     }
     __syncthreads();
     if (lane == 0) {
 #pragma unroll
         for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-            red[(wave * GPK_MAX_TERMS + t) * 2] = s1[t];
-            red[(wave * GPK_MAX_TERMS + t) * 2 + 1] = s2[t];
+            red[(wave * GPK_MAX_TERMS + t) * NS] = s1[t];
+            red[(wave * GPK_MAX_TERMS + t) * NS + 1] = s2[t];
+            if (SH) red[(wave * GPK_MAX_TERMS + t) * NS + 2] = s3[SH ? t : 0];
         }
     }
     __syncthreads();
-    if (tid < 2 * GPK_MAX_TERMS) {
-        out[tid] = red[tid] + red[2 * GPK_MAX_TERMS + tid] + red[4 * GPK_MAX_TERMS + tid] + red[6 * GPK_MAX_TERMS + tid];
-    } else if (tid == 2 * GPK_MAX_TERMS) {
+    if (tid < NS * GPK_MAX_TERMS) {
+        out[tid] = red[tid] + red[NS * GPK_MAX_TERMS + tid] + red[2 * NS * GPK_MAX_TERMS + tid] + red[3 * NS * GPK_MAX_TERMS + tid];
+    } else if (tid == NS * GPK_MAX_TERMS) {
         out[tid] = T(0);
     }
     // d/dX: reduce over the 16 tx lanes of each row group, one partial per column chunk
@@ -442,13 +490,19 @@ void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64
     if (tiles_per_chunk) *tiles_per_chunk = tpc;
 }
 
-template <typename T>
-int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
-                              const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                              const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                              T* colsum, T* gradx, hipStream_t stream) {
+// SH = false: kinds without a shape parameter only (an RQ term is refused: no alpha was given); SH = true: `shapes` is read for RQ terms
+template <typename T, bool SH>
+static int vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                            const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                            const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
+                            T* colsum, T* gradx, hipStream_t stream) {
     if (n <= 0 || m <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(5);
+    for (int t = 0; t < nterms; ++t) {
+        if (kinds[t] < VK_EQ || kinds[t] > VK_RQ) return GPK_ERR_ARG(1);
+        if (kinds[t] == VK_RQ && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
+        if (kinds[t] == VK_RQ && !(shapes[t] > 0)) return GPK_ERR_ARG(4);
+    }
     if (n > INT32_MAX || m > INT32_MAX) return GPK_ERR_ARG(7);
     if ((w == nullptr) != (b == nullptr)) return GPK_ERR_ARG(17);
     if (gradx != nullptr && d > VDC) return GPK_ERR_ARG(12);     // d/dX is implemented for d <= 8
@@ -464,12 +518,38 @@ int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const d
         a.kind[t] = t < nterms ? kinds[t] : VK_CONST;
         a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
         a.var[t] = t < nterms ? (T)variances[t] : T(0);
+        a.shape[t] = (SH && t < nterms && kinds[t] == VK_RQ) ? (T)shapes[t] : T(1);
     }
     if (nc > 65535) return GPK_ERR_ARG(9);
-    hipLaunchKernelGGL((kmat_vjp_dense_kernel<T>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, SH>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
+
+template <typename T>
+int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
+                              const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                              const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
+                              T* colsum, T* gradx, hipStream_t stream) {
+    return vjp_dense_launch<T, false>(kinds, variances, inv_ls, nullptr, nterms, X, n, ldx, Y, m, ldy, d, G, ldg, colscale, w, b, partial,
+                                      colsum, gradx, stream);
+}
+template <typename T>
+int gpk_kmat_vjp_dense_s_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                                const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                                const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
+                                T* colsum, T* gradx, hipStream_t stream) {
+    return vjp_dense_launch<T, true>(kinds, variances, inv_ls, shapes, nterms, X, n, ldx, Y, m, ldy, d, G, ldg, colscale, w, b, partial,
+                                     colsum, gradx, stream);
+}
+template int gpk_kmat_vjp_dense_s_launch<double>(const int*, const double*, const double*, const double*, int, const double*, int64_t,
+                                                 int64_t, const double*, int64_t, int64_t, int, const double*, int64_t,
+                                                 const double*, const double*, const double*, double*, double*,
+                                                 double*, hipStream_t);
+template int gpk_kmat_vjp_dense_s_launch<float>(const int*, const double*, const double*, const double*, int, const float*, int64_t,
+                                                int64_t, const float*, int64_t, int64_t, int, const float*, int64_t,
+                                                const float*, const float*, const float*, float*, float*, float*,
+                                                hipStream_t);
 
 template int gpk_kmat_vjp_dense_launch<double>(const int*, const double*, const double*, int, const double*, int64_t,
                                                int64_t, const double*, int64_t, int64_t, int, const double*, int64_t,
@@ -486,12 +566,17 @@ int64_t gpk_kmat_vjp_blocks_impl(int64_t n) {
 }
 
 // partial: gpk_kmat_vjp_blocks(n) * (2 * GPK_MAX_TERMS + 1) elements; diag_g: n elements
-template <typename T>
-int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, int nterms, const T* X, int64_t n, int64_t ldx,
-                        int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
-                        T* partial, T* diag_g, hipStream_t stream) {
+template <typename T, bool SH>
+static int vjp_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
+                      int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
+                      T* partial, T* diag_g, hipStream_t stream) {
     if (n <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(3);
+    for (int t = 0; t < nterms; ++t) {
+        if (kinds[t] < VK_EQ || kinds[t] > VK_RQ) return GPK_ERR_ARG(1);
+        if (kinds[t] == VK_RQ && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
+        if (kinds[t] == VK_RQ && !(shapes[t] > 0)) return GPK_ERR_ARG(3);
+    }
     if (C < 1 || C > VMAXC) return GPK_ERR_ARG(11);
     if (n > INT32_MAX) return GPK_ERR_ARG(5);
     VjpArgs<T> a;
@@ -508,12 +593,33 @@ int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, int nterms, cons
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
         a.kind[t] = t < nterms ? kinds[t] : VK_CONST;
         a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
+        a.shape[t] = (SH && t < nterms && kinds[t] == VK_RQ) ? (T)shapes[t] : T(1);
     }
     const int64_t nb = gpk_kmat_vjp_blocks_impl(n);
-    hipLaunchKernelGGL((kmat_vjp_kernel<T>), dim3((unsigned)nb), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((kmat_vjp_kernel<T, SH>), dim3((unsigned)nb), dim3(256), 0, stream, a);
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
+
+template <typename T>
+int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, int nterms, const T* X, int64_t n, int64_t ldx,
+                        int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
+                        T* partial, T* diag_g, hipStream_t stream) {
+    return vjp_launch<T, false>(kinds, inv_ls, nullptr, nterms, X, n, ldx, d, Kinv, ldk, A, C, lda, g, partial, diag_g, stream);
+}
+// partial: gpk_kmat_vjp_blocks(n) * (3 * GPK_MAX_TERMS + 1) elements
+template <typename T>
+int gpk_kmat_vjp_s_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
+                          int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
+                          T* partial, T* diag_g, hipStream_t stream) {
+    return vjp_launch<T, true>(kinds, inv_ls, shapes, nterms, X, n, ldx, d, Kinv, ldk, A, C, lda, g, partial, diag_g, stream);
+}
+template int gpk_kmat_vjp_s_launch<double>(const int*, const double*, const double*, int, const double*, int64_t, int64_t, int,
+                                           const double*, int64_t, const double*, int, int64_t, const double*,
+                                           double*, double*, hipStream_t);
+template int gpk_kmat_vjp_s_launch<float>(const int*, const double*, const double*, int, const float*, int64_t, int64_t, int,
+                                          const float*, int64_t, const float*, int, int64_t, const double*, float*,
+                                          float*, hipStream_t);
 
 template int gpk_kmat_vjp_launch<double>(const int*, const double*, int, const double*, int64_t, int64_t, int,
                                          const double*, int64_t, const double*, int, int64_t, const double*,

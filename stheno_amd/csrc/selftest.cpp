@@ -3,6 +3,7 @@
 // Makefile into gpk_selftest; run on the MI355X box:
 //     ./gpk_selftest            correctness of every entry point vs host loops
 //     ./gpk_selftest --perf     + timings (HIP events) of the hot kernels
+//     ./gpk_selftest --rq       only the checks of the term kind with a shape parameter (rational quadratic)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -1040,6 +1041,165 @@ static void test_vjp_dense() {
     }
 }
 
+
+// ----------------------------------------------------------------------------
+// rational quadratic: the kind with a shape parameter (gpk_kmat_s / gpk_kdiag_s / gpk_kmat_vjp_s / gpk_kmat_vjp_dense_s)   --rq
+// ----------------------------------------------------------------------------
+// RQ values element by element against the 80-bit reference, in units of eps (1 + alpha log1p(u)), u = q / (2 alpha): the rounding
+// of the squared distance reaches the value multiplied by the exponent alpha log1p(u) (at most, for u >> 1), the rest is the device's
+// log1p and exp.  `generic`: a second term of variance 0 sends the call through the term-table program instead of the dedicated one.
+// Asserted at twice the worst figure measured on the MI355X (profiles/README.md), which leaves room for another compiler's log1p.
+#define GPK_RQ_ULP_BOUND 4.9      /* measured: 2.41 (fp32), 2.26 (fp64) */
+template <typename T>
+static void test_rq_ulp(double alpha, double scale, double ilv, bool generic) {
+    const int n = 192, m = 320, d = 8;
+    auto X = randv<T>((size_t)n * d, scale), Y = randv<T>((size_t)m * d, scale);
+    for (int k = 0; k < d; ++k) Y[k] = X[k] * (T)(1 + 64 * (double)std::numeric_limits<T>::epsilon());
+    for (int k = 0; k < d; ++k) Y[d + k] = X[d + k];
+    Dev<T> dX(X.size()), dY(Y.size()), dO((size_t)n * m);
+    dX.up(X); dY.up(Y);
+    int kinds[2] = {GPK_K_RQ, GPK_K_CONST};
+    double var[2] = {1.3, 0.0}, il[2] = {ilv, 1.0}, sh[2] = {alpha, 0.0};
+    int st = gpk_kmat_s(DT<T>::v, kinds, var, il, sh, generic ? 2 : 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    auto got = dO.down();
+    double worst = 0, amax = 0;
+    bool dup_exact = (double)got[(size_t)1 * m + 1] == (double)(T)1.3;      // x_1 == y_1: exactly the variance
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < m; ++j) {
+            long double r2 = 0;
+            for (int k = 0; k < d; ++k) { const long double df = (long double)X[(size_t)i * d + k] - (long double)Y[(size_t)j * d + k]; r2 += df * df; }
+            const long double u = r2 * (long double)ilv * (long double)ilv / (2 * (long double)alpha);
+            const long double a = (long double)alpha * log1pl(u);
+            const long double v = 1.3L * expl(-a);
+            if (a > (sizeof(T) == 8 ? 700 : 85)) continue;
+            const double e = (double)(fabsl((long double)got[(size_t)i * m + j] - v) / v) / ((double)std::numeric_limits<T>::epsilon() * (1.0 + (double)a));
+            worst = std::max(worst, e);
+            amax = std::max(amax, (double)a);
+        }
+    char nm[200];
+    snprintf(nm, sizeof nm, "kmat_%s rq alpha=%g il=%g %s elementwise, exponents up to %.0f: worst error / (eps (1 + alpha log1p u)) st%d", DT<T>::name(), alpha, ilv,
+             generic ? "term table" : "own program", amax, st);
+    report(nm, st ? INFINITY : worst, GPK_RQ_ULP_BOUND);
+    report(std::string("kmat_") + DT<T>::name() + " rq duplicate point gives the variance exactly", dup_exact ? 0.0 : INFINITY, 0.0);
+}
+static void kappa_rq_host(double q, double a, double& k, double& dkq, double& dk, double& da) {
+    const double u = q / (2 * a), lg = std::log1p(u);
+    k = std::exp(-a * lg); dk = -0.5 * k / (1 + u); dkq = dk * q; da = k * (u / (1 + u) - lg);
+}
+template <typename T>
+static void test_rq() {
+    for (int band = 1; band >= 0; --band) {
+        gpk_tune(12, band);
+        for (double alpha : {0.1, 1.0, 50.0})
+            for (int generic = 0; generic < 2; ++generic) {
+                test_rq_ulp<T>(alpha, 1.0, 0.9, generic);
+                test_rq_ulp<T>(alpha, 1.0, 30.0, generic);
+                test_rq_ulp<T>(alpha, 1e-3, 1.0, generic);
+            }
+    }
+    gpk_tune(12, 1);
+    {   // the entries with shapes and kinds without one: the same bits as the entries without; an RQ term without alpha is refused
+        const int n = 130, d = 3;
+        auto X = randv<T>((size_t)n * d);
+        Dev<T> dX(X.size()), dA((size_t)n * n), dB((size_t)n * n);
+        dX.up(X);
+        int kind = GPK_K_EQ, rq = GPK_K_RQ; double var = 0.8, il = 1.1, sh = 7.0, bad = 0.0;
+        int st = gpk_kmat(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        st |= gpk_kmat_s(DT<T>::v, &kind, &var, &il, &sh, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dB.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        auto a = dA.down(), b = dB.down();
+        report(std::string("kmat_s without rq terms == kmat, bit for bit ") + DT<T>::name(), (st == 0 && !memcmp(a.data(), b.data(), a.size() * sizeof(T))) ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat(DT<T>::v, &rq, &var, &il, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        report(std::string("kmat refuses an rq term (no alpha) ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_s(DT<T>::v, &rq, &var, &il, &bad, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        report(std::string("kmat_s refuses alpha <= 0 ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
+        Dev<T> dD(n);
+        int k2[2] = {GPK_K_RQ, GPK_K_LINEAR}; double v2[2] = {0.7, 1.3}, l2[2] = {1.0, 0.5}, s2[2] = {0.3, 0.0};
+        st = gpk_kdiag_s(DT<T>::v, k2, v2, l2, s2, 2, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        std::vector<double> ref(n);
+        for (int i = 0; i < n; ++i) { double nr = 0; for (int k = 0; k < d; ++k) nr += (double)X[i * d + k] * X[i * d + k]; ref[i] = 0.7 + 1.3 * 0.25 * nr; }
+        report(std::string("kdiag_s rq + linear ") + DT<T>::name(), st ? INFINITY : relerr(dD.down(), ref), DT<T>::eps * 50);
+    }
+    {   // explicit-cotangent VJP with RQ terms: three sums per term, column sums, d/dx
+        const int n = 130, m = 257, d = 3, nt = 3;
+        int kinds[nt] = {GPK_K_RQ, GPK_K_EQ, GPK_K_RQ};
+        double var[nt] = {0.6, 0.85, 1.1}, il[nt] = {1.0 / 0.8, 1.0 / 1.1, 1.0 / 2.5}, sh[nt] = {0.4, 0.0, 9.0};
+        const int64_t ldg = m + 5;
+        auto X = randv<T>((size_t)n * d), Y = randv<T>((size_t)m * d), G = randv<T>((size_t)n * ldg);
+        auto cs = randv<T>(m), w = randv<T>(n), b = randv<T>(m);
+        int64_t rt = 0, nc = 0;
+        gpk_kmat_vjp_dense_grid(n, m, &rt, &nc);
+        const int W = 3 * GPK_MAX_TERMS + 1;
+        Dev<T> dX(X.size()), dY(Y.size()), dG(G.size()), dcs(m), dw(n), db(m), dP((size_t)rt * nc * W), dC((size_t)rt * m), dGX((size_t)nc * n * d);
+        dX.up(X); dY.up(Y); dG.up(G); dcs.up(cs); dw.up(w); db.up(b);
+        int st = gpk_kmat_vjp_dense_s(DT<T>::v, kinds, var, il, sh, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg, dcs.p, dw.p, db.p, dP.p, dC.p, dGX.p, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        auto P = dP.down(), C = dC.down(), GX = dGX.down();
+        std::vector<double> rS(3 * nt, 0.0), rC(m, 0.0), rGX((size_t)n * d, 0.0);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < m; ++j) {
+                const double ge = (double)G[(size_t)i * ldg + j] * (double)cs[j] + (double)w[i] * (double)b[j];
+                double r2 = 0;
+                for (int k = 0; k < d; ++k) { const double a = X[(size_t)i * d + k], c = Y[(size_t)j * d + k]; r2 += (a - c) * (a - c); }
+                double kfull = 0;
+                for (int t = 0; t < nt; ++t) {
+                    const double q = r2 * il[t] * il[t];
+                    double k, dkq, dk, da = 0;
+                    if (kinds[t] == GPK_K_RQ) kappa_rq_host(q, sh[t], k, dkq, dk, da); else kappa_all_host(kinds[t], q, k, dkq, dk);
+                    rS[3 * t] += ge * k; rS[3 * t + 1] += ge * dkq; rS[3 * t + 2] += ge * da; kfull += var[t] * k;
+                    for (int c = 0; c < d; ++c) rGX[(size_t)i * d + c] += ge * var[t] * dk * 2 * il[t] * il[t] * ((double)X[(size_t)i * d + c] - (double)Y[(size_t)j * d + c]);
+                }
+                rC[j] += ge * kfull;
+            }
+        std::vector<T> gS(3 * nt, T(0)), gC(m, T(0)), gGX((size_t)n * d, T(0));
+        for (int64_t wg = 0; wg < rt * nc; ++wg) for (int t = 0; t < nt; ++t) for (int c = 0; c < 3; ++c) gS[3 * t + c] += P[(size_t)wg * W + 3 * t + c];
+        for (int64_t r = 0; r < rt; ++r) for (int j = 0; j < m; ++j) gC[j] += C[(size_t)r * m + j];
+        for (int64_t c = 0; c < nc; ++c) for (size_t e = 0; e < (size_t)n * d; ++e) gGX[e] += GX[(size_t)c * n * d + e];
+        std::string nm = std::string("vjp_dense_s_") + DT<T>::name() + " rq+eq+rq n130 m257 d3";
+        report(nm + " sums (S1, S2, S3)", st ? INFINITY : relerr(gS, rS), DT<T>::eps * 50);
+        report(nm + " colsum", st ? INFINITY : relerr(gC, rC), DT<T>::eps * 50);
+        report(nm + " gradx", st ? INFINITY : relerr(gGX, rGX), DT<T>::eps * 50);
+        st = gpk_kmat_vjp_dense(DT<T>::v, kinds, var, il, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg, dcs.p, dw.p, db.p, dP.p, dC.p, dGX.p, nullptr);
+        report(std::string("vjp_dense refuses an rq term (no alpha) ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
+
+        // the log-density form (gpk_kmat_vjp_s): G = 1/2 (A diag(g) A^T - sum(g) Kinv) over the lower triangle of a symmetric Kinv
+        const int C2 = 2;
+        auto Kh = randv<T>((size_t)n * n), A = randv<T>((size_t)n * C2);
+        for (int i = 0; i < n; ++i) for (int j = 0; j < i; ++j) Kh[(size_t)j * n + i] = Kh[(size_t)i * n + j];
+        double g[C2] = {0.7, -0.2};
+        const int64_t nb = gpk_kmat_vjp_blocks(n);
+        Dev<T> dK(Kh.size()), dA(A.size()), dP2((size_t)nb * W), dDg(n);
+        dK.up(Kh); dA.up(A);
+        st = gpk_kmat_vjp_s(DT<T>::v, kinds, il, sh, nt, dX.p, n, d, d, dK.p, n, dA.p, C2, C2, g, dP2.p, dDg.p, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        auto P2 = dP2.down();
+        std::vector<double> rS2(3 * nt + 1, 0.0);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) {
+                double aa = 0;
+                for (int c = 0; c < C2; ++c) aa += g[c] * (double)A[(size_t)i * C2 + c] * (double)A[(size_t)j * C2 + c];
+                const double Gij = 0.5 * (aa - (g[0] + g[1]) * (double)Kh[(size_t)std::max(i, j) * n + std::min(i, j)]);
+                double r2 = 0;
+                for (int k = 0; k < d; ++k) { const double a = X[(size_t)i * d + k], c = X[(size_t)j * d + k]; r2 += (a - c) * (a - c); }
+                for (int t = 0; t < nt; ++t) {
+                    const double q = r2 * il[t] * il[t];
+                    double k, dkq, dk, da = 0;
+                    if (kinds[t] == GPK_K_RQ) kappa_rq_host(q, sh[t], k, dkq, dk, da); else kappa_all_host(kinds[t], q, k, dkq, dk);
+                    rS2[3 * t] += Gij * k; rS2[3 * t + 1] += Gij * dkq; rS2[3 * t + 2] += Gij * da;
+                }
+                if (i == j) rS2[3 * nt] += Gij;
+            }
+        std::vector<T> gS2(3 * nt + 1, T(0));
+        for (int64_t bk = 0; bk < nb; ++bk) {
+            for (int t = 0; t < 3 * nt; ++t) gS2[t] += P2[(size_t)bk * W + t];
+            gS2[3 * nt] += P2[(size_t)bk * W + 3 * GPK_MAX_TERMS];
+        }
+        report(std::string("kmat_vjp_s_") + DT<T>::name() + " rq+eq+rq n130 d3 sums (S1, S2, S3, trace)", st ? INFINITY : relerr(gS2, rS2), DT<T>::eps * 50);
+    }
+}
+
 // ----------------------------------------------------------------------------
 // perf
 // ----------------------------------------------------------------------------
@@ -1435,7 +1595,7 @@ static void la_clock(int n, int nb, int warm = 0) {
 
 // kernel-matrix kernel alone, the shapes of the four GPU configs:  --perf-kmat
 template <typename T>
-static void perf_kmat_case(const char* nm, int nterms, const int* kinds, int64_t n, int64_t m, int d, int batch, int lower, int ldpad = 0) {
+static void perf_kmat_case(const char* nm, int nterms, const int* kinds, int64_t n, int64_t m, int d, int batch, int lower, int ldpad = 0, const double* shapes = nullptr) {
     const bool sym = (m == 0);
     if (sym) m = n;
     const int64_t ldk = m + ldpad;
@@ -1450,7 +1610,8 @@ static void perf_kmat_case(const char* nm, int nterms, const int* kinds, int64_t
         float best = 1e30f;
         for (int rep = 0; rep < 4; ++rep) {
             tm.start();
-            gpk_kmat(DT<T>::v, kinds, var, il, nterms, X.p, n, d, n * d, sym ? X.p : Y.p, m, d, sym ? n * d : 0, d, K.p, ldk, n * ldk, batch, lower, sym ? 1 : 0, 0.1, nullptr, 0, 0, nullptr);
+            if (shapes) gpk_kmat_s(DT<T>::v, kinds, var, il, shapes, nterms, X.p, n, d, n * d, sym ? X.p : Y.p, m, d, sym ? n * d : 0, d, K.p, ldk, n * ldk, batch, lower, sym ? 1 : 0, 0.1, nullptr, 0, 0, nullptr);
+            else gpk_kmat(DT<T>::v, kinds, var, il, nterms, X.p, n, d, n * d, sym ? X.p : Y.p, m, d, sym ? n * d : 0, d, K.p, ldk, n * ldk, batch, lower, sym ? 1 : 0, 0.1, nullptr, 0, 0, nullptr);
             const float ms = tm.stop();
             if (rep) best = std::min(best, ms);
         }
@@ -1477,6 +1638,12 @@ static void perf_kmat() {
     perf_kmat_case<double>("N=16384 D=3 Matern52 lower", 1, m52, 16384, 0, 3, 1, 1);
     perf_kmat_case<float>("N=32768 D=4 Matern52 lower", 1, m52, 32768, 0, 4, 1, 1);
     perf_kmat_case<float>("N=16384x2048 D=8 EQ (K_x*)", 1, eq, 16384, 2048, 8, 1, 0);
+    // the rational quadratic next to Matern-5/2 (closest instruction mix: one transcendental more than EQ)
+    const int rq[1] = {GPK_K_RQ};
+    const double rqa[1] = {1.5};
+    perf_kmat_case<double>("N=16384 D=8 RQ lower", 1, rq, 16384, 0, 8, 1, 1, 0, rqa);
+    perf_kmat_case<float>("N=16384 D=8 RQ lower", 1, rq, 16384, 0, 8, 1, 1, 0, rqa);
+    perf_kmat_case<float>("N=16384 D=8 Matern52 lower", 1, m52, 16384, 0, 8, 1, 1);
 }
 
 // one problem, for rocprofv3: kmat + potrf (+ trsv, merge, trsm) at order n
@@ -2168,6 +2335,11 @@ int main(int argc, char** argv) {
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
+        if (!strcmp(argv[i], "--rq")) {                        // only the checks of the kind with a shape parameter (rational quadratic)
+            test_rq<double>(); test_rq<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
         if (!strcmp(argv[i], "--potrf")) {                     // only the factorisation checks (plain + look-ahead)
             test_potrf<double>(); test_potrf<float>();
             test_lookahead<double>(); test_lookahead<float>();
@@ -2238,6 +2410,7 @@ int main(int argc, char** argv) {
         test_potrf_rhs<double>(); test_potrf_rhs<float>();
         test_misc<double>(); test_misc<float>();
         test_vjp_dense<double>(); test_vjp_dense<float>();
+        test_rq<double>(); test_rq<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

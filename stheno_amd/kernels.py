@@ -1,9 +1,10 @@
 """Kernels and means on the GP hot path -- the slice of the reference's ``mlkernels``
 dependency that ``stheno/model/*.py`` uses:
 
-* primitives ``EQ``, ``Exp``/``Matern12``, ``Matern32``, ``Matern52``, ``Linear``,
-  ``OneKernel``, ``ZeroKernel`` with the ``v * k``, ``k1 + k2``, ``k.stretch(l)`` algebra
-  (usage: ``readme_example13_optimisation_torch.py:34``, ``tests/model/test_cases.py:138``);
+* primitives ``EQ``, ``RQ``, ``Exp``/``Matern12``, ``Matern32``, ``Matern52``, ``Linear``,
+  ``OneKernel``, ``ZeroKernel`` with the ``v * k``, ``k1 + k2``, ``k.stretch(l)``, ``k.periodic(p)`` algebra
+  (usage: ``readme_example13_optimisation_torch.py:34``, ``tests/model/test_cases.py:138``,
+  ``readme_example1_simple_regression.py``);
 * ``pairwise`` (``k(x, y)``) and ``elwise`` (``k.elwise(x)``) evaluation -- one fused HIP
   kernel launch per call for any sum of primitives (``gpk_kmat`` / ``gpk_kdiag``);
 * ``PosteriorKernel``, ``PosteriorMean``, ``SubspaceKernel`` (constructed at
@@ -21,7 +22,7 @@ from . import ops
 from .matrix import Dense, KernelDense
 
 __all__ = [
-    "Kernel", "EQ", "Exp", "Matern12", "Matern32", "Matern52", "Linear", "OneKernel", "ZeroKernel",
+    "Kernel", "EQ", "RQ", "Periodic", "Exp", "Matern12", "Matern32", "Matern52", "Linear", "OneKernel", "ZeroKernel",
     "Mean", "ZeroMean", "OneMean", "PosteriorKernel", "PosteriorMean", "SubspaceKernel",
     "mean_var", "mean_var_diag", "uprank", "num_elements",
     "MultiInput", "MultiOutputKernel", "MultiOutputMean", "InputScaled",
@@ -131,7 +132,8 @@ def _as_param(v):
 class Kernel:
     """Base class.  A kernel that is a sum of stretched/scaled primitives exposes it as
     ``terms()`` -> list of ``(kind, variance, scale)``; other kernels override
-    ``pairwise`` / ``elwise``."""
+    ``pairwise`` / ``elwise``.  Shape parameters (``RQ``'s alpha) travel beside the terms: ``shapes()`` has one entry per term,
+    ``None`` for the kinds without one."""
 
     stationary = False
 
@@ -143,21 +145,33 @@ class Kernel:
         tensors (so gradients can flow back to them)."""
         return self.terms()
 
+    def shapes(self):
+        """One shape parameter per entry of ``terms()`` (a float; ``None`` for kinds without one), or None like ``terms()``."""
+        t = self.terms()
+        return None if t is None else [None] * len(t)
+
+    def tensor_shapes(self):
+        """Like ``shapes()``, beside ``tensor_terms()``: a tensor the user gave stays that tensor."""
+        t = self.tensor_terms()
+        return None if t is None else [None] * len(t)
+
     def num_outputs(self, x):
         return num_elements(x)
 
     def input_scaled_view(self):
-        """``(k, scales)`` such that ``self(x, y) == k(x / scales, y / scales)`` with ``k`` a sum of primitives
-        (``k.terms()`` is not None) and ``scales`` a vector of per-dimension length scales, or None for "inputs as they
-        are"; None when the kernel has no such form.  The differentiable paths run ``k`` on the divided inputs and
-        leave the division to torch, which carries the gradient to the length scales (and to ``x``)."""
+        """``(k, imap)`` such that ``self(x, y) == k(imap(x), imap(y))`` with ``k`` a sum of primitives
+        (``k.terms()`` is not None) and ``imap`` a differentiable map of the inputs (:class:`InputMap`: the division by
+        per-dimension length scales of ``k.stretch(vector)``, the ``(sin, cos)`` embedding of ``k.periodic(p)``), or None for
+        "inputs as they are"; None when the kernel has no such form.  The differentiable paths run ``k`` on the mapped inputs and
+        leave the map to torch, which carries the gradient to its parameters (length scales, period) and to ``x``."""
         return (self, None) if self.terms() is not None else None
 
     # -- evaluation ------------------------------------------------------------
-    def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None, out=None):
+    def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None, out=None, accumulate=False):
         """``k(x, y)`` as a tensor (..., N, M); ``y is None``: symmetric case, where
         ``diag_add`` / ``diag_vec`` are added to the diagonal in the same pass.  ``out``: a
-        (strided) matrix view to write into (blocks of a multi-output kernel matrix)."""
+        (strided) matrix view to write into (blocks of a multi-output kernel matrix); ``accumulate``: add to it
+        (the groups of a sum whose terms see differently mapped inputs)."""
         t = self.terms()
         if t is None:
             raise NotImplementedError(f"pairwise evaluation is not implemented for {type(self).__name__}")
@@ -165,7 +179,10 @@ class Kernel:
         y = None if y is None else uprank(y)
         if isinstance(x, MultiInput) or isinstance(y, MultiInput):
             raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
-        return ops.get_backend().kmat(ops.KTerms(t), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out)
+        if accumulate:
+            return ops.get_backend().kmat(ops.KTerms(t, self.shapes()), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out,
+                                          accumulate=True)
+        return ops.get_backend().kmat(ops.KTerms(t, self.shapes()), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out)
 
     def elwise(self, x, y=None, *, cache=None):
         """``k(x_i, x_i)`` as a column (..., N, 1)."""
@@ -174,7 +191,7 @@ class Kernel:
         t = self.terms()
         if t is None:
             raise NotImplementedError(f"elwise evaluation is not implemented for {type(self).__name__}")
-        return ops.get_backend().kdiag(ops.KTerms(t), uprank(x))[..., None]
+        return ops.get_backend().kdiag(ops.KTerms(t, self.shapes()), uprank(x))[..., None]
 
     def __call__(self, x, y=None):
         """``k(x)`` / ``k(x, y)`` as a ``Dense`` matrix (lazily materialised for ``k(x)``)."""
@@ -214,9 +231,14 @@ class Kernel:
             return InputScaled(self, scale)
         return Stretched(self, _as_param(scale))
 
+    def periodic(self, period):
+        """``k.periodic(p)``: ``k`` on ``(sin(2 pi x / p), cos(2 pi x / p))`` (mlkernels' ``Periodic``).  ``p``: a positive scalar,
+        or one period per input dimension."""
+        return Periodic(self, period)
+
     def __reversed__(self):
-        # sums of (stretched / scaled) primitives are symmetric, the zero kernel included
-        return self if self.terms() is not None else Reversed(self)
+        # sums of (stretched / scaled) primitives are symmetric, the zero kernel included -- and so are they behind input maps
+        return self if (self.terms() is not None or _map_groups(self) is not None) else Reversed(self)
 
     def __eq__(self, other):
         if isinstance(self, ZeroKernel) and isinstance(other, ZeroKernel):
@@ -241,6 +263,32 @@ class EQ(_Primitive):
     """Exponentiated quadratic ``exp(-r^2 / 2)``."""
     kind = "eq"
     stationary = True
+
+
+class RQ(_Primitive):
+    """Rational quadratic ``(1 + r^2 / (2 alpha))^(-alpha)`` (mlkernels' ``RQ(alpha)``).  ``alpha``: a positive number, or a
+    scalar tensor -- kept as the caller's object (a learnable shape parameter, like a length scale)."""
+    kind = "rq"
+    stationary = True
+
+    def __init__(self, alpha):
+        if torch.is_tensor(alpha):
+            if alpha.numel() != 1:
+                raise ValueError("kernel hyper-parameters must be scalars")
+            self.alpha = alpha if alpha.dim() == 0 else alpha.reshape(())
+        else:
+            self.alpha = float(alpha)
+        if not _as_float(self.alpha) > 0:
+            raise ValueError("the shape parameter alpha of RQ must be positive")
+
+    def shapes(self):
+        return [_as_float(self.alpha)]
+
+    def tensor_shapes(self):
+        return [self.alpha]
+
+    def __repr__(self):
+        return f"RQ({_as_float(self.alpha):g})"
 
 
 class Matern12(_Primitive):
@@ -315,6 +363,12 @@ class Scaled(Kernel):
         t = self.k.tensor_terms()
         return None if t is None else [(kind, var * self.v, s) for kind, var, s in t]
 
+    def shapes(self):
+        return self.k.shapes()
+
+    def tensor_shapes(self):
+        return self.k.tensor_shapes()
+
     def input_scaled_view(self):
         v = self.k.input_scaled_view()
         return None if v is None else (Scaled(v[0], self.v), v[1])
@@ -324,7 +378,7 @@ class Scaled(Kernel):
             return super().pairwise(x, y, **kw)
         view = self.input_scaled_view()
         if view is not None:                       # v * k0(x / l): still ONE fused launch, on the divided inputs
-            return InputScaled(*view).pairwise(x, y, **kw)
+            return _Mapped(*view).pairwise(x, y, **kw)
         da, dv = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
         out = _as_float(self.v) * self.k.pairwise(x, y, **kw)
         return _add_diag(out, da, dv) if y is None else out
@@ -334,7 +388,7 @@ class Scaled(Kernel):
             return super().elwise(x, y, **kw)
         view = self.input_scaled_view()
         if view is not None:
-            return InputScaled(*view).elwise(x, y, **kw)
+            return _Mapped(*view).elwise(x, y, **kw)
         return _as_float(self.v) * self.k.elwise(x, y, **kw)
 
     def __repr__(self):
@@ -354,11 +408,120 @@ class Stretched(Kernel):
     def tensor_terms(self):
         return [(kind, var, s * self.scale) for kind, var, s in self.k.tensor_terms()]
 
+    def shapes(self):
+        return self.k.shapes()
+
+    def tensor_shapes(self):
+        return self.k.tensor_shapes()
+
     def __repr__(self):
         return f"({self.k!r} > {self.scale})"
 
 
-class InputScaled(Kernel):
+class InputMap:
+    """A differentiable map of the inputs in front of a sum of primitives: ``k(x, y) = k0(imap(x), imap(y))``.  ``imap(x)`` is a
+    torch expression (gradients reach the map's parameter and ``x``), ``imap.values(x)`` the same numbers cut off from the graph
+    (what the fused launch of a plain evaluation sees).  The map costs O(N D); the kernel matrix behind it is the unchanged
+    fused launch, lower-triangle-only / in-place-factorisable like any other."""
+
+    param = None          # the tensor (or host value) the map depends on
+
+    def __call__(self, x):
+        raise NotImplementedError
+
+    def values(self, x):
+        with torch.no_grad():
+            return self(x.detach())
+
+    @property
+    def requires_grad(self):
+        return bool(torch.is_tensor(self.param) and self.param.requires_grad)
+
+    def stamp(self):
+        """Identity + version of the parameter (what a cached comparison of two maps was made for); None: nothing vouches for it."""
+        if not torch.is_tensor(self.param):
+            return (id(self), 0)
+        return _scale_stamp(self.param)
+
+    def same(self, other):
+        """The same map as ``other``?  (Learnable parameters are the same only if they are the same tensor.)"""
+        if type(other) is not type(self):
+            return False
+        a, b = self.param, other.param
+        if a is b:
+            return True
+        if not (torch.is_tensor(a) and torch.is_tensor(b)):
+            if torch.is_tensor(a) or torch.is_tensor(b):
+                return False
+            return bool(np.array_equal(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)))
+        return bool(a.shape == b.shape and not a.requires_grad and not b.requires_grad
+                    and (a.data_ptr() == b.data_ptr() and a.device == b.device and a.dtype == b.dtype
+                         or bool(torch.equal(a, b.to(a)))))
+
+
+class _ScaleMap(InputMap):
+    """``x / scales``: one length scale per input dimension."""
+
+    def __init__(self, scales):
+        self.param = scales
+
+    def __call__(self, x):
+        if x.shape[-1] != self.param.numel():
+            raise ValueError(f"inputs have {x.shape[-1]} dimensions, the kernel has {self.param.numel()} length scales")
+        return x / self.param.to(dtype=x.dtype, device=x.device)
+
+
+class _PeriodMap(InputMap):
+    """``x -> cat(sin(2 pi x / p), cos(2 pi x / p))``: squared distances become ``4 sum_d sin^2(pi (x_d - y_d) / p_d)``."""
+
+    def __init__(self, period):
+        self.param = period
+
+    def __call__(self, x):
+        p = self.param
+        p = p.to(dtype=x.dtype, device=x.device) if torch.is_tensor(p) else torch.as_tensor(p, dtype=x.dtype, device=x.device)
+        if p.numel() > 1:
+            p = p.reshape(-1)
+            if p.numel() != x.shape[-1]:
+                raise ValueError(f"inputs have {x.shape[-1]} dimensions, the kernel has {p.numel()} periods")
+        a = (2.0 * np.pi) * x / p
+        return torch.cat([torch.sin(a), torch.cos(a)], dim=-1)
+
+
+class _Mapped(Kernel):
+    """``k0(imap(x), imap(y))`` for a sum of primitives ``k0`` (or anything whose ``pairwise`` takes mapped inputs)."""
+
+    def __init__(self, k, imap):
+        self.k, self.imap = k, imap
+        self.stationary = k.stationary
+
+    def _mapped(self, x):
+        x = uprank(x)
+        if isinstance(x, MultiInput):
+            raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
+        # (values only: the differentiable log-density / bound take the kernel apart through `input_scaled_view`
+        # and map the inputs themselves; everything that is not covered there refuses loudly at its own entry)
+        return x.detach() if self.imap is None else self.imap.values(x)
+
+    def input_scaled_view(self):
+        return (self.k, self.imap)
+
+    def num_outputs(self, x):
+        return self.k.num_outputs(x)
+
+    def pairwise(self, x, y=None, **kw):
+        return self.k.pairwise(self._mapped(x), None if y is None else self._mapped(y), **kw)
+
+    def elwise(self, x, y=None, **kw):
+        if y is not None and y is not x:
+            raise NotImplementedError("elwise is implemented for identical inputs")
+        return self.k.elwise(self._mapped(x), **kw)
+
+    def __reversed__(self):
+        return self                      # k(m(x), m(y)) of a symmetric k is symmetric
+
+
+class InputScaled(_Mapped):
     """``k.stretch(l)`` with one length scale per input dimension (mlkernels' ``Stretched`` with a vector:
     ``k(x / l, y / l)``).  The inputs are divided once -- O(N D) -- and the inner kernel (a sum of primitives) runs
     its fused kernel-matrix launch on them, lower-triangle-only / in-place-factorisable like any other; sums of
@@ -376,66 +539,111 @@ class InputScaled(Kernel):
         if not bool((scales > 0).all()):
             raise ValueError("length scales must be positive")
         self.k, self.scales = k, scales
+        self.imap = _ScaleMap(scales)
         self.stationary = k.stationary
-
-    def _scaled(self, x):
-        x = uprank(x)
-        if isinstance(x, MultiInput):
-            raise ValueError("InputScaled is a single-output kernel; it cannot take multi-process inputs")
-        if x.shape[-1] != self.scales.numel():
-            raise ValueError(f"inputs have {x.shape[-1]} dimensions, the kernel has {self.scales.numel()} length scales")
-        # (values only: the differentiable log-density / bound take the kernel apart through `input_scaled_view`
-        # and divide the inputs themselves; everything that is not covered there refuses loudly at its own entry)
-        return x.detach() / self.scales.detach().to(dtype=x.dtype, device=x.device)
-
-    def input_scaled_view(self):
-        return (self.k, self.scales)
-
-    def num_outputs(self, x):
-        return self.k.num_outputs(x)
-
-    def pairwise(self, x, y=None, **kw):
-        return self.k.pairwise(self._scaled(x), None if y is None else self._scaled(y), **kw)
-
-    def elwise(self, x, y=None, **kw):
-        if y is not None and y is not x:
-            raise NotImplementedError("elwise is implemented for identical inputs")
-        return self.k.elwise(self._scaled(x), **kw)
 
     def stretch(self, scale):
         if _is_vector_scale(scale):
             return InputScaled(self.k, self.scales * (scale if torch.is_tensor(scale) else torch.as_tensor(scale)).to(self.scales))
         return InputScaled(self.k, self.scales * _as_float(scale))
 
-    def __reversed__(self):
-        return self                      # k(x / l, y / l) of a symmetric k is symmetric
-
     def __repr__(self):
         return f"({self.k!r} > {self.scales.tolist()})"
 
 
-def _merge_terms(terms):
-    """Add up the variances of terms with the same primitive and the same length scale (``p + p``
-    has the kernel ``4 k``, not four terms; the fused kernels take at most 8 distinct terms)."""
-    out = []
-    for kind, var, scale in terms:
+class Periodic(_Mapped):
+    """``k.periodic(p)`` (mlkernels' ``Periodic``): ``k`` evaluated on ``(sin(2 pi x / p), cos(2 pi x / p))`` -- for ``EQ`` that is
+    ``exp(-2 sum_d sin^2(pi (x_d - y_d) / p_d))``.  ``p``: a positive scalar or one period per input dimension, a number or a tensor
+    (kept as given: a learnable period).  The inputs are mapped once -- O(N D), twice the dimension behind the map -- and the inner
+    kernel, a sum of primitives, runs its fused kernel-matrix launch on them, exactly as ``InputScaled`` does behind its division."""
+
+    def __init__(self, k, period):
+        if k.terms() is None:
+            raise NotImplementedError("periodic is implemented for sums of primitive kernels")
+        if torch.is_tensor(period):
+            if period.dim() > 1:
+                raise ValueError("a period is a scalar or a vector (one entry per input dimension)")
+            ok = bool((period.detach() > 0).all())
+        else:
+            period = tuple(float(v) for v in period) if isinstance(period, (list, tuple)) or np.ndim(period) > 0 else float(period)
+            ok = bool(np.all(np.asarray(period) > 0))
+        if not ok:
+            raise ValueError("periods must be positive")
+        self.k, self.period = k, period
+        self.imap = _PeriodMap(period)
+        self.stationary = k.stationary
+
+    def stretch(self, scale):
+        return Periodic(self.k.stretch(scale), self.period)      # (mlkernels: the stretch goes to the kernel behind the map)
+
+    def __repr__(self):
+        return f"({self.k!r} per {self.period})"
+
+
+def _same_param(a, b):
+    return (a is b) if (torch.is_tensor(a) or torch.is_tensor(b)) else (a == b)
+
+
+def _merge(terms, shapes):
+    """Add up the variances of terms with the same primitive, the same length scale and the same shape parameter (``p + p``
+    has the kernel ``4 k``, not four terms; the fused kernels take at most 8 distinct terms).  Returns ``(terms, shapes)``."""
+    out, osh = [], []
+    for (kind, var, scale), shp in zip(terms, shapes):
         for i, (k2, v2, s2) in enumerate(out):
-            same = (scale is s2) if (torch.is_tensor(scale) or torch.is_tensor(s2)) else (scale == s2)
-            if k2 == kind and same:
+            if k2 == kind and _same_param(scale, s2) and _same_param(shp, osh[i]):
                 out[i] = (k2, v2 + var, s2)
                 break
         else:
             out.append((kind, var, scale))
-    return out
+            osh.append(shp)
+    return out, osh
+
+
+def _merge_terms(terms):
+    """``_merge`` for terms without shape parameters."""
+    terms = list(terms)
+    return _merge(terms, [None] * len(terms))[0]
 
 
 def _scale_stamp(t):
-    """Identity + version of a length-scale vector (``None`` scale: a constant stamp; a tensor nothing vouches for: ``None``)."""
+    """Identity + version of the parameter of an input map -- a length-scale vector, a period (``None``: no map, a constant stamp;
+    a tensor nothing vouches for: ``None``)."""
     if t is None:
         return (0, 0)
+    if isinstance(t, InputMap):
+        return t.stamp()
     if not torch.is_tensor(t) or t.is_inference() or not t.is_cuda:
         return None
     return (id(t), t._version)
+
+
+def _same_map(a, b):
+    return (a is b) or (a is not None and b is not None and a.same(b))
+
+
+def _map_groups(k):
+    """A kernel as groups of terms that see the same inputs: ``[(k_g, imap_g)]`` with ``k(x, y) = sum_g k_g(imap_g(x), imap_g(y))``,
+    every ``k_g`` a sum of primitives; None when the kernel has no such form.  One group: ``input_scaled_view()``."""
+    v = k.input_scaled_view()
+    if v is not None:
+        return [v]
+    if isinstance(k, Sum):
+        ga, gb = _map_groups(k.a), _map_groups(k.b)
+        if ga is None or gb is None:
+            return None
+        out = list(ga)
+        for kern, m in gb:
+            for i, (k2, m2) in enumerate(out):
+                if _same_map(m, m2):
+                    out[i] = (Sum(k2, kern), m2)
+                    break
+            else:
+                out.append((kern, m))
+        return out
+    if isinstance(k, Scaled):
+        g = _map_groups(k.k)
+        return None if g is None else [(Scaled(kern, k.v), m) for kern, m in g]
+    return None
 
 
 class Sum(Kernel):
@@ -452,13 +660,25 @@ class Sum(Kernel):
         ta, tb = self.a.terms(), self.b.terms()
         if ta is None or tb is None:
             return None
-        return _merge_terms(ta + tb)
+        return _merge(ta + tb, self.a.shapes() + self.b.shapes())[0]
 
     def tensor_terms(self):
         ta, tb = self.a.tensor_terms(), self.b.tensor_terms()
         if ta is None or tb is None:
             return None
-        return _merge_terms(ta + tb)
+        return _merge(ta + tb, self.a.tensor_shapes() + self.b.tensor_shapes())[0]
+
+    def shapes(self):
+        ta, tb = self.a.terms(), self.b.terms()
+        if ta is None or tb is None:
+            return None
+        return _merge(ta + tb, self.a.shapes() + self.b.shapes())[1]
+
+    def tensor_shapes(self):
+        ta, tb = self.a.tensor_terms(), self.b.tensor_terms()
+        if ta is None or tb is None:
+            return None
+        return _merge(ta + tb, self.a.tensor_shapes() + self.b.tensor_shapes())[1]
 
     def input_scaled_view(self):
         # asked several times per FDD / log-density: the comparison of the two length-scale vectors (a device-to-host
@@ -476,19 +696,28 @@ class Sum(Kernel):
         va, vb = self.a.input_scaled_view(), self.b.input_scaled_view()
         if va is None or vb is None:
             return None
-        sa, sb = va[1], vb[1]
-        same = (sa is sb) or (sa is not None and sb is not None and sa.shape == sb.shape and not sa.requires_grad
-                              and not sb.requires_grad
-                              and (sa.data_ptr() == sb.data_ptr() and sa.device == sb.device and sa.dtype == sb.dtype
-                                   or bool(torch.equal(sa, sb.to(sa)))))
-        return (Sum(va[0], vb[0]), sa) if same else None      # different length-scale vectors: no common division
+        return (Sum(va[0], vb[0]), va[1]) if _same_map(va[1], vb[1]) else None      # different maps (length-scale vectors, periods): no common one
 
     def pairwise(self, x, y=None, **kw):
         if self.terms() is not None:
             return super().pairwise(x, y, **kw)
         view = self.input_scaled_view()
-        if view is not None:                       # both summands divide the inputs by the same length scales
-            return InputScaled(*view).pairwise(x, y, **kw)
+        if view is not None:                       # both summands see the inputs through the same map
+            return _Mapped(*view).pairwise(x, y, **kw)
+        groups = _map_groups(self)
+        if groups is not None:
+            # terms behind DIFFERENT input maps (per-dimension length scales, periods, none): group by group into ONE buffer -- the
+            # first fused launch writes it (with the diagonal), the others add to it; `lower` / `out` keep their meaning
+            kw.pop("cache", None)
+            out, da, dv = kw.pop("out", None), kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
+            first = not kw.pop("accumulate", False)
+            xr = uprank(x)
+            yr = None if y is None else uprank(y)
+            for kern, m in groups:
+                g = _Mapped(kern, m)
+                out = g.pairwise(xr, yr, out=out, accumulate=not first, diag_add=da if first else 0.0, diag_vec=dv if first else None, **kw)
+                first = False
+            return out
         da, dv = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
         kw.pop("lower", None)
         out = self.a.pairwise(x, y, **kw) + self.b.pairwise(x, y, **kw)
@@ -499,7 +728,7 @@ class Sum(Kernel):
             return super().elwise(x, y, **kw)
         view = self.input_scaled_view()
         if view is not None:
-            return InputScaled(*view).elwise(x, y, **kw)
+            return _Mapped(*view).elwise(x, y, **kw)
         return self.a.elwise(x, y, **kw) + self.b.elwise(x, y, **kw)
 
     def __repr__(self):
@@ -521,6 +750,12 @@ class Reversed(Kernel):
 
     def tensor_terms(self):
         return self.k.tensor_terms()
+
+    def shapes(self):
+        return self.k.shapes()
+
+    def tensor_shapes(self):
+        return self.k.tensor_shapes()
 
     def pairwise(self, x, y=None, **kw):
         if self.terms() is not None or y is None:
@@ -1018,7 +1253,7 @@ def _learnable_marginals(pm, pk, x, cache):
     view = k.input_scaled_view()
     if view is None:
         return None
-    kern, scales = view
+    kern, imap = view
     tt = kern.tensor_terms()
     if not tt:
         return None
@@ -1035,10 +1270,9 @@ def _learnable_marginals(pm, pk, x, cache):
                  or (noise_vec is not None and noise_vec.requires_grad) or (r is not None and r.requires_grad))
     if not learnable:
         return None
-    sc = None if scales is None else scales.to(dtype=z.dtype, device=z.device)
-    zin = z if sc is None else z / sc
-    xin = x if sc is None else x / sc
-    if (zin.requires_grad or xin.requires_grad) and x.shape[-1] > 8:
+    zin = z if imap is None else imap(z)
+    xin = x if imap is None else imap(x)
+    if (zin.requires_grad or xin.requires_grad) and xin.shape[-1] > 8:       # (behind a periodic map: twice the input dimension)
         raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
                                   "are implemented for at most 8 input dimensions")
     xd = x.detach()                  # (the plain path sees values only: the rows path stays open, one whitening serves mean and variance)

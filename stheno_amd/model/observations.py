@@ -225,9 +225,9 @@ class AbstractPseudoObservations(AbstractObservations):
         view = k.input_scaled_view() if hasattr(k, "input_scaled_view") else None
         if view is None or isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
             return autograd.kernel_requires_grad(k) or self.y.requires_grad
-        kern, scales = view
-        return (autograd.elbo_needs_grad(kern.tensor_terms(), noise_x.diag(), z, self.y - measure.means[p_x](x), x)
-                or (scales is not None and scales.requires_grad))
+        kern, imap = view
+        return (autograd.elbo_needs_grad(kern.tensor_terms(), noise_x.diag(), z, self.y - measure.means[p_x](x), x, kern.tensor_shapes())
+                or (imap is not None and imap.requires_grad))
 
     def _differentiable(self, measure):
         from .. import autograd
@@ -242,10 +242,10 @@ class AbstractPseudoObservations(AbstractObservations):
         view = k.input_scaled_view()
         if view is None:
             return None
-        kern, scales = view                       # k(a, b) = kern(a / scales, b / scales)
+        kern, imap = view                         # k(a, b) = kern(imap(a), imap(b))
         tt = kern.tensor_terms()
         y_bar = self.y - measure.means[p_x](x)
-        if not (autograd.elbo_needs_grad(tt, noise_x.diag(), z, y_bar, x) or (scales is not None and scales.requires_grad)):
+        if not (autograd.elbo_needs_grad(tt, noise_x.diag(), z, y_bar, x, kern.tensor_shapes()) or (imap is not None and imap.requires_grad)):
             return None
         if not (measure.kernels[p_x] is k and measure.kernels[p_z, p_x] is k and isinstance(noise_z, Zero)
                 and x.dim() == 2 and z.dim() == 2):
@@ -253,9 +253,8 @@ class AbstractPseudoObservations(AbstractObservations):
                 "gradients of the bound are implemented for noise-free inducing points of the observed "
                 "process itself (one kernel that is a sum of primitives), unbatched"
             )
-        if scales is not None:                    # torch differentiates the division (d/d scales, d/dx, d/dz)
-            sc = scales.to(dtype=x.dtype, device=x.device)
-            x, z = x / sc, z / sc
+        if imap is not None:                      # torch differentiates the map (d/d scales or period, d/dx, d/dz)
+            x, z = imap(x), imap(z)
         if x.requires_grad and x.shape[-1] > 8:
             raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) are "
                                       "implemented for at most 8 input dimensions")

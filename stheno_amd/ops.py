@@ -24,13 +24,19 @@ _KIND_IDS = {
     "matern52": _native.K_MATERN52,
     "linear": _native.K_LINEAR,
     "const": _native.K_CONST,
+    "rq": _native.K_RQ,
 }
+
+#: kinds with a shape parameter (``rq``: alpha of ``(1 + r^2 / (2 alpha))^(-alpha)``)
+_SHAPED = ("rq",)
 
 
 class KTerms:
-    """A kernel as a sum of ``variance * kind(. / scale)`` terms (host-side descriptor)."""
+    """A kernel as a sum of ``variance * kind(. / scale)`` terms (host-side descriptor).  ``shapes``: one entry per term, the shape
+    parameter of the kinds that have one (``"rq"``: alpha > 0) and ``None`` for the others; ``self.shapes`` is ``None`` when no term
+    has one -- the calls into the library are then the ones without shapes."""
 
-    def __init__(self, terms):
+    def __init__(self, terms, shapes=None):
         terms = list(terms)
         if len(terms) > _native.MAX_TERMS:
             raise ValueError(f"at most {_native.MAX_TERMS} kernel terms are supported")
@@ -40,6 +46,18 @@ class KTerms:
                 raise ValueError(f"unknown kernel kind {k!r}")
             if not s > 0:
                 raise ValueError("length scales must be positive")
+        shapes = [None] * len(self.terms) if shapes is None else list(shapes)
+        if len(shapes) != len(self.terms):
+            raise ValueError("one shape entry per term (None for the kinds without a shape parameter)")
+        out = []
+        for (k, _, _), a in zip(self.terms, shapes):
+            if k in _SHAPED:
+                if a is None or not float(a) > 0:
+                    raise ValueError(f"a {k!r} term needs a positive shape parameter (alpha), got {a!r}")
+                out.append(float(a))
+            else:
+                out.append(None)
+        self.shapes = out if any(a is not None for a in out) else None
 
     def __len__(self):
         return len(self.terms)
@@ -50,6 +68,11 @@ class KTerms:
         var = (ctypes.c_double * max(n, 1))(*[v for _, v, _ in self.terms])
         ils = (ctypes.c_double * max(n, 1))(*[1.0 / s for _, _, s in self.terms])
         return kinds, var, ils, n
+
+    def c_shapes(self):
+        """The ``shapes`` host array of the library's ``_s`` entries (0 where a term has none); only called when ``self.shapes``."""
+        n = len(self.terms)
+        return (ctypes.c_double * max(n, 1))(*[0.0 if a is None else a for a in self.shapes])
 
 
 def _dtype_id(t):
@@ -192,11 +215,13 @@ class HipBackend:
         if diag_vec is not None:
             dv = diag_vec.reshape(B, n).contiguous()
         kinds, var, ils, nt = terms.c_arrays()
-        code = self.lib.gpk_kmat(
-            _dtype_id(x3), kinds, var, ils, nt, self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
-            _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
-            self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream(),
-        )
+        tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
+                _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
+                self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
+        if terms.shapes is not None:      # (a term with a shape parameter: the entry that carries them; everything else calls what it always called)
+            self._st(self.lib.gpk_kmat_s(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, *tail), "gpk_kmat_s")
+            return out
+        code = self.lib.gpk_kmat(_dtype_id(x3), kinds, var, ils, nt, *tail)
         self._st(code, "gpk_kmat")
         return out
 
@@ -207,6 +232,10 @@ class HipBackend:
         B, n, d = x3.shape
         out = torch.empty(bshape + (n,), dtype=x.dtype, device=x.device)
         kinds, var, ils, nt = terms.c_arrays()
+        if terms.shapes is not None:
+            self._st(self.lib.gpk_kdiag_s(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, self._ptr(x3), n, _ld(x3), _bs(x3), d,
+                                          self._ptr(out), n, B, self._stream()), "gpk_kdiag_s")
+            return out
         code = self.lib.gpk_kdiag(_dtype_id(x3), kinds, var, ils, nt, self._ptr(x3), n, _ld(x3), _bs(x3), d,
                                   self._ptr(out), n, B, self._stream())
         self._st(code, "gpk_kdiag")
@@ -511,7 +540,8 @@ class HipBackend:
     def kmat_vjp(self, terms, x, kinv, alpha, g):
         """Sums for the hyper-parameter gradient of the log-density (see gpk_kmat_vjp):
         returns ``(S, trace_G, diag_G)`` with ``S[t] = (sum G kappa_t, sum G kappa_t' q)``.
-        ``x`` (n, d), ``kinv`` (n, n; lower triangle read), ``alpha`` (n, C <= 8), ``g``: C floats."""
+        ``x`` (n, d), ``kinv`` (n, n; lower triangle read), ``alpha`` (n, C <= 8), ``g``: C floats.
+        Terms with a shape parameter (``terms.shapes``): ``S`` has a third column, ``sum G d kappa_t / d shape_t`` (``gpk_kmat_vjp_s``)."""
         self._check(x, kinv, alpha)
         n, d = x.shape
         C = alpha.shape[1]
@@ -522,6 +552,15 @@ class HipBackend:
         diag_g = torch.empty((n,), dtype=x.dtype, device=x.device)
         gs = (ctypes.c_double * max(C, 1))(*[float(v) for v in g])
         alpha = alpha.contiguous()
+        if terms.shapes is not None:
+            width = 3 * _native.MAX_TERMS + 1
+            partial = torch.zeros((nb, width), dtype=x.dtype, device=x.device)
+            code = self.lib.gpk_kmat_vjp_s(_dtype_id(x), kinds, ils, terms.c_shapes(), nt, self._ptr(x), n, x.stride(0), d, self._ptr(kinv),
+                                           kinv.stride(0), self._ptr(alpha), C, alpha.stride(0), gs, self._ptr(partial),
+                                           self._ptr(diag_g), self._stream())
+            self._st(code, "gpk_kmat_vjp_s")
+            tot = partial.sum(0)
+            return tot[: 3 * nt].reshape(nt, 3), tot[3 * _native.MAX_TERMS], diag_g
         code = self.lib.gpk_kmat_vjp(_dtype_id(x), kinds, ils, nt, self._ptr(x), n, x.stride(0), d, self._ptr(kinv),
                                      kinv.stride(0), self._ptr(alpha), C, alpha.stride(0), gs, self._ptr(partial),
                                      self._ptr(diag_g), self._stream())
@@ -534,7 +573,8 @@ class HipBackend:
         """Sums over an explicit cotangent ``Geff = g * colscale[None, :] + w[:, None] b[None, :]`` of
         ``K = k(x, y)`` (see gpk_kmat_vjp_dense): returns ``(S, colsum, gradx)`` with
         ``S[t] = (sum Geff kappa_t, sum Geff kappa_t' q)``, ``colsum[j] = sum_i Geff_ij K_ij`` and
-        ``gradx[i] = sum_j Geff_ij dK_ij/dx_i`` (``None`` unless asked for)."""
+        ``gradx[i] = sum_j Geff_ij dK_ij/dx_i`` (``None`` unless asked for).
+        Terms with a shape parameter: ``S`` has a third column, ``sum Geff d kappa_t / d shape_t`` (``gpk_kmat_vjp_dense_s``)."""
         self._check(x, y, g, colscale, w, b)
         n, d = x.shape
         m = y.shape[0]
@@ -543,7 +583,8 @@ class HipBackend:
         rt, nc = ctypes.c_int64(), ctypes.c_int64()
         self._st(self.lib.gpk_kmat_vjp_dense_grid(n, m, ctypes.byref(rt), ctypes.byref(nc)), "gpk_kmat_vjp_dense_grid")
         rt, nc = rt.value, nc.value
-        width = 2 * _native.MAX_TERMS + 1
+        ns = 2 if terms.shapes is None else 3
+        width = ns * _native.MAX_TERMS + 1
         partial = torch.zeros((rt * nc, width), dtype=x.dtype, device=x.device)
         colsum = torch.zeros((rt, m), dtype=x.dtype, device=x.device) if want_colsum else None
         gradx = torch.zeros((nc, n, d), dtype=x.dtype, device=x.device) if want_gradx else None
@@ -552,13 +593,16 @@ class HipBackend:
         cs = colscale.contiguous() if colscale is not None else None
         w = w.contiguous() if w is not None else None
         b = b.contiguous() if b is not None else None
-        code = self.lib.gpk_kmat_vjp_dense(_dtype_id(x), kinds, var, ils, nt, self._ptr(x), n, x.stride(0), self._ptr(y),
-                                           m, y.stride(0), d, self._ptr(g), g.stride(0), self._ptr(cs), self._ptr(w),
-                                           self._ptr(b), self._ptr(partial), self._ptr(colsum), self._ptr(gradx),
-                                           self._stream())
-        self._st(code, "gpk_kmat_vjp_dense")
+        tail = (self._ptr(x), n, x.stride(0), self._ptr(y),
+                m, y.stride(0), d, self._ptr(g), g.stride(0), self._ptr(cs), self._ptr(w),
+                self._ptr(b), self._ptr(partial), self._ptr(colsum), self._ptr(gradx),
+                self._stream())
+        if terms.shapes is not None:
+            self._st(self.lib.gpk_kmat_vjp_dense_s(_dtype_id(x), kinds, var, ils, terms.c_shapes(), nt, *tail), "gpk_kmat_vjp_dense_s")
+        else:
+            self._st(self.lib.gpk_kmat_vjp_dense(_dtype_id(x), kinds, var, ils, nt, *tail), "gpk_kmat_vjp_dense")
         tot = partial.sum(0)
-        return (tot[: 2 * nt].reshape(nt, 2), colsum.sum(0) if want_colsum else None,
+        return (tot[: ns * nt].reshape(nt, ns), colsum.sum(0) if want_colsum else None,
                 gradx.sum(0) if want_gradx else None)
 
     # -- in-place odds and ends ------------------------------------------------

@@ -257,14 +257,14 @@ class Normal(RandomVector):
                 noise_vec, noise_mat = None, var.noise.mat       # a dense noise covariance: its cotangent is that of K
             if noise_vec is not None and noise_vec is not NotImplemented and noise_vec.dim() != r.dim() - 1:
                 noise_vec = NotImplemented
-            # k(x) = k0(x / l) with k0 a sum of primitives (l: per-dimension length scales, or none): the fused path runs
-            # k0 on the divided inputs; torch differentiates the division (d/dl, d/dx)
+            # k(x) = k0(m(x)) with k0 a sum of primitives (m: the division by per-dimension length scales, the periodic embedding, or
+            # none): the fused path runs k0 on the mapped inputs; torch differentiates the map (d/dl, d/dperiod, d/dx)
             view = var.kernel.input_scaled_view() if torch.is_tensor(var.x) else None
             if noise_vec is not NotImplemented and view is not None:
-                kern, scales = view
-                xin = var.x if scales is None else var.x / scales.to(dtype=var.x.dtype, device=var.x.device)
+                kern, imap = view
+                xin = var.x if imap is None else imap(var.x)
                 tt = kern.tensor_terms()
-                if tt is not None and _ag.needs_grad(tt, noise_vec, r, xin, noise_mat):
+                if tt is not None and _ag.needs_grad(tt, noise_vec, r, xin, noise_mat, kern.tensor_shapes()):
                     if xin.requires_grad and torch.is_grad_enabled() and xin.shape[-1] > 8:
                         raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
                                                   "are implemented for at most 8 input dimensions")
