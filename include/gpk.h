@@ -40,7 +40,7 @@ extern "C" {
 #define GPK_OK 0
 #define GPK_ERR_LAUNCH (-100)
 
-/* kernel term kinds; one term = variance * kappa(dist(x, y) * inv_ls)   (GPK_K_RQ: kappa also takes a shape parameter) */
+/* kernel term kinds; one term = variance * kappa(dist(x, y) * inv_ls)   (GPK_K_RQ, GPK_K_DELTA: kappa also takes a shape parameter) */
 #define GPK_K_EQ 0        /* exp(-r^2/2)                        mlkernels.EQ        */
 #define GPK_K_MATERN12 1  /* exp(-r)                            mlkernels.Exp       */
 #define GPK_K_MATERN32 2  /* (1+sqrt3 r) exp(-sqrt3 r)          mlkernels.Matern32  */
@@ -48,6 +48,7 @@ extern "C" {
 #define GPK_K_LINEAR 4    /* <x, y>                             mlkernels.Linear    */
 #define GPK_K_CONST 5     /* 1                                  mlkernels.OneKernel */
 #define GPK_K_RQ 6        /* (1 + r^2/(2 alpha))^(-alpha)       mlkernels.RQ(alpha): one SHAPE parameter, see gpk_kmat_s */
+#define GPK_K_DELTA 7     /* 1 if r^2 < epsilon, else 0         mlkernels.Delta(epsilon): one SHAPE parameter, see gpk_kmat_s */
 #define GPK_MAX_TERMS 8
 
 #define GPK_GEMM_LOWER 1
@@ -90,7 +91,12 @@ int gpk_kmat(int dtype, const int* kinds, const double* variances, const double*
  * `kinds` free of GPK_K_RQ both write the same bits; gpk_kmat with a GPK_K_RQ term returns -1 (no alpha was given), gpk_kmat_s with a
  * non-positive alpha -5.  RQ is evaluated as exp(-alpha log1p(q / (2 alpha))), q = r^2 / scale^2: a single RQ term has a row-band
  * program of its own next to EQ / Matern; within ~2.5 eps (1 + alpha log1p(q / (2 alpha))) of the exactly rounded value
- * (csrc/selftest.cpp, `--rq`).  Replaces mlkernels `pairwise` of `RQ(alpha)` and of sums with it. */
+ * (csrc/selftest.cpp, `--rq`).  Replaces mlkernels `pairwise` of `RQ(alpha)` and of sums with it.
+ * GPK_K_DELTA (version 103): shapes[t] = epsilon > 0; with q = r^2 / scale^2 (direct differences) the value is 1 where q < epsilon and 0
+ * elsewhere -- no transcendental, so coincident points give exactly the variance and every element is exact in both dtypes unless q
+ * lies within rounding of epsilon; NaN inputs give NaN.  Same return codes as RQ's alpha: -1 through gpk_kmat (no epsilon was given),
+ * -5 for a non-positive epsilon.  A Delta term always takes the term-table program of the launches with shapes (csrc/selftest.cpp,
+ * `--delta`).  Replaces mlkernels `pairwise` of `Delta(epsilon)`: the noise process e of `y = f + e`. */
 int gpk_kmat_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
                int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
@@ -102,7 +108,8 @@ int gpk_kmat_s(int dtype, const int* kinds, const double* variances, const doubl
 int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
               const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
               int64_t batch, void* stream);
-/* ... with the shape parameters of gpk_kmat_s (an RQ term contributes its variance on the diagonal, whatever alpha). */
+/* ... with the shape parameters of gpk_kmat_s (an RQ or Delta term contributes its variance on the diagonal, whatever its shape; a
+ * Delta term through gpk_kdiag returns -1, a non-positive epsilon -5). */
 int gpk_kdiag_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                 const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
                 int64_t batch, void* stream);
@@ -363,7 +370,9 @@ int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, int nterms, 
  * shape), and a row layout of its own --
  *   partial[b][3t] = S1_t,  partial[b][3t+1] = S2_t,  partial[b][3t+2] = S3_t,  partial[b][3*GPK_MAX_TERMS] = trace(G)
  *   (row stride 3*GPK_MAX_TERMS + 1; sum over b).  d logpdf / d alpha_t = v_t S3_t.
- * RQ, with u = q / (2 alpha): kappa' q = -(q / 2) kappa / (1 + u),  d kappa / d alpha = kappa (u / (1 + u) - log1p(u)). */
+ * RQ, with u = q / (2 alpha): kappa' q = -(q / 2) kappa / (1 + u),  d kappa / d alpha = kappa (u / (1 + u) - log1p(u)).
+ * Delta (piecewise constant): S1_t = sum_ij G_ij kappa_t, S2_t = S3_t = 0 -- its variance is learnable, its scale and epsilon are not.
+ * A Delta term through gpk_kmat_vjp returns -1; a non-positive epsilon -5, the code gpk_kmat_s gives it. */
 int gpk_kmat_vjp_s(int dtype, const int* kinds, const double* inv_ls, const double* shapes, int nterms, const void* x, int64_t n,
                    int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
                    const double* g, void* partial, void* diag_g, void* stream);
@@ -385,7 +394,8 @@ int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, con
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream);
 /* ... with shape parameters: partial[wg][3t .. 3t+2] = S1_t, S2_t, S3_t as for gpk_kmat_vjp_s (row stride 3*GPK_MAX_TERMS + 1; the
- * last element of a row is unused), colsum / gradx as above (RQ: dK/dx through kappa' = -kappa / (2 (1 + u))). */
+ * last element of a row is unused), colsum / gradx as above (RQ: dK/dx through kappa' = -kappa / (2 (1 + u)); Delta: S2_t = S3_t = 0,
+ * its kappa_t counts in colsum, nothing in gradx; -1 through gpk_kmat_vjp_dense, -5 for a non-positive epsilon). */
 int gpk_kmat_vjp_dense_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                          const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                          const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,

@@ -16,7 +16,7 @@ _p_dbl = ctypes.POINTER(ctypes.c_double)
 GPK_F32 = 0
 GPK_F64 = 1
 
-K_EQ, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_CONST, K_RQ = range(7)
+K_EQ, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_CONST, K_RQ, K_DELTA = range(8)
 MAX_TERMS = 8
 DIAG_BLOCK = 128
 
@@ -38,7 +38,7 @@ SIGNATURES = {
         [_c_int, _p_int, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64,
          _c_i64, _c_ptr],
     ),
-    # the entries with one shape parameter per term (RQ's alpha): one more host array behind `inv_ls`
+    # the entries with one shape parameter per term (RQ's alpha, Delta's epsilon): one more host array behind `inv_ls`
     "gpk_kmat_s": (
         _c_int,
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,

@@ -25,7 +25,8 @@ __all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals"]
 
 
 # Hyper-parameters travel through the autograd functions as one flat list of scalar tensors: the variances, then the scales and --
-# only when a term has a shape parameter (RQ's alpha) -- one more entry per term behind them (a constant 0 for the kinds without).
+# only when a term has a shape parameter (RQ's alpha, Delta's epsilon) -- one more entry per term behind them (a constant 0 for the
+# kinds without).  Only RQ's is learnable: Delta is piecewise constant in its epsilon, whose gradient entry is None.
 def _as_t(v):
     return v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
 
@@ -35,6 +36,9 @@ def _pack(tt, shapes):
     kinds = tuple(k for k, _, _ in tt)
     params = [_as_t(v) for _, v, _ in tt] + [_as_t(s) for _, _, s in tt]
     if shapes is not None and any(a is not None for a in shapes):
+        for k, a in zip(kinds, shapes):
+            if k not in ops._LEARNABLE_SHAPE and torch.is_tensor(a) and a.requires_grad:
+                raise ValueError(f"the shape parameter of a {k!r} term is not learnable")
         params += [_as_t(0.0 if a is None else a) for a in shapes]
     return kinds, params
 
@@ -57,7 +61,7 @@ def _param_grads(kinds, values, S, meta, wgt=1.0):
     nt = len(kinds)
     gr = [wgt * S[t, 0] for t in range(nt)] + [wgt * -2.0 * variances[t] / scales[t] * S[t, 1] for t in range(nt)]
     if alphas is not None:
-        gr += [(wgt * variances[t] * S[t, 2]) if kinds[t] in ops._SHAPED else None for t in range(nt)]
+        gr += [(wgt * variances[t] * S[t, 2]) if kinds[t] in ops._LEARNABLE_SHAPE else None for t in range(nt)]
     return [None if g_ is None else g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(gr, meta)]
 
 
@@ -434,7 +438,7 @@ class _SparseELBO(torch.autograd.Function):
             grads_v.append(gv * go)
             grads_s.append(gs * go)
         # (shape parameters: through the kernel matrices only -- every stationary kind is 1 on the diagonal, whatever its shape)
-        grads_a = [] if alphas is None else [(variances[t] * S[t, 2] * go) if ctx.kinds[t] in ops._SHAPED else None for t in range(nt)]
+        grads_a = [] if alphas is None else [(variances[t] * S[t, 2] * go) if ctx.kinds[t] in ops._LEARNABLE_SHAPE else None for t in range(nt)]
         grads = [None if g_ is None else g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(grads_v + grads_s + grads_a, ctx.param_meta)]
         grad_z = (gz_k + 2.0 * gz_kz) * go if need_z else None
         grad_x = gx_k * go if need_x else None

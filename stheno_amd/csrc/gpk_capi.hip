@@ -39,7 +39,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 102; }
+int gpk_version(void) { return 103; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 

@@ -16,7 +16,7 @@
 // direct differences (no |a|^2 + |b|^2 - 2ab cancellation).
 #include "gpk_common.hpp"
 
-enum { GPK_K_EQ = 0, GPK_K_MATERN12 = 1, GPK_K_MATERN32 = 2, GPK_K_MATERN52 = 3, GPK_K_LINEAR = 4, GPK_K_CONST = 5, GPK_K_RQ = 6 };
+enum { GPK_K_EQ = 0, GPK_K_MATERN12 = 1, GPK_K_MATERN32 = 2, GPK_K_MATERN52 = 3, GPK_K_LINEAR = 4, GPK_K_CONST = 5, GPK_K_RQ = 6, GPK_K_DELTA = 7 };
 
 GPK_KNOB(int, g_kmat_compact, 1);   // tuning knob (gpk_tune(34, v)): 1-D compact grid for the lower triangle of a square matrix
 GPK_KNOB(int, g_kmat_band, 1);      // tuning knob (gpk_tune(12, v)): 1 = row-band kernel, 0 = the one-tile-per-workgroup kernel
@@ -57,7 +57,7 @@ struct KmatArgs {
     int nbands;       // row-band kernel: number of row bands (TM rows each)
     int compact;      // row-band kernel, lower triangle of one square matrix: a 1-D grid of exactly the (row band, column chunk) pairs on or
                       // below the diagonal -- `compact` = row bands per column chunk; 0 = the plain 2-D grid
-    // shape parameters (GPK_K_RQ: alpha, and 1 / (2 alpha)).  Behind everything else: the programs that have none read the same
+    // shape parameters (GPK_K_RQ: alpha, and 1 / (2 alpha); GPK_K_DELTA: epsilon in `shape`).  Behind everything else: the programs that have none read the same
     // argument offsets as before and compile to the code they compiled to without these two arrays.
     T shape[GPK_MAX_TERMS];
     T hshape[GPK_MAX_TERMS];
@@ -99,8 +99,9 @@ __device__ __forceinline__ double gpk_log1p<double>(double u) { return log1p(u);
 template <>
 __device__ __forceinline__ float gpk_log1p<float>(float u) { return log1pf(u); }
 
-// RQ: the term table may hold rational-quadratic terms (a launch with shape parameters).  A template parameter, not one more branch
-// of the kind switch: the table program of kernels WITHOUT such a term stays the code it was (the logarithm costs ~25 registers).
+// RQ: the term table may hold terms of the kinds with a shape parameter -- rational quadratic, Delta -- (a launch with shape
+// parameters).  A template parameter, not one more branch of the kind switch: the table program of kernels WITHOUT such a term stays
+// the code it was (the logarithm costs ~25 registers).
 template <typename T, bool RQ>
 __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
     T val = T(0);
@@ -123,6 +124,10 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
         } else if (RQ && kind == GPK_K_RQ) {
             // (1 + u)^(-alpha), u = q / (2 alpha), as exp(-alpha log1p(u)): the exponent is <= 0 like every other on this path
             k = gpk_exp<T>(-p.shape[t] * gpk_log1p<T>(q * p.hshape[t]));
+        } else if (RQ && kind == GPK_K_DELTA) {
+            // 1 within epsilon (in q: the scaled squared distance), else 0 -- no transcendental; q is a sum of squared direct
+            // differences, so coincident points give exactly 1; NaN inputs stay NaN like every other kind
+            k = q != q ? q : (q < p.shape[t] ? T(1) : T(0));
         } else {
             k = T(1);
         }
@@ -606,7 +611,7 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     a.nterms = nterms;
     a.need_dot = 0;
     for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_RQ) return GPK_ERR_ARG(1);
+        if (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_DELTA) return GPK_ERR_ARG(1);
         a.terms[t].kind = kinds[t];
         a.terms[t].variance = (T)variances[t];
         a.terms[t].ils2 = (T)(inv_ls[t] * inv_ls[t]);
@@ -621,6 +626,12 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
             if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
             a.shape[t] = (T)shapes[t];
             a.hshape[t] = (T)(0.5 / shapes[t]);
+        }
+        if (t < nterms && kinds[t] == GPK_K_DELTA) {
+            has_rq = true;                                         // (the shaped term table: Delta has no program of its own)
+            if (shapes == nullptr) return GPK_ERR_ARG(1);          // a Delta term through an entry that carries no epsilon
+            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
+            a.shape[t] = (T)shapes[t];
         }
     }
     a.diag_add = (T)diag_add;
@@ -714,7 +725,7 @@ int gpk_kdiag_launch(const int* kinds, const double* variances, const double* in
     if (n <= 0 || batch <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
     for (int t = 0; t < nterms; ++t)
-        if (kinds[t] == GPK_K_RQ) {
+        if (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA) {
             if (shapes == nullptr) return GPK_ERR_ARG(1);
             if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
         }

@@ -12,10 +12,11 @@
 //
 // Kinds with a SHAPE parameter (rational quadratic: alpha) go through the `_s` entries: the same kernels instantiated with SH = true,
 // which know VK_RQ and carry a third sum per term, S3_t = sum_ij G_ij d kappa_t / d alpha_t, in partial rows of 3 T + 1 elements.
+// VK_DELTA (1 where q < epsilon, else 0; epsilon in `shape`) lives there too: piecewise constant, so S2_t = S3_t = 0 and no d/dx.
 // The SH = false instantiations are what the entries without shapes launch: the code they have always been.
 #include "gpk_common.hpp"
 
-enum { VK_EQ = 0, VK_MATERN12 = 1, VK_MATERN32 = 2, VK_MATERN52 = 3, VK_LINEAR = 4, VK_CONST = 5, VK_RQ = 6 };
+enum { VK_EQ = 0, VK_MATERN12 = 1, VK_MATERN32 = 2, VK_MATERN52 = 3, VK_LINEAR = 4, VK_CONST = 5, VK_RQ = 6, VK_DELTA = 7 };
 
 namespace {
 
@@ -96,6 +97,12 @@ __device__ __forceinline__ void kappa_rq(T q, T a, T& k, T& dkq, T& dk, T& da) {
     dk = T(-0.5) * k * ri;
     dkq = dk * q;
     da = k * (u * ri - lg);
+}
+
+// Delta: 1 within epsilon (in q), else 0; NaN stays NaN.  Piecewise constant: no derivative in q, x or epsilon.
+template <typename T>
+__device__ __forceinline__ T kappa_delta(T q, T eps) {
+    return q != q ? q : (q < eps ? T(1) : T(0));
 }
 
 template <typename T, bool SH>
@@ -192,6 +199,9 @@ __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
                         T dk, da;
                         kappa_rq<T>(q, p.shape[t], k, dkq, dk, da);
                         s3 += Gw[u][v] * da;
+                    } else if (SH && kind == VK_DELTA) {
+                        k = kappa_delta<T>(q, p.shape[t]);
+                        dkq = T(0);
                     } else {
                         kappa_and_dq<T>(kind, q, k, dkq);
                     }
@@ -384,6 +394,9 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
                             T da;
                             kappa_rq<T>(q, p.shape[t], k, dkq, dk, da);
                             s3[SH ? t : 0] += Ge[u][v] * da;
+                        } else if (SH && kind == VK_DELTA) {
+                            k = kappa_delta<T>(q, p.shape[t]);
+                            dkq = dk = T(0);
                         } else {
                             kappa_all<T>(kind, q, k, dkq, dk);
                         }
@@ -490,7 +503,8 @@ void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64
     if (tiles_per_chunk) *tiles_per_chunk = tpc;
 }
 
-// SH = false: kinds without a shape parameter only (an RQ term is refused: no alpha was given); SH = true: `shapes` is read for RQ terms
+// SH = false: kinds without a shape parameter only (an RQ or Delta term is refused: no alpha / epsilon was given); SH = true: `shapes` is
+// read for RQ and Delta terms
 template <typename T, bool SH>
 static int vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                             const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
@@ -499,9 +513,10 @@ static int vjp_dense_launch(const int* kinds, const double* variances, const dou
     if (n <= 0 || m <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(5);
     for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < VK_EQ || kinds[t] > VK_RQ) return GPK_ERR_ARG(1);
-        if (kinds[t] == VK_RQ && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
+        if (kinds[t] < VK_EQ || kinds[t] > VK_DELTA) return GPK_ERR_ARG(1);
+        if ((kinds[t] == VK_RQ || kinds[t] == VK_DELTA) && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
         if (kinds[t] == VK_RQ && !(shapes[t] > 0)) return GPK_ERR_ARG(4);
+        if (kinds[t] == VK_DELTA && !(shapes[t] > 0)) return GPK_ERR_ARG(5);
     }
     if (n > INT32_MAX || m > INT32_MAX) return GPK_ERR_ARG(7);
     if ((w == nullptr) != (b == nullptr)) return GPK_ERR_ARG(17);
@@ -518,7 +533,7 @@ static int vjp_dense_launch(const int* kinds, const double* variances, const dou
         a.kind[t] = t < nterms ? kinds[t] : VK_CONST;
         a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
         a.var[t] = t < nterms ? (T)variances[t] : T(0);
-        a.shape[t] = (SH && t < nterms && kinds[t] == VK_RQ) ? (T)shapes[t] : T(1);
+        a.shape[t] = (SH && t < nterms && (kinds[t] == VK_RQ || kinds[t] == VK_DELTA)) ? (T)shapes[t] : T(1);
     }
     if (nc > 65535) return GPK_ERR_ARG(9);
     hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, SH>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
@@ -573,9 +588,10 @@ static int vjp_launch(const int* kinds, const double* inv_ls, const double* shap
     if (n <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(3);
     for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < VK_EQ || kinds[t] > VK_RQ) return GPK_ERR_ARG(1);
-        if (kinds[t] == VK_RQ && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
+        if (kinds[t] < VK_EQ || kinds[t] > VK_DELTA) return GPK_ERR_ARG(1);
+        if ((kinds[t] == VK_RQ || kinds[t] == VK_DELTA) && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
         if (kinds[t] == VK_RQ && !(shapes[t] > 0)) return GPK_ERR_ARG(3);
+        if (kinds[t] == VK_DELTA && !(shapes[t] > 0)) return GPK_ERR_ARG(5);       // (the code gpk_kmat_s gives a bad epsilon)
     }
     if (C < 1 || C > VMAXC) return GPK_ERR_ARG(11);
     if (n > INT32_MAX) return GPK_ERR_ARG(5);
@@ -593,7 +609,7 @@ static int vjp_launch(const int* kinds, const double* inv_ls, const double* shap
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
         a.kind[t] = t < nterms ? kinds[t] : VK_CONST;
         a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
-        a.shape[t] = (SH && t < nterms && kinds[t] == VK_RQ) ? (T)shapes[t] : T(1);
+        a.shape[t] = (SH && t < nterms && (kinds[t] == VK_RQ || kinds[t] == VK_DELTA)) ? (T)shapes[t] : T(1);
     }
     const int64_t nb = gpk_kmat_vjp_blocks_impl(n);
     hipLaunchKernelGGL((kmat_vjp_kernel<T, SH>), dim3((unsigned)nb), dim3(256), 0, stream, a);

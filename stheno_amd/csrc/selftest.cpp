@@ -4,6 +4,7 @@
 //     ./gpk_selftest            correctness of every entry point vs host loops
 //     ./gpk_selftest --perf     + timings (HIP events) of the hot kernels
 //     ./gpk_selftest --rq       only the checks of the term kind with a shape parameter (rational quadratic)
+//     ./gpk_selftest --delta    only the checks of the Delta term kind
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -1201,6 +1202,167 @@ static void test_rq() {
 }
 
 // ----------------------------------------------------------------------------
+// Delta: 1 where the scaled squared distance is below epsilon, else 0 (gpk_kmat_s / gpk_kdiag_s and the `_s` VJP entries)   --delta
+// ----------------------------------------------------------------------------
+// Inputs are small integers over 4 with rows of y copied from x: every squared distance is 0 or at least 1/16, computed without
+// rounding in both dtypes, so the host evaluates the kernel EXACTLY and every element has to match bit for bit -- Delta alone, beside
+// a constant term, lower-only (nothing above the diagonal tiles is written), accumulated into a filled buffer, through both kernels.
+template <typename T>
+static std::vector<T> quarters(size_t n, int span) {
+    std::vector<T> v(n);
+    for (auto& x : v) x = (T)((int)(rng() % (2 * span + 1)) - span) / (T)4;
+    return v;
+}
+template <typename T>
+static void test_delta() {
+    const double eps = 1e-6;
+    for (int band = 1; band >= 0; --band) {
+        gpk_tune(12, band);
+        const char* kn = band ? "row-band" : "tile";
+        for (int d : {1, 3, 8, 9}) {                       // (d = 9: past one staged chunk -- the tile kernel whatever the knob says)
+            const int n = 130, m = 259;
+            auto X = quarters<T>((size_t)n * d, d == 1 ? 40 : 2), Y = quarters<T>((size_t)m * d, d == 1 ? 40 : 2);
+            for (int j = 0; j < m; j += 3) for (int k = 0; k < d; ++k) Y[(size_t)j * d + k] = X[(size_t)((j * 7) % n) * d + k];
+            Dev<T> dX(X.size()), dY(Y.size()), dO((size_t)n * m);
+            dX.up(X); dY.up(Y);
+            int kinds[2] = {GPK_K_DELTA, GPK_K_CONST};
+            double var[2] = {1.5, 0.25}, sh[2] = {eps, 0.0};
+            for (double il : {1.0, 0.5}) {                 // (power-of-two scales keep q exact: 0 or >= 1/64)
+                double ils[2] = {il, 1.0};
+                for (int nt = 1; nt <= 2; ++nt) {
+                    for (int acc = 0; acc < 2; ++acc) {
+                        std::vector<T> base((size_t)n * m);
+                        for (size_t e = 0; e < base.size(); ++e) base[e] = (T)((int)(e % 7) - 3);
+                        dO.up(base);
+                        int st = gpk_kmat_s(DT<T>::v, kinds, var, ils, sh, nt, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, acc, nullptr);
+                        HIPCHK(hipDeviceSynchronize());
+                        auto got = dO.down();
+                        size_t bad = 0, ones = 0;
+                        for (int i = 0; i < n; ++i)
+                            for (int j = 0; j < m; ++j) {
+                                bool same = true;
+                                for (int k = 0; k < d; ++k) same = same && X[(size_t)i * d + k] == Y[(size_t)j * d + k];
+                                const T want = (T)((acc ? base[(size_t)i * m + j] : T(0)) + (T)(same ? 1.5 : 0.0) + (T)(nt == 2 ? 0.25 : 0.0));
+                                ones += same;
+                                bad += got[(size_t)i * m + j] != want;
+                            }
+                        char nm[200];
+                        snprintf(nm, sizeof nm, "kmat_%s delta%s %s d%d il=%g%s: mismatching elements (%zu ones) st%d", DT<T>::name(), nt == 2 ? "+const" : "", kn, d, il,
+                                 acc ? " accumulate" : "", ones, st);
+                        report(nm, (st || ones < (size_t)m / 3) ? INFINITY : (double)bad, 0.0);
+                    }
+                }
+            }
+            // symmetric, lower-only, diag_add: tiles above the diagonal keep what was there, the diagonal is variance + diag_add
+            {
+                Dev<T> dS((size_t)n * n);
+                std::vector<T> fill((size_t)n * n, (T)-7);
+                dS.up(fill);
+                for (int i = 100; i < n; ++i) for (int k = 0; k < d; ++k) X[(size_t)i * d + k] = X[(size_t)(i - 100) * d + k];
+                dX.up(X);
+                double one = 1.0;
+                int st = gpk_kmat_s(DT<T>::v, kinds, var, &one, sh, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dS.p, n, 0, 1, 1, 1, 0.5, nullptr, 0, 0, nullptr);
+                HIPCHK(hipDeviceSynchronize());
+                auto got = dS.down();
+                size_t bad = 0;
+                const int TN = 64 * (16 / (int)sizeof(T));
+                for (int i = 0; i < n; ++i)
+                    for (int j = 0; j < n; ++j) {
+                        bool same = true;
+                        for (int k = 0; k < d; ++k) same = same && X[(size_t)i * d + k] == X[(size_t)j * d + k];
+                        const T want = (T)((same ? 1.5 : 0.0) + (i == j ? 0.5 : 0.0));
+                        if (j <= i) bad += got[(size_t)i * n + j] != want;
+                        else if ((j / TN) * TN > (i / 32) * 32 + 31) bad += got[(size_t)i * n + j] != (T)-7;      // a skipped tile
+                    }
+                char nm[200];
+                snprintf(nm, sizeof nm, "kmat_%s delta %s d%d symmetric lower-only + diag_add: mismatching elements st%d", DT<T>::name(), kn, d, st);
+                report(nm, st ? INFINITY : (double)bad, 0.0);
+            }
+        }
+    }
+    gpk_tune(12, 1);
+    {   // a NaN input row gives a NaN row; the two return codes; the diagonal
+        const int n = 33, m = 65, d = 3;
+        auto X = quarters<T>((size_t)n * d, 2), Y = quarters<T>((size_t)m * d, 2);
+        X[5 * d + 1] = std::numeric_limits<T>::quiet_NaN();
+        Dev<T> dX(X.size()), dY(Y.size()), dO((size_t)n * m), dD(n);
+        dX.up(X); dY.up(Y);
+        int kind = GPK_K_DELTA; double var = 1.5, il = 1.0, sh = eps, bad = 0.0;
+        int st = gpk_kmat_s(DT<T>::v, &kind, &var, &il, &sh, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        auto got = dO.down();
+        size_t wrong = 0;
+        for (int i = 0; i < n; ++i) for (int j = 0; j < m; ++j) wrong += (i == 5) != (got[(size_t)i * m + j] != got[(size_t)i * m + j]);
+        report(std::string("kmat_s delta: a NaN input row is a NaN row, no other ") + DT<T>::name(), st ? INFINITY : (double)wrong, 0.0);
+        st = gpk_kmat(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+        report(std::string("kmat refuses a delta term (no epsilon) with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_s(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+        report(std::string("kmat_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kdiag(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        report(std::string("kdiag refuses a delta term with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kdiag_s(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        report(std::string("kdiag_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        int k2[2] = {GPK_K_DELTA, GPK_K_LINEAR}; double v2[2] = {0.75, 1.5}, l2[2] = {1.0, 0.5}, s2[2] = {eps, 0.0};
+        X[5 * d + 1] = (T)0.25;
+        dX.up(X);
+        st = gpk_kdiag_s(DT<T>::v, k2, v2, l2, s2, 2, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        auto dg = dD.down();
+        size_t wd = 0;
+        for (int i = 0; i < n; ++i) { double nr = 0; for (int k = 0; k < d; ++k) nr += (double)X[i * d + k] * X[i * d + k]; wd += (double)dg[i] != 0.75 + 1.5 * 0.25 * nr; }
+        report(std::string("kdiag_s delta + linear: mismatching elements ") + DT<T>::name(), st ? INFINITY : (double)wd, 0.0);
+        // the VJP entries: -1 without shapes, -5 for a bad epsilon
+        Dev<T> dG((size_t)n * m), dP((size_t)64 * (3 * GPK_MAX_TERMS + 1)), dK((size_t)n * n), dA(n), dDg(n);
+        double g1 = 1.0;
+        st = gpk_kmat_vjp_dense(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, nullptr, nullptr, nullptr);
+        report(std::string("vjp_dense refuses a delta term with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_vjp_dense_s(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, nullptr, nullptr, nullptr);
+        report(std::string("vjp_dense_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_vjp(DT<T>::v, &kind, &il, 1, dX.p, n, d, d, dK.p, n, dA.p, 1, 1, &g1, dP.p, dDg.p, nullptr);
+        report(std::string("kmat_vjp refuses a delta term with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_vjp_s(DT<T>::v, &kind, &il, &bad, 1, dX.p, n, d, d, dK.p, n, dA.p, 1, 1, &g1, dP.p, dDg.p, nullptr);
+        report(std::string("kmat_vjp_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+    }
+    {   // explicit-cotangent VJP, Delta beside EQ: S1 = sum Geff kappa, S2 = S3 = 0 exactly, kappa in colsum, nothing in gradx
+        const int n = 130, m = 259, d = 3, nt = 2;
+        int kinds[nt] = {GPK_K_EQ, GPK_K_DELTA};
+        double var[nt] = {0.75, 1.5}, il[nt] = {1.0, 1.0}, sh[nt] = {0.0, eps};
+        auto X = quarters<T>((size_t)n * d, 2), Y = quarters<T>((size_t)m * d, 2), G = randv<T>((size_t)n * m);
+        int64_t rt = 0, nc = 0;
+        gpk_kmat_vjp_dense_grid(n, m, &rt, &nc);
+        const int W = 3 * GPK_MAX_TERMS + 1;
+        Dev<T> dX(X.size()), dY(Y.size()), dG(G.size()), dP((size_t)rt * nc * W), dC((size_t)rt * m), dGX((size_t)nc * n * d);
+        dX.up(X); dY.up(Y); dG.up(G);
+        int st = gpk_kmat_vjp_dense_s(DT<T>::v, kinds, var, il, sh, nt, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, dC.p, dGX.p, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        auto P = dP.down(), C = dC.down(), GX = dGX.down();
+        std::vector<double> rS(2, 0.0), rC(m, 0.0), rGX((size_t)n * d, 0.0);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < m; ++j) {
+                double r2 = 0;
+                for (int k = 0; k < d; ++k) { const double a = X[(size_t)i * d + k], c = Y[(size_t)j * d + k]; r2 += (a - c) * (a - c); }
+                const double ge = G[(size_t)i * m + j], kd = r2 < eps ? 1.0 : 0.0;
+                rS[0] += ge * std::exp(-0.5 * r2); rS[1] += ge * kd;
+                rC[j] += ge * (0.75 * std::exp(-0.5 * r2) + 1.5 * kd);
+                for (int c = 0; c < d; ++c) rGX[(size_t)i * d + c] += ge * 0.75 * -std::exp(-0.5 * r2) * ((double)X[(size_t)i * d + c] - (double)Y[(size_t)j * d + c]);
+            }
+        std::vector<T> gS(2, T(0)), gC(m, T(0)), gGX((size_t)n * d, T(0));
+        for (int64_t c = 0; c < nc; ++c) for (size_t e = 0; e < (size_t)n * d; ++e) gGX[e] += GX[(size_t)c * n * d + e];
+        bool zeros = true;
+        for (int64_t wg = 0; wg < rt * nc; ++wg) {
+            gS[0] += P[(size_t)wg * W]; gS[1] += P[(size_t)wg * W + 3];
+            zeros = zeros && P[(size_t)wg * W + 4] == T(0) && P[(size_t)wg * W + 5] == T(0);
+        }
+        for (int64_t r = 0; r < rt; ++r) for (int j = 0; j < m; ++j) gC[j] += C[(size_t)r * m + j];
+        std::string nm = std::string("vjp_dense_s_") + DT<T>::name() + " eq+delta n130 m259 d3";
+        report(nm + " S1", st ? INFINITY : relerr(gS, rS), DT<T>::eps * 50);
+        report(nm + " S2 = S3 = 0 for the delta term", zeros ? 0.0 : INFINITY, 0.0);
+        report(nm + " colsum", st ? INFINITY : relerr(gC, rC), DT<T>::eps * 50);
+        report(nm + " gradx (the eq term's alone)", st ? INFINITY : relerr(gGX, rGX), DT<T>::eps * 50);
+    }
+}
+
+// ----------------------------------------------------------------------------
 // perf
 // ----------------------------------------------------------------------------
 struct Timer {
@@ -1644,6 +1806,11 @@ static void perf_kmat() {
     perf_kmat_case<double>("N=16384 D=8 RQ lower", 1, rq, 16384, 0, 8, 1, 1, 0, rqa);
     perf_kmat_case<float>("N=16384 D=8 RQ lower", 1, rq, 16384, 0, 8, 1, 1, 0, rqa);
     perf_kmat_case<float>("N=16384 D=8 Matern52 lower", 1, m52, 16384, 0, 8, 1, 1);
+    // noise as a process: EQ + v * Delta takes the term table of the launches with shapes; EQ with diag_add (the cases above) is its rival
+    const int eqd[2] = {GPK_K_EQ, GPK_K_DELTA};
+    const double eqds[2] = {0.0, 1e-6};
+    perf_kmat_case<double>("N=16384 D=8 EQ+Delta lower", 2, eqd, 16384, 0, 8, 1, 1, 0, eqds);
+    perf_kmat_case<float>("N=16384 D=8 EQ+Delta lower", 2, eqd, 16384, 0, 8, 1, 1, 0, eqds);
 }
 
 // one problem, for rocprofv3: kmat + potrf (+ trsv, merge, trsm) at order n
@@ -2340,6 +2507,11 @@ int main(int argc, char** argv) {
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
+        if (!strcmp(argv[i], "--delta")) {                     // only the checks of the Delta kind
+            test_delta<double>(); test_delta<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
         if (!strcmp(argv[i], "--potrf")) {                     // only the factorisation checks (plain + look-ahead)
             test_potrf<double>(); test_potrf<float>();
             test_lookahead<double>(); test_lookahead<float>();
@@ -2411,6 +2583,7 @@ int main(int argc, char** argv) {
         test_misc<double>(); test_misc<float>();
         test_vjp_dense<double>(); test_vjp_dense<float>();
         test_rq<double>(); test_rq<float>();
+        test_delta<double>(); test_delta<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

@@ -1,7 +1,7 @@
 """Kernels and means on the GP hot path -- the slice of the reference's ``mlkernels``
 dependency that ``stheno/model/*.py`` uses:
 
-* primitives ``EQ``, ``RQ``, ``Exp``/``Matern12``, ``Matern32``, ``Matern52``, ``Linear``,
+* primitives ``EQ``, ``RQ``, ``Exp``/``Matern12``, ``Matern32``, ``Matern52``, ``Linear``, ``Delta``,
   ``OneKernel``, ``ZeroKernel`` with the ``v * k``, ``k1 + k2``, ``k.stretch(l)``, ``k.periodic(p)`` algebra
   (usage: ``readme_example13_optimisation_torch.py:34``, ``tests/model/test_cases.py:138``,
   ``readme_example1_simple_regression.py``);
@@ -22,7 +22,7 @@ from . import ops
 from .matrix import Dense, KernelDense
 
 __all__ = [
-    "Kernel", "EQ", "RQ", "Periodic", "Exp", "Matern12", "Matern32", "Matern52", "Linear", "OneKernel", "ZeroKernel",
+    "Kernel", "EQ", "RQ", "Delta", "Periodic", "Exp", "Matern12", "Matern32", "Matern52", "Linear", "OneKernel", "ZeroKernel",
     "Mean", "ZeroMean", "OneMean", "PosteriorKernel", "PosteriorMean", "SubspaceKernel",
     "mean_var", "mean_var_diag", "uprank", "num_elements",
     "MultiInput", "MultiOutputKernel", "MultiOutputMean", "InputScaled",
@@ -132,7 +132,7 @@ def _as_param(v):
 class Kernel:
     """Base class.  A kernel that is a sum of stretched/scaled primitives exposes it as
     ``terms()`` -> list of ``(kind, variance, scale)``; other kernels override
-    ``pairwise`` / ``elwise``.  Shape parameters (``RQ``'s alpha) travel beside the terms: ``shapes()`` has one entry per term,
+    ``pairwise`` / ``elwise``.  Shape parameters (``RQ``'s alpha, ``Delta``'s epsilon) travel beside the terms: ``shapes()`` has one entry per term,
     ``None`` for the kinds without one."""
 
     stationary = False
@@ -289,6 +289,30 @@ class RQ(_Primitive):
 
     def __repr__(self):
         return f"RQ({_as_float(self.alpha):g})"
+
+
+class Delta(_Primitive):
+    """Kronecker delta ``1 if r^2 < epsilon else 0`` (mlkernels' ``Delta(epsilon=1e-6)``): the kernel of a noise process,
+    ``e = GP(v * Delta())`` in ``y = f + e``.  ``r^2`` is the squared distance of the inputs as the term sees them (after a stretch or an
+    input map).  ``epsilon``: a positive number -- a threshold, not a hyper-parameter: a tensor that requires a gradient is refused."""
+    kind = "delta"
+    stationary = True
+
+    def __init__(self, epsilon=1e-6):
+        if torch.is_tensor(epsilon) and epsilon.requires_grad:
+            raise ValueError("the epsilon of Delta is not learnable (the kernel is piecewise constant in it); pass a number")
+        self.epsilon = _as_float(epsilon)
+        if not self.epsilon > 0:
+            raise ValueError("the epsilon of Delta must be positive")
+
+    def shapes(self):
+        return [self.epsilon]
+
+    def tensor_shapes(self):
+        return [self.epsilon]
+
+    def __repr__(self):
+        return f"Delta({self.epsilon:g})"
 
 
 class Matern12(_Primitive):

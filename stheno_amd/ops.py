@@ -25,15 +25,19 @@ _KIND_IDS = {
     "linear": _native.K_LINEAR,
     "const": _native.K_CONST,
     "rq": _native.K_RQ,
+    "delta": _native.K_DELTA,
 }
 
-#: kinds with a shape parameter (``rq``: alpha of ``(1 + r^2 / (2 alpha))^(-alpha)``)
-_SHAPED = ("rq",)
+#: kinds with a shape parameter (``rq``: alpha of ``(1 + r^2 / (2 alpha))^(-alpha)``; ``delta``: epsilon of ``r^2 < epsilon``)
+_SHAPED = ("rq", "delta")
+#: ... of which these have a LEARNABLE one (``delta`` is piecewise constant in its epsilon: no gradient)
+_LEARNABLE_SHAPE = ("rq",)
+_SHAPE_NAME = {"rq": "alpha", "delta": "epsilon"}
 
 
 class KTerms:
     """A kernel as a sum of ``variance * kind(. / scale)`` terms (host-side descriptor).  ``shapes``: one entry per term, the shape
-    parameter of the kinds that have one (``"rq"``: alpha > 0) and ``None`` for the others; ``self.shapes`` is ``None`` when no term
+    parameter of the kinds that have one (``"rq"``: alpha > 0, ``"delta"``: epsilon > 0) and ``None`` for the others; ``self.shapes`` is ``None`` when no term
     has one -- the calls into the library are then the ones without shapes."""
 
     def __init__(self, terms, shapes=None):
@@ -53,7 +57,7 @@ class KTerms:
         for (k, _, _), a in zip(self.terms, shapes):
             if k in _SHAPED:
                 if a is None or not float(a) > 0:
-                    raise ValueError(f"a {k!r} term needs a positive shape parameter (alpha), got {a!r}")
+                    raise ValueError(f"a {k!r} term needs a positive shape parameter ({_SHAPE_NAME[k]}), got {a!r}")
                 out.append(float(a))
             else:
                 out.append(None)
@@ -669,6 +673,102 @@ class HipBackend:
         return out
 
 
+class _HostDelta:
+    """Around a backend that is not the HIP one (the checker backends of ``tests/``, built on an oracle that predates the ``"delta"``
+    kind): ``"delta"`` terms are evaluated here, in NumPy, and every other term is handed on unchanged.  ``HipBackend`` is never
+    wrapped: there the Delta terms are terms of the fused HIP kernels like any other."""
+
+    def __init__(self, inner):
+        self._inner = inner
+
+    def __getattr__(self, name):
+        return getattr(self._inner, name)
+
+    @staticmethod
+    def _split(terms):
+        sh = terms.shapes or [None] * len(terms)
+        rest = [(t, a) for t, a in zip(terms.terms, sh) if t[0] != "delta"]
+        delta = [(i, t, a) for i, (t, a) in enumerate(zip(terms.terms, sh)) if t[0] == "delta"]
+        keep = [i for i, t in enumerate(terms.terms) if t[0] != "delta"]
+        return KTerms([t for t, _ in rest], [a for _, a in rest]), delta, keep
+
+    @staticmethod
+    def _kappa(x, y, scale, eps):
+        import numpy as np
+
+        a, b = x.detach().cpu().numpy(), y.detach().cpu().numpy()
+        q = ((a[..., :, None, :] - b[..., None, :, :]) ** 2).sum(-1) * (1.0 / scale) ** 2
+        return np.where(np.isnan(q), q, (q < eps).astype(q.dtype))
+
+    @staticmethod
+    def _t(a, like):
+        import numpy as np
+
+        return torch.as_tensor(np.ascontiguousarray(a), dtype=like.dtype, device=like.device)
+
+    def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        rest, delta, _ = self._split(terms)
+        if not delta:
+            return self._inner.kmat(terms, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out, accumulate=accumulate)
+        res = self._inner.kmat(rest, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec)
+        for _, (_, var, scale), eps in delta:
+            res = res + self._t(var * self._kappa(x, x if y is None else y, scale, eps), res)
+        if out is None:
+            return res
+        if accumulate:
+            out += res
+        else:
+            out.copy_(res)
+        return out
+
+    def kdiag(self, terms, x):
+        rest, delta, _ = self._split(terms)
+        if not delta:
+            return self._inner.kdiag(terms, x)
+        base = self._inner.kdiag(rest, x) if len(rest) else torch.zeros(x.shape[:-1], dtype=x.dtype, device=x.device)
+        return base + sum(var for _, (_, var, _), _ in delta)
+
+    def _merge_sums(self, terms, S_rest, keep, delta, sums):
+        S = torch.zeros((len(terms), 3), dtype=S_rest.dtype, device=S_rest.device)
+        if keep:
+            S[keep, : S_rest.shape[1]] = S_rest
+        for (i, _, _), v in zip(delta, sums):
+            S[i, 0] = v
+        return S
+
+    def kmat_vjp(self, terms, x, kinv, alpha, g):
+        import numpy as np
+
+        rest, delta, keep = self._split(terms)
+        if not delta:
+            return self._inner.kmat_vjp(terms, x, kinv, alpha, g)
+        S_rest, tr, dg = self._inner.kmat_vjp(rest, x, kinv, alpha, g)
+        ki = kinv.detach().cpu().numpy()
+        ki = np.tril(ki) + np.tril(ki, -1).T
+        A, gv = alpha.detach().cpu().numpy(), np.asarray(g, dtype=np.float64)
+        G = 0.5 * ((A * gv) @ A.T - gv.sum() * ki)
+        sums = [float(np.sum(G * self._kappa(x, x, scale, eps))) for _, (_, _, scale), eps in delta]
+        return self._merge_sums(terms, S_rest, keep, delta, sums), tr, dg
+
+    def kmat_vjp_dense(self, terms, x, y, g, colscale=None, w=None, b=None, want_colsum=False, want_gradx=False):
+        rest, delta, keep = self._split(terms)
+        if not delta:
+            return self._inner.kmat_vjp_dense(terms, x, y, g, colscale, w, b, want_colsum=want_colsum, want_gradx=want_gradx)
+        S_rest, colsum, gradx = self._inner.kmat_vjp_dense(rest, x, y, g, colscale, w, b, want_colsum=want_colsum, want_gradx=want_gradx)
+        Ge = g.detach().cpu().numpy().copy()
+        if colscale is not None:
+            Ge = Ge * colscale.detach().cpu().numpy()[None, :]
+        if w is not None:
+            Ge = Ge + w.detach().cpu().numpy()[:, None] * b.detach().cpu().numpy()[None, :]
+        sums = []
+        for _, (_, var, scale), eps in delta:          # piecewise constant: S1 and the column sums, nothing for the scale or the inputs
+            k = self._kappa(x, y, scale, eps)
+            sums.append(float((Ge * k).sum()))
+            if want_colsum:
+                colsum = colsum + self._t(var * (Ge * k).sum(0), colsum)
+        return self._merge_sums(terms, S_rest, keep, delta, sums), colsum, gradx
+
+
 _backend = None
 
 
@@ -683,7 +783,9 @@ def get_backend():
 
 def set_backend(backend):
     """Install an op backend.  TEST HOOK ONLY (host-logic unit tests without a GPU);
-    returns the previous backend."""
+    returns the previous backend.  A backend other than the HIP one is wrapped in :class:`_HostDelta`."""
     global _backend
+    if backend is not None and not isinstance(backend, _HostDelta) and getattr(backend, "name", None) != "hip":
+        backend = _HostDelta(backend)
     prev, _backend = _backend, backend
     return prev
