@@ -13,7 +13,7 @@
  *  - `batch` independent problems are laid out with a stride `s*` in ELEMENTS
  *    (stheno's batched computation: README.md:744-766, random.py:261,274).
  *  - Every pointer named x/y/a/b/l/out/... is a DEVICE pointer owned by the
- *    caller; term descriptors (`kinds`, `variances`, `inv_ls`, and `shapes` of the `_s` entries) are HOST arrays.
+ *    caller; term descriptors (`kinds`, `variances`, `inv_ls`, `shapes`) are HOST arrays of `nterms` entries.
  *  - `dtype`: GPK_F32 or GPK_F64; all device buffers of a call share it.
  *  - `stream` is a hipStream_t passed as void*.  Calls only ENQUEUE work: no
  *    device allocation, no free, no host synchronisation, no retained pointers.
@@ -40,15 +40,16 @@ extern "C" {
 #define GPK_OK 0
 #define GPK_ERR_LAUNCH (-100)
 
-/* kernel term kinds; one term = variance * kappa(dist(x, y) * inv_ls)   (GPK_K_RQ, GPK_K_DELTA: kappa also takes a shape parameter) */
+/* kernel term kinds; one term = variance * kappa(dist(x, y) * inv_ls)   (GPK_K_RQ, GPK_K_DELTA: kappa also takes a SHAPE parameter,
+ * shapes[t]; a term table with such a kind is "shaped") */
 #define GPK_K_EQ 0        /* exp(-r^2/2)                        mlkernels.EQ        */
 #define GPK_K_MATERN12 1  /* exp(-r)                            mlkernels.Exp       */
 #define GPK_K_MATERN32 2  /* (1+sqrt3 r) exp(-sqrt3 r)          mlkernels.Matern32  */
 #define GPK_K_MATERN52 3  /* (1+sqrt5 r+5r^2/3) exp(-sqrt5 r)   mlkernels.Matern52  */
 #define GPK_K_LINEAR 4    /* <x, y>                             mlkernels.Linear    */
 #define GPK_K_CONST 5     /* 1                                  mlkernels.OneKernel */
-#define GPK_K_RQ 6        /* (1 + r^2/(2 alpha))^(-alpha)       mlkernels.RQ(alpha): one SHAPE parameter, see gpk_kmat_s */
-#define GPK_K_DELTA 7     /* 1 if r^2 < epsilon, else 0         mlkernels.Delta(epsilon): one SHAPE parameter, see gpk_kmat_s */
+#define GPK_K_RQ 6        /* (1 + r^2/(2 alpha))^(-alpha)       mlkernels.RQ(alpha): shape = alpha > 0, see gpk_kmat */
+#define GPK_K_DELTA 7     /* 1 if r^2 < epsilon, else 0         mlkernels.Delta(epsilon): shape = epsilon > 0, see gpk_kmat */
 #define GPK_MAX_TERMS 8
 
 #define GPK_GEMM_LOWER 1
@@ -58,6 +59,7 @@ extern "C" {
 
 #define GPK_DIAG_BLOCK 128 /* order of the diagonal blocks whose inverses gpk_potrf leaves in `dinv` */
 
+/* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -70,49 +72,38 @@ int gpk_init(void);
  * teardown of the runtime / of a profiler wrapped around the process. */
 void gpk_shutdown(void);
 
-/* Kernel matrix  out[i][j] (+)= sum_t variances[t] * kappa_kinds[t](x_i, y_j; inv_ls[t])
+/* Kernel matrix  out[i][j] (+)= sum_t variances[t] * kappa_kinds[t](x_i, y_j; inv_ls[t], shapes[t])
  * and, if `symmetric` (x and y are the same points), + diag_add + diag_vec[i] on i == j.
  * Replaces mlkernels `pairwise` + `B.add(K, noise)`:  stheno/model/fdd.py:79,
  * stheno/model/observations.py:139 (K_x), :285-286 (K_zx, K_z).
  *   x: n x d (ldx), y: m x d (ldy), out: n x m (ld).  lower_only: skip tiles above the diagonal.
  *   diag_vec: nullable, n values per batch (stride s_diag).  accumulate: out += instead of out =.
+ *   shapes: read for the kinds that have a shape parameter (GPK_K_RQ: alpha, GPK_K_DELTA: epsilon) and ignored for the others; may be
+ *   NULL exactly when no term is GPK_K_RQ or GPK_K_DELTA.  A term table without such a kind writes the same bits whatever `shapes` holds.
+ *   Returns -4 for nterms outside 0 .. GPK_MAX_TERMS, -1 for an unknown kind or a shaped kind with shapes == NULL, -5 for a shape <= 0.
  *   Numerics: squared distances from direct differences (no |x|^2 + |y|^2 - 2 x.y cancellation); exp and sqrt are the library's own
  *   branch-free device routines -- every value within ~2.5 eps (1 + |argument of the exponential|) of the exactly rounded one for the
  *   given inputs (measured element by element against an 80-bit reference: csrc/selftest.cpp, `kmat_* elementwise`); NaN inputs give
- *   NaN values; the distance of a point to itself is exactly 0 (sqrt(0) is evaluated as 1e-140 in fp64). */
-int gpk_kmat(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
+ *   NaN values; the distance of a point to itself is exactly 0 (sqrt(0) is evaluated as 1e-140 in fp64).
+ *   GPK_K_RQ is evaluated as exp(-alpha log1p(q / (2 alpha))), q = r^2 / scale^2: a single RQ term has a row-band program of its own
+ *   next to EQ / Matern; within ~2.5 eps (1 + alpha log1p(q / (2 alpha))) of the exactly rounded value (csrc/selftest.cpp, `--rq`).
+ *   GPK_K_DELTA: with q = r^2 / scale^2 (direct differences) the value is 1 where q < epsilon and 0 elsewhere -- no transcendental, so
+ *   coincident points give exactly the variance and every element is exact in both dtypes unless q lies within rounding of epsilon;
+ *   NaN inputs give NaN.  A Delta term always takes the term-table program of the shaped launches (csrc/selftest.cpp, `--delta`):
+ *   mlkernels `Delta(epsilon)`, the noise process e of `y = f + e`. */
+int gpk_kmat(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
              const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
              int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
              int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
              void* stream);
 
-/* The same with one SHAPE parameter per term (version 102): `shapes` is a host array like `inv_ls`, read for the kinds that have a
- * shape -- GPK_K_RQ: alpha > 0 -- and ignored for the others; NULL: no term has one.  gpk_kmat IS gpk_kmat_s(shapes = NULL): with
- * `kinds` free of GPK_K_RQ both write the same bits; gpk_kmat with a GPK_K_RQ term returns -1 (no alpha was given), gpk_kmat_s with a
- * non-positive alpha -5.  RQ is evaluated as exp(-alpha log1p(q / (2 alpha))), q = r^2 / scale^2: a single RQ term has a row-band
- * program of its own next to EQ / Matern; within ~2.5 eps (1 + alpha log1p(q / (2 alpha))) of the exactly rounded value
- * (csrc/selftest.cpp, `--rq`).  Replaces mlkernels `pairwise` of `RQ(alpha)` and of sums with it.
- * GPK_K_DELTA (version 103): shapes[t] = epsilon > 0; with q = r^2 / scale^2 (direct differences) the value is 1 where q < epsilon and 0
- * elsewhere -- no transcendental, so coincident points give exactly the variance and every element is exact in both dtypes unless q
- * lies within rounding of epsilon; NaN inputs give NaN.  Same return codes as RQ's alpha: -1 through gpk_kmat (no epsilon was given),
- * -5 for a non-positive epsilon.  A Delta term always takes the term-table program of the launches with shapes (csrc/selftest.cpp,
- * `--delta`).  Replaces mlkernels `pairwise` of `Delta(epsilon)`: the noise process e of `y = f + e`. */
-int gpk_kmat_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-               const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
-               int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
-               int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
-               void* stream);
-
 /* Kernel diagonal  out[i] = k(x_i, x_i).  Replaces mlkernels `elwise`:
- * stheno/model/fdd.py:66, stheno/model/observations.py:304. */
-int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
+ * stheno/model/fdd.py:66, stheno/model/observations.py:304.
+ * `shapes` as for gpk_kmat, with the same return codes (-4, -1 for a shaped kind with shapes == NULL, -5 for a shape <= 0; kinds are
+ * not range-checked): an RQ or Delta term contributes its variance on the diagonal, whatever its shape. */
+int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
               const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
               int64_t batch, void* stream);
-/* ... with the shape parameters of gpk_kmat_s (an RQ or Delta term contributes its variance on the diagonal, whatever its shape; a
- * Delta term through gpk_kdiag returns -1, a non-positive epsilon -5). */
-int gpk_kdiag_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
-                int64_t batch, void* stream);
 
 /* Number of elements of the `dinv` workspace gpk_potrf needs per batch entry. */
 int64_t gpk_dinv_elems(int64_t n);
@@ -354,28 +345,26 @@ int gpk_gemv(int dtype, int trans, int64_t m, int64_t k, int nrhs, double alpha,
 int gpk_trtri_lower(int dtype, const void* l, int64_t n, int64_t ld, const void* dinv_sb, int sb, void* w,
                     int64_t ldw, void* tmp, void* stream);
 
+/* The two kernel VJPs below leave per-workgroup PARTIAL ROWS of NS * GPK_MAX_TERMS + 1 elements, to be summed over the rows by the
+ * caller: NS = 3 if any term's kind has a shape parameter (GPK_K_RQ, GPK_K_DELTA), NS = 2 otherwise --
+ *   row[NS t] = S1_t = sum G kappa_t,   row[NS t + 1] = S2_t = sum G kappa_t'(q) q,   row[NS t + 2] = S3_t = sum G d kappa_t / d shape_t
+ *   (NS = 3 only; 0 for kinds without a shape),   row[NS * GPK_MAX_TERMS]: the trace slot.
+ * d/d variance_t = S1_t;  d/d scale_t = -2 v_t S2_t / l_t;  d/d alpha_t = v_t S3_t.
+ * RQ, with u = q / (2 alpha): kappa' q = -(q / 2) kappa / (1 + u),  d kappa / d alpha = kappa (u / (1 + u) - log1p(u)).
+ * Delta (piecewise constant): S2_t = S3_t = 0 -- its variance is learnable, its scale and epsilon are not.
+ * `shapes` as for gpk_kmat: may be NULL exactly when no term is shaped; a shaped kind with shapes == NULL returns -1. */
+
 /* Kernel-hyperparameter VJP of the GP log-density (hyper-parameter learning through
  * `f(x, noise).logpdf(y)`: readme_example13_optimisation_torch.py:47-53).  With
  *   G = d logpdf / dK = 1/2 (A diag(g) A^T - sum(g) K^{-1}),  A = K^{-1} (y - m)  (n x ncols <= 8),
- * one pass over the LOWER triangle of `kinv` accumulates per workgroup
- *   partial[b][2t] = sum_ij G_ij kappa_t,  partial[b][2t+1] = sum_ij G_ij kappa_t'(q) q,
- *   partial[b][2*GPK_MAX_TERMS] = trace(G)   (row stride 2*GPK_MAX_TERMS + 1; sum over b),
- * and writes diag_g[i] = G_ii.  d logpdf/d variance_t = S1_t; d logpdf/d scale_t = -2 v_t S2_t / l_t;
- * d logpdf / d noise_i = G_ii.  `g` (host): upstream gradient per column. */
+ * one pass over the LOWER triangle of `kinv` accumulates one partial row per workgroup (gpk_kmat_vjp_blocks(n) of them; the trace
+ * slot holds trace(G)) and writes diag_g[i] = G_ii = d logpdf / d noise_i.  `g` (host): upstream gradient per column.
+ * Returns -3 for nterms outside 0 .. GPK_MAX_TERMS, -1 for an unknown kind or missing `shapes`, -3 for an RQ alpha <= 0, -5 for a
+ * Delta epsilon <= 0. */
 int64_t gpk_kmat_vjp_blocks(int64_t n);
-int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, int nterms, const void* x, int64_t n,
+int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, const double* shapes, int nterms, const void* x, int64_t n,
                  int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
                  const double* g, void* partial, void* diag_g, void* stream);
-/* The same with shape parameters (gpk_kmat_s): one more sum per term, S3_t = sum_ij G_ij d kappa_t / d shape_t (0 for kinds without a
- * shape), and a row layout of its own --
- *   partial[b][3t] = S1_t,  partial[b][3t+1] = S2_t,  partial[b][3t+2] = S3_t,  partial[b][3*GPK_MAX_TERMS] = trace(G)
- *   (row stride 3*GPK_MAX_TERMS + 1; sum over b).  d logpdf / d alpha_t = v_t S3_t.
- * RQ, with u = q / (2 alpha): kappa' q = -(q / 2) kappa / (1 + u),  d kappa / d alpha = kappa (u / (1 + u) - log1p(u)).
- * Delta (piecewise constant): S1_t = sum_ij G_ij kappa_t, S2_t = S3_t = 0 -- its variance is learnable, its scale and epsilon are not.
- * A Delta term through gpk_kmat_vjp returns -1; a non-positive epsilon -5, the code gpk_kmat_s gives it. */
-int gpk_kmat_vjp_s(int dtype, const int* kinds, const double* inv_ls, const double* shapes, int nterms, const void* x, int64_t n,
-                   int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
-                   const double* g, void* partial, void* diag_g, void* stream);
 
 /* Kernel VJP with an explicit cotangent (gradient of the pseudo-point ELBO w.r.t. kernel
  * hyper-parameters, observation noise and inducing inputs: the learning loop that
@@ -383,23 +372,17 @@ int gpk_kmat_vjp_s(int dtype, const int* kinds, const double* inv_ls, const doub
  * tensors carry gradients).  For K = k(x, y) (n x m, never formed) and
  *   Geff_ij = g[i][j] * colscale[j] + w[i] * b[j]      (colscale and the pair (w, b) may be NULL),
  * one pass over g writes, per workgroup (rowtiles x nchunks of them, see gpk_kmat_vjp_dense_grid),
- *   partial[wg][2t] = sum Geff kappa_t,  partial[wg][2t+1] = sum Geff kappa_t'(q) q   (row stride
- *   2*GPK_MAX_TERMS + 1; sum over wg; d/dvariance_t = S1_t, d/dscale_t = -2 v_t S2_t / l_t),
+ *   one partial row of sums over Geff (the trace slot is unused: 0),
  *   colsum[rowtile][j] = sum_{i in tile} Geff_ij K_ij        (NULL to skip; sum over row tiles),
- *   gradx[chunk][i][0..d) = sum_{j in chunk} Geff_ij dK_ij/dx_i   (NULL to skip; needs d <= 8; sum over chunks).
- * Deterministic (no atomics). */
+ *   gradx[chunk][i][0..d) = sum_{j in chunk} Geff_ij dK_ij/dx_i   (NULL to skip; needs d <= 8; sum over chunks;
+ *   RQ: through kappa' = -kappa / (2 (1 + u)); a Delta term counts in colsum, nothing in gradx).
+ * Deterministic (no atomics).  Returns -5 for nterms outside 0 .. GPK_MAX_TERMS, -1 for an unknown kind or missing `shapes`, -4 for an
+ * RQ alpha <= 0, -5 for a Delta epsilon <= 0. */
 int gpk_kmat_vjp_dense_grid(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks);
-int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                        const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream);
-/* ... with shape parameters: partial[wg][3t .. 3t+2] = S1_t, S2_t, S3_t as for gpk_kmat_vjp_s (row stride 3*GPK_MAX_TERMS + 1; the
- * last element of a row is unused), colsum / gradx as above (RQ: dK/dx through kappa' = -kappa / (2 (1 + u)); Delta: S2_t = S3_t = 0,
- * its kappa_t counts in colsum, nothing in gradx; -1 through gpk_kmat_vjp_dense, -5 for a non-positive epsilon). */
-int gpk_kmat_vjp_dense_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                         const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
-                         const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
-                         void* partial, void* colsum, void* gradx, void* stream);
 
 /* Measurement hooks (bench.py's live roofline figure).  Between gpk_prof_start and
  * gpk_prof_stop every MFMA GEMM launch of this process is bracketed by HIP events on its

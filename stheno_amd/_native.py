@@ -27,38 +27,17 @@ SIGNATURES = {
     "gpk_shutdown": (None, []),
     "gpk_dinv_elems": (_c_i64, [_c_i64]),
     "gpk_colreduce_chunks": (_c_i64, [_c_i64]),
+    # (kinds, variances, inv_ls, shapes: host arrays, one entry per term; shapes is NULL when no term has a shape parameter)
     "gpk_kmat": (
-        _c_int,
-        [_c_int, _p_int, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
-         _c_i64, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
-         _c_ptr],
-    ),
-    "gpk_kdiag": (
-        _c_int,
-        [_c_int, _p_int, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64,
-         _c_i64, _c_ptr],
-    ),
-    # the entries with one shape parameter per term (RQ's alpha, Delta's epsilon): one more host array behind `inv_ls`
-    "gpk_kmat_s": (
         _c_int,
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
          _c_i64, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
          _c_ptr],
     ),
-    "gpk_kdiag_s": (
+    "gpk_kdiag": (
         _c_int,
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64,
          _c_i64, _c_ptr],
-    ),
-    "gpk_kmat_vjp_s": (
-        _c_int,
-        [_c_int, _p_int, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_int, _c_i64,
-         _p_dbl, _c_ptr, _c_ptr, _c_ptr],
-    ),
-    "gpk_kmat_vjp_dense_s": (
-        _c_int,
-        [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr,
-         _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr],
     ),
     "gpk_potrf": (_c_int, [_c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_int, _c_ptr]),
     "gpk_potrf_la_ws_elems": (_c_i64, [_c_i64, _c_int]),
@@ -124,13 +103,13 @@ SIGNATURES = {
     "gpk_kmat_vjp_blocks": (_c_i64, [_c_i64]),
     "gpk_kmat_vjp": (
         _c_int,
-        [_c_int, _p_int, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_int, _c_i64,
+        [_c_int, _p_int, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_int, _c_i64,
          _p_dbl, _c_ptr, _c_ptr, _c_ptr],
     ),
     "gpk_kmat_vjp_dense_grid": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "gpk_kmat_vjp_dense": (
         _c_int,
-        [_c_int, _p_int, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr,
+        [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr,
          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr],
     ),
     "gpk_gemm_colss_rows": (_c_i64, [_c_i64]),

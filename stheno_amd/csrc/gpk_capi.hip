@@ -1,7 +1,6 @@
 // gpk_capi.hip -- the extern "C" boundary declared in include/gpk.h: dtype
 // dispatch onto the templated launchers.  No torch types, no exceptions.
 #include "gpk_common.hpp"
-#include "../../include/gpk.h"
 
 #define DISPATCH(dtype, CALL_F32, CALL_F64)  \
     do {                                     \
@@ -39,44 +38,27 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 103; }
+int gpk_version(void) { return 104; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
 int64_t gpk_dinv_elems(int64_t n) { return gpk_cdiv(n > 0 ? n : 1, GPK_DB) * GPK_DB * GPK_DB; }
 
-int gpk_kmat(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kmat(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
              const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
              int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
              int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
              void* stream) {
-    D1(dtype, gpk_kmat_launch<T>(kinds, variances, inv_ls, nterms, (const T*)x, n, ldx, sx, (const T*)y, m,
+    D1(dtype, gpk_kmat_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, sx, (const T*)y, m,
                                  ldy, sy, d, (T*)out, ld, so, batch, lower_only, symmetric, diag_add,
                                  (const T*)diag_vec, s_diag, accumulate, (hipStream_t)stream));
 }
 
-int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
               const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
               int64_t batch, void* stream) {
-    D1(dtype, gpk_kdiag_launch<T>(kinds, variances, inv_ls, nterms, (const T*)x, n, ldx, sx, d, (T*)out, so,
+    D1(dtype, gpk_kdiag_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, sx, d, (T*)out, so,
                                   batch, (hipStream_t)stream));
-}
-
-int gpk_kmat_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-               const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
-               int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
-               int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
-               void* stream) {
-    D1(dtype, gpk_kmat_launch<T>(kinds, variances, inv_ls, nterms, (const T*)x, n, ldx, sx, (const T*)y, m,
-                                 ldy, sy, d, (T*)out, ld, so, batch, lower_only, symmetric, diag_add,
-                                 (const T*)diag_vec, s_diag, accumulate, (hipStream_t)stream, shapes));
-}
-
-int gpk_kdiag_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
-                int64_t batch, void* stream) {
-    D1(dtype, gpk_kdiag_launch<T>(kinds, variances, inv_ls, nterms, (const T*)x, n, ldx, sx, d, (T*)out, so,
-                                  batch, (hipStream_t)stream, shapes));
 }
 
 int gpk_potrf(int dtype, void* a, int64_t n, int64_t ld, int64_t sa, int64_t batch, void* dinv,
@@ -260,18 +242,11 @@ int gpk_trtri_lower(int dtype, const void* l, int64_t n, int64_t ld, const void*
 
 int64_t gpk_kmat_vjp_blocks(int64_t n) { return gpk_kmat_vjp_blocks_impl(n); }
 
-int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, int nterms, const void* x, int64_t n,
+int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, const double* shapes, int nterms, const void* x, int64_t n,
                  int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
                  const double* g, void* partial, void* diag_g, void* stream) {
-    D1(dtype, gpk_kmat_vjp_launch<T>(kinds, inv_ls, nterms, (const T*)x, n, ldx, d, (const T*)kinv, ldk,
+    D1(dtype, gpk_kmat_vjp_launch<T>(kinds, inv_ls, shapes, nterms, (const T*)x, n, ldx, d, (const T*)kinv, ldk,
                                      (const T*)alpha, ncols, lda, g, (T*)partial, (T*)diag_g, (hipStream_t)stream));
-}
-
-int gpk_kmat_vjp_s(int dtype, const int* kinds, const double* inv_ls, const double* shapes, int nterms, const void* x, int64_t n,
-                   int64_t ldx, int d, const void* kinv, int64_t ldk, const void* alpha, int ncols, int64_t lda,
-                   const double* g, void* partial, void* diag_g, void* stream) {
-    D1(dtype, gpk_kmat_vjp_s_launch<T>(kinds, inv_ls, shapes, nterms, (const T*)x, n, ldx, d, (const T*)kinv, ldk,
-                                       (const T*)alpha, ncols, lda, g, (T*)partial, (T*)diag_g, (hipStream_t)stream));
 }
 
 int gpk_kmat_vjp_dense_grid(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks) {
@@ -280,22 +255,13 @@ int gpk_kmat_vjp_dense_grid(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nc
     return GPK_OK;
 }
 
-int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                        const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream) {
-    D1(dtype, gpk_kmat_vjp_dense_launch<T>(kinds, variances, inv_ls, nterms, (const T*)x, n, ldx, (const T*)y, m,
+    D1(dtype, gpk_kmat_vjp_dense_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, (const T*)y, m,
                                            ldy, d, (const T*)g, ldg, (const T*)colscale, (const T*)w,
                                            (const T*)b, (T*)partial, (T*)colsum, (T*)gradx, (hipStream_t)stream));
-}
-
-int gpk_kmat_vjp_dense_s(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                         const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
-                         const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
-                         void* partial, void* colsum, void* gradx, void* stream) {
-    D1(dtype, gpk_kmat_vjp_dense_s_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, (const T*)y, m,
-                                             ldy, d, (const T*)g, ldg, (const T*)colscale, (const T*)w,
-                                             (const T*)b, (T*)partial, (T*)colsum, (T*)gradx, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/gpk.h"   // status codes, kernel term kinds, GPK_MAX_TERMS, flags
 
 // Tuning knobs.  A RELEASE build (the default) has none: every "knob" is a compile-time constant at its measured optimum, the
 // branches it guards are folded away and gpk_tune() does nothing.  `make dev` (-DGPK_DEV_KNOBS, into dev/) builds the library with
@@ -25,12 +26,8 @@
 #define GPK_WAVE 64
 #define GPK_TILE 128      // GEMM block tile (rows and cols)
 #define GPK_DB 128        // diagonal block factorised in LDS by one workgroup
-#define GPK_MAX_TERMS 8
 
-// status codes (mirrored in include/gpk.h)
-#define GPK_OK 0
 #define GPK_ERR_ARG(i) (-(i))
-#define GPK_ERR_LAUNCH (-100)
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -239,16 +236,31 @@ int gpk_sum_lower_launch(const T* parts, int64_t nparts, int64_t n, int64_t ldp,
 template <typename T>
 int gpk_add_diag_launch(T* A, int64_t n, int64_t ld, int64_t sA, T s, const T* v, int64_t sv,
                         int64_t batch, hipStream_t stream);
+// Check a kernel term table (host arrays; 0 <= nterms <= GPK_MAX_TERMS) for the four launchers that take one.  GPK_OK and *shaped (if
+// asked for) = "some term's kind has a shape parameter" (GPK_K_RQ, GPK_K_DELTA: the launch takes the instantiation that knows them), or the status
+// of the first bad term: -1 for a kind out of range (where `check_kinds`) or a shaped kind without a `shapes` array, `rq_err` for an RQ
+// alpha <= 0, -5 for a Delta epsilon <= 0.  These numbers are what each entry has always returned (tests pin them), not argument positions.
+static inline int gpk_check_terms(const int* kinds, const double* shapes, int nterms, bool check_kinds, int rq_err, bool* shaped) {
+    if (shaped) *shaped = false;
+    for (int t = 0; t < nterms; ++t) {
+        if (check_kinds && (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_DELTA)) return GPK_ERR_ARG(1);
+        if (kinds[t] != GPK_K_RQ && kinds[t] != GPK_K_DELTA) continue;
+        if (shaped) *shaped = true;
+        if (shapes == nullptr) return GPK_ERR_ARG(1);
+        if (!(shapes[t] > 0)) return kinds[t] == GPK_K_RQ ? rq_err : GPK_ERR_ARG(5);
+    }
+    return GPK_OK;
+}
 template <typename T>
-int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                     const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
-                    hipStream_t stream, const double* shapes = nullptr);
+                    hipStream_t stream);
 template <typename T>
-int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                      const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
-                     int64_t batch, hipStream_t stream, const double* shapes = nullptr);
+                     int64_t batch, hipStream_t stream);
 template <typename T>
 int gpk_scale_cols_launch(T* V, int64_t rows, int64_t cols, int64_t ld, int64_t sV, const T* s, int64_t ss,
                           int64_t batch, hipStream_t stream);
@@ -267,30 +279,15 @@ int gpk_trsv_step_launch(const T* W, int64_t ldw, int64_t rq, const T* Lbelow, i
 template <typename T>
 int gpk_potrf_rhs_launch(T* A, int64_t n, int64_t ld, int64_t batch, int64_t bstride, T* dinv, int* info, int nbo, T* B, int64_t sB, T* tmp,
                          hipStream_t stream);
-// (flags of gpk_potrf_rows_rhs, as gpk.h defines them)
-#ifndef GPK_ROWS_RHS
-#define GPK_ROWS_RHS 1
-#define GPK_ROWS_NO_TAIL_INVERSES 2
-#define GPK_ROWS_RHS_STRIP 64
-#endif
 int64_t gpk_kmat_vjp_blocks_impl(int64_t n);
+// partial rows of NS * GPK_MAX_TERMS + 1 elements, NS = 3 if some term is shaped (gpk_check_terms), else 2: gpk.h
 template <typename T>
-int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, int nterms, const T* X, int64_t n, int64_t ldx,
+int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
                         int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
                         T* partial, T* diag_g, hipStream_t stream);
-// the entries with shape parameters (gpk_kmat_vjp_s / gpk_kmat_vjp_dense_s): partial rows of 3 * GPK_MAX_TERMS + 1 elements
-template <typename T>
-int gpk_kmat_vjp_s_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
-                          int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
-                          T* partial, T* diag_g, hipStream_t stream);
-template <typename T>
-int gpk_kmat_vjp_dense_s_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                                const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                                const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                                T* colsum, T* gradx, hipStream_t stream);
 void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk);
 template <typename T>
-int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                               const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
                               const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
                               T* colsum, T* gradx, hipStream_t stream);

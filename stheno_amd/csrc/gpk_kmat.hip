@@ -16,8 +16,6 @@
 // direct differences (no |a|^2 + |b|^2 - 2ab cancellation).
 #include "gpk_common.hpp"
 
-enum { GPK_K_EQ = 0, GPK_K_MATERN12 = 1, GPK_K_MATERN32 = 2, GPK_K_MATERN52 = 3, GPK_K_LINEAR = 4, GPK_K_CONST = 5, GPK_K_RQ = 6, GPK_K_DELTA = 7 };
-
 GPK_KNOB(int, g_kmat_compact, 1);   // tuning knob (gpk_tune(34, v)): 1-D compact grid for the lower triangle of a square matrix
 GPK_KNOB(int, g_kmat_band, 1);      // tuning knob (gpk_tune(12, v)): 1 = row-band kernel, 0 = the one-tile-per-workgroup kernel
 GPK_KNOB(int, g_kmat_band_f64_sqrt, 1);   // tuning knob (gpk_tune(51, v)): fp64 kernels with a square root (Matern) take the row-band kernel too
@@ -99,10 +97,10 @@ __device__ __forceinline__ double gpk_log1p<double>(double u) { return log1p(u);
 template <>
 __device__ __forceinline__ float gpk_log1p<float>(float u) { return log1pf(u); }
 
-// RQ: the term table may hold terms of the kinds with a shape parameter -- rational quadratic, Delta -- (a launch with shape
+// SH: the term table may hold terms of the kinds with a shape parameter -- rational quadratic, Delta -- (a launch with shape
 // parameters).  A template parameter, not one more branch of the kind switch: the table program of kernels WITHOUT such a term stays
 // the code it was (the logarithm costs ~25 registers).
-template <typename T, bool RQ>
+template <typename T, bool SH>
 __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
     T val = T(0);
     for (int t = 0; t < p.nterms; ++t) {
@@ -121,10 +119,10 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
             k = (T(1) + s + s * s * T(1.0 / 3.0)) * gpk_exp<T>(-s);
         } else if (kind == GPK_K_LINEAR) {
             k = dot * p.terms[t].ils2;
-        } else if (RQ && kind == GPK_K_RQ) {
+        } else if (SH && kind == GPK_K_RQ) {
             // (1 + u)^(-alpha), u = q / (2 alpha), as exp(-alpha log1p(u)): the exponent is <= 0 like every other on this path
             k = gpk_exp<T>(-p.shape[t] * gpk_log1p<T>(q * p.hshape[t]));
-        } else if (RQ && kind == GPK_K_DELTA) {
+        } else if (SH && kind == GPK_K_DELTA) {
             // 1 within epsilon (in q: the scaled squared distance), else 0 -- no transcendental; q is a sum of squared direct
             // differences, so coincident points give exactly 1; NaN inputs stay NaN like every other kind
             k = q != q ? q : (q < p.shape[t] ? T(1) : T(0));
@@ -136,7 +134,7 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
     return val;
 }
 
-template <typename T, bool DOT, int DC, bool RQ>
+template <typename T, bool DOT, int DC, bool SH>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
     constexpr int VEC = Traits<T>::VEC;
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             const int col = colb + v;
-            T val = eval_terms<T, RQ>(p, r2[r][v], dt[r][v]);
+            T val = eval_terms<T, SH>(p, r2[r][v], dt[r][v]);
             if (p.symmetric && col == row) {
                 val += p.diag_add;
                 if (p.diag_vec != nullptr) val += p.diag_vec[b * p.sDiag + row];
@@ -594,15 +592,17 @@ __global__ __launch_bounds__(256) void kdiag_kernel(KdiagArgs<T> p) {
 
 // terms: host arrays of length nterms
 template <typename T>
-int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                     const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
-                    hipStream_t stream, const double* shapes) {
+                    hipStream_t stream) {
     if (n <= 0 || m <= 0 || batch <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
     if (n > INT32_MAX || m > INT32_MAX || batch > 65535) return GPK_ERR_ARG(6);
     if (d < 0) return GPK_ERR_ARG(13);
+    bool shaped;      // some term is RQ or Delta: the term-table program that knows them (Delta has no program of its own)
+    if (const int st = gpk_check_terms(kinds, shapes, nterms, true, GPK_ERR_ARG(5), &shaped)) return st;
     constexpr int VEC = Traits<T>::VEC;
     KmatArgs<T> a;
     a.X = X; a.Y = Y; a.out = out; a.diag_vec = diag_vec;
@@ -611,28 +611,15 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     a.nterms = nterms;
     a.need_dot = 0;
     for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_DELTA) return GPK_ERR_ARG(1);
         a.terms[t].kind = kinds[t];
         a.terms[t].variance = (T)variances[t];
         a.terms[t].ils2 = (T)(inv_ls[t] * inv_ls[t]);
         if (kinds[t] == GPK_K_LINEAR) a.need_dot = 1;
     }
-    bool has_rq = false;
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        a.shape[t] = a.hshape[t] = T(0);
-        if (t < nterms && kinds[t] == GPK_K_RQ) {
-            has_rq = true;
-            if (shapes == nullptr) return GPK_ERR_ARG(1);          // an RQ term through an entry that carries no alpha
-            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
-            a.shape[t] = (T)shapes[t];
-            a.hshape[t] = (T)(0.5 / shapes[t]);
-        }
-        if (t < nterms && kinds[t] == GPK_K_DELTA) {
-            has_rq = true;                                         // (the shaped term table: Delta has no program of its own)
-            if (shapes == nullptr) return GPK_ERR_ARG(1);          // a Delta term through an entry that carries no epsilon
-            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
-            a.shape[t] = (T)shapes[t];
-        }
+        const bool rq = t < nterms && kinds[t] == GPK_K_RQ, delta = t < nterms && kinds[t] == GPK_K_DELTA;
+        a.shape[t] = (rq || delta) ? (T)shapes[t] : T(0);
+        a.hshape[t] = rq ? (T)(0.5 / shapes[t]) : T(0);
     }
     a.diag_add = (T)diag_add;
     a.symmetric = symmetric; a.lower_only = lower_only; a.accumulate = accumulate;
@@ -682,7 +669,7 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
             case PROG_EQ_LINEAR: GPK_BAND_DC(PROG_EQ_LINEAR, true); break;
             case PROG_RQ: GPK_BAND_DC(PROG_RQ, false); break;
             default:
-                if (has_rq) {
+                if (shaped) {
                     if (a.need_dot) GPK_BAND_DC(PROG_GENERIC_RQ, true);
                     else GPK_BAND_DC(PROG_GENERIC_RQ, false);
                 } else if (a.need_dot) GPK_BAND_DC(PROG_GENERIC, true);
@@ -696,9 +683,9 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     dim3 grid((unsigned)gpk_cdiv(m, 64 * VEC), (unsigned)gy, (unsigned)batch);
 #define GPK_KMAT_LAUNCH(DCV)                                                                            \
     do {                                                                                                \
-        if (has_rq && a.need_dot)                                                                       \
+        if (shaped && a.need_dot)                                                                       \
             hipLaunchKernelGGL((kmat_kernel<T, true, DCV, true>), grid, dim3(256), 0, stream, a);       \
-        else if (has_rq)                                                                                \
+        else if (shaped)                                                                                \
             hipLaunchKernelGGL((kmat_kernel<T, false, DCV, true>), grid, dim3(256), 0, stream, a);      \
         else if (a.need_dot)                                                                            \
             hipLaunchKernelGGL((kmat_kernel<T, true, DCV, false>), grid, dim3(256), 0, stream, a);      \
@@ -719,16 +706,13 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
 }
 
 template <typename T>
-int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
+int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                      const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
-                     int64_t batch, hipStream_t stream, const double* shapes) {
+                     int64_t batch, hipStream_t stream) {
     if (n <= 0 || batch <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
-    for (int t = 0; t < nterms; ++t)
-        if (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA) {
-            if (shapes == nullptr) return GPK_ERR_ARG(1);
-            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
-        }
+    // (an RQ or Delta term is 1 on the diagonal whatever its shape: checked, not used; kinds are not range-checked here)
+    if (const int st = gpk_check_terms(kinds, shapes, nterms, false, GPK_ERR_ARG(5), nullptr)) return st;
     KdiagArgs<T> a;
     a.X = X; a.out = out; a.ldx = ldx; a.sX = sX; a.sO = sO;
     a.n = (int)n; a.d = d; a.nterms = nterms;
@@ -744,11 +728,11 @@ int gpk_kdiag_launch(const int* kinds, const double* variances, const double* in
 }
 
 #define GPK_INST(T)                                                                                   \
-    template int gpk_kmat_launch<T>(const int*, const double*, const double*, int, const T*, int64_t, \
+    template int gpk_kmat_launch<T>(const int*, const double*, const double*, const double*, int, const T*, int64_t, \
                                     int64_t, int64_t, const T*, int64_t, int64_t, int64_t, int, T*,   \
                                     int64_t, int64_t, int64_t, int, int, double, const T*, int64_t,   \
-                                    int, hipStream_t, const double*);                                 \
-    template int gpk_kdiag_launch<T>(const int*, const double*, const double*, int, const T*, int64_t, \
-                                     int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t, const double*);
+                                    int, hipStream_t);                                                \
+    template int gpk_kdiag_launch<T>(const int*, const double*, const double*, const double*, int, const T*, int64_t, \
+                                     int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t);
 GPK_INST(double)
 GPK_INST(float)

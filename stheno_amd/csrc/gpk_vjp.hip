@@ -10,13 +10,11 @@
 // HBM-bound: reads N^2/2 elements once.  Output: per-workgroup partial sums
 // [nblocks][2 T + 1] (S1_t, S2_t, trace(G)) -- summed by the caller -- and diag(G).
 //
-// Kinds with a SHAPE parameter (rational quadratic: alpha) go through the `_s` entries: the same kernels instantiated with SH = true,
-// which know VK_RQ and carry a third sum per term, S3_t = sum_ij G_ij d kappa_t / d alpha_t, in partial rows of 3 T + 1 elements.
-// VK_DELTA (1 where q < epsilon, else 0; epsilon in `shape`) lives there too: piecewise constant, so S2_t = S3_t = 0 and no d/dx.
-// The SH = false instantiations are what the entries without shapes launch: the code they have always been.
+// A term table with a kind that has a SHAPE parameter (rational quadratic: alpha) launches the same kernels instantiated with SH = true,
+// which know GPK_K_RQ and carry a third sum per term, S3_t = sum_ij G_ij d kappa_t / d alpha_t, in partial rows of 3 T + 1 elements.
+// GPK_K_DELTA (1 where q < epsilon, else 0; epsilon in `shape`) lives there too: piecewise constant, so S2_t = S3_t = 0 and no d/dx.
+// The SH = false instantiations are what every other term table launches: the code they have always been.
 #include "gpk_common.hpp"
-
-enum { VK_EQ = 0, VK_MATERN12 = 1, VK_MATERN32 = 2, VK_MATERN52 = 3, VK_LINEAR = 4, VK_CONST = 5, VK_RQ = 6, VK_DELTA = 7 };
 
 namespace {
 
@@ -56,22 +54,22 @@ __device__ __forceinline__ float vsqrt<float>(float x) { return sqrtf(x); }
 // kappa(q) and kappa'(q) * q
 template <typename T>
 __device__ __forceinline__ void kappa_and_dq(int kind, T q, T& k, T& dkq) {
-    if (kind == VK_EQ) {
+    if (kind == GPK_K_EQ) {
         k = vexp<T>(T(-0.5) * q);
         dkq = T(-0.5) * q * k;
-    } else if (kind == VK_MATERN12) {
+    } else if (kind == GPK_K_MATERN12) {
         const T r = vsqrt<T>(q);
         k = vexp<T>(-r);
         dkq = T(-0.5) * r * k;
-    } else if (kind == VK_MATERN32) {
+    } else if (kind == GPK_K_MATERN32) {
         const T s = vsqrt<T>(T(3) * q), e = vexp<T>(-s);
         k = (T(1) + s) * e;
         dkq = T(-0.5) * s * s * e;
-    } else if (kind == VK_MATERN52) {
+    } else if (kind == GPK_K_MATERN52) {
         const T s = vsqrt<T>(T(5) * q), e = vexp<T>(-s);
         k = (T(1) + s + s * s * T(1.0 / 3.0)) * e;
         dkq = -(s * s * T(1.0 / 6.0)) * (T(1) + s) * e;
-    } else if (kind == VK_LINEAR) {
+    } else if (kind == GPK_K_LINEAR) {
         k = q;
         dkq = q;
     } else {
@@ -193,13 +191,13 @@ __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
             for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
-                    const T q = (kind == VK_LINEAR ? dt[u][v] : r2[u][v]) * ils2;
+                    const T q = (kind == GPK_K_LINEAR ? dt[u][v] : r2[u][v]) * ils2;
                     T k, dkq;
-                    if (SH && kind == VK_RQ) {
+                    if (SH && kind == GPK_K_RQ) {
                         T dk, da;
                         kappa_rq<T>(q, p.shape[t], k, dkq, dk, da);
                         s3 += Gw[u][v] * da;
-                    } else if (SH && kind == VK_DELTA) {
+                    } else if (SH && kind == GPK_K_DELTA) {
                         k = kappa_delta<T>(q, p.shape[t]);
                         dkq = T(0);
                     } else {
@@ -264,26 +262,26 @@ struct VjpDenseArgs {
 // kappa(q), kappa'(q) q and kappa'(q)   (kappa' of exp(-sqrt(q)) is singular at 0: reported as 0)
 template <typename T>
 __device__ __forceinline__ void kappa_all(int kind, T q, T& k, T& dkq, T& dk) {
-    if (kind == VK_EQ) {
+    if (kind == GPK_K_EQ) {
         k = vexp<T>(T(-0.5) * q);
         dk = T(-0.5) * k;
         dkq = dk * q;
-    } else if (kind == VK_MATERN12) {
+    } else if (kind == GPK_K_MATERN12) {
         const T r = vsqrt<T>(q);
         k = vexp<T>(-r);
         dkq = T(-0.5) * r * k;
         dk = r > T(0) ? T(-0.5) * k / r : T(0);
-    } else if (kind == VK_MATERN32) {
+    } else if (kind == GPK_K_MATERN32) {
         const T s = vsqrt<T>(T(3) * q), e = vexp<T>(-s);
         k = (T(1) + s) * e;
         dk = T(-1.5) * e;
         dkq = dk * q;
-    } else if (kind == VK_MATERN52) {
+    } else if (kind == GPK_K_MATERN52) {
         const T s = vsqrt<T>(T(5) * q), e = vexp<T>(-s);
         k = (T(1) + s + s * s * T(1.0 / 3.0)) * e;
         dk = T(-5.0 / 6.0) * (T(1) + s) * e;
         dkq = dk * q;
-    } else if (kind == VK_LINEAR) {
+    } else if (kind == GPK_K_LINEAR) {
         k = q;
         dkq = q;
         dk = T(1);
@@ -388,13 +386,13 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
-                        const T q = (kind == VK_LINEAR ? dt[u][v] : r2[u][v]) * ils2;
+                        const T q = (kind == GPK_K_LINEAR ? dt[u][v] : r2[u][v]) * ils2;
                         T k, dkq, dk;
-                        if (SH && kind == VK_RQ) {
+                        if (SH && kind == GPK_K_RQ) {
                             T da;
                             kappa_rq<T>(q, p.shape[t], k, dkq, dk, da);
                             s3[SH ? t : 0] += Ge[u][v] * da;
-                        } else if (SH && kind == VK_DELTA) {
+                        } else if (SH && kind == GPK_K_DELTA) {
                             k = kappa_delta<T>(q, p.shape[t]);
                             dkq = dk = T(0);
                         } else {
@@ -403,7 +401,7 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
                         s1[t] += Ge[u][v] * k;
                         s2[t] += Ge[u][v] * dkq;
                         kfull[u][v] += var * k;
-                        if (kind == VK_LINEAR)
+                        if (kind == GPK_K_LINEAR)
                             cL[u][v] += var * ils2;
                         else
                             cS[u][v] += T(2) * var * ils2 * dk;
@@ -503,21 +501,16 @@ void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64
     if (tiles_per_chunk) *tiles_per_chunk = tpc;
 }
 
-// SH = false: kinds without a shape parameter only (an RQ or Delta term is refused: no alpha / epsilon was given); SH = true: `shapes` is
-// read for RQ and Delta terms
-template <typename T, bool SH>
-static int vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                            const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                            const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                            T* colsum, T* gradx, hipStream_t stream) {
+// SH = some term is RQ or Delta: the instantiation that reads `shapes` for them and writes the 3-wide partial rows
+template <typename T>
+int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                              const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                              const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
+                              T* colsum, T* gradx, hipStream_t stream) {
     if (n <= 0 || m <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(5);
-    for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < VK_EQ || kinds[t] > VK_DELTA) return GPK_ERR_ARG(1);
-        if ((kinds[t] == VK_RQ || kinds[t] == VK_DELTA) && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
-        if (kinds[t] == VK_RQ && !(shapes[t] > 0)) return GPK_ERR_ARG(4);
-        if (kinds[t] == VK_DELTA && !(shapes[t] > 0)) return GPK_ERR_ARG(5);
-    }
+    bool shaped;
+    if (const int st = gpk_check_terms(kinds, shapes, nterms, true, GPK_ERR_ARG(4), &shaped)) return st;
     if (n > INT32_MAX || m > INT32_MAX) return GPK_ERR_ARG(7);
     if ((w == nullptr) != (b == nullptr)) return GPK_ERR_ARG(17);
     if (gradx != nullptr && d > VDC) return GPK_ERR_ARG(12);     // d/dX is implemented for d <= 8
@@ -530,47 +523,24 @@ static int vjp_dense_launch(const int* kinds, const double* variances, const dou
     gpk_kmat_vjp_dense_grid_impl(n, m, &rt, &nc, &tpc);
     a.tiles_per_chunk = (int)tpc; a.nchunks = (int)nc; a.ctiles = (int)gpk_cdiv(m, DT);
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        a.kind[t] = t < nterms ? kinds[t] : VK_CONST;
+        a.kind[t] = t < nterms ? kinds[t] : GPK_K_CONST;
         a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
         a.var[t] = t < nterms ? (T)variances[t] : T(0);
-        a.shape[t] = (SH && t < nterms && (kinds[t] == VK_RQ || kinds[t] == VK_DELTA)) ? (T)shapes[t] : T(1);
+        a.shape[t] = (t < nterms && (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA)) ? (T)shapes[t] : T(1);
     }
     if (nc > 65535) return GPK_ERR_ARG(9);
-    hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, SH>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
+    if (shaped)
+        hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, true>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, false>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
-
-template <typename T>
-int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, int nterms,
-                              const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                              const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                              T* colsum, T* gradx, hipStream_t stream) {
-    return vjp_dense_launch<T, false>(kinds, variances, inv_ls, nullptr, nterms, X, n, ldx, Y, m, ldy, d, G, ldg, colscale, w, b, partial,
-                                      colsum, gradx, stream);
-}
-template <typename T>
-int gpk_kmat_vjp_dense_s_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                                const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                                const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                                T* colsum, T* gradx, hipStream_t stream) {
-    return vjp_dense_launch<T, true>(kinds, variances, inv_ls, shapes, nterms, X, n, ldx, Y, m, ldy, d, G, ldg, colscale, w, b, partial,
-                                     colsum, gradx, stream);
-}
-template int gpk_kmat_vjp_dense_s_launch<double>(const int*, const double*, const double*, const double*, int, const double*, int64_t,
-                                                 int64_t, const double*, int64_t, int64_t, int, const double*, int64_t,
-                                                 const double*, const double*, const double*, double*, double*,
-                                                 double*, hipStream_t);
-template int gpk_kmat_vjp_dense_s_launch<float>(const int*, const double*, const double*, const double*, int, const float*, int64_t,
-                                                int64_t, const float*, int64_t, int64_t, int, const float*, int64_t,
-                                                const float*, const float*, const float*, float*, float*, float*,
-                                                hipStream_t);
-
-template int gpk_kmat_vjp_dense_launch<double>(const int*, const double*, const double*, int, const double*, int64_t,
+template int gpk_kmat_vjp_dense_launch<double>(const int*, const double*, const double*, const double*, int, const double*, int64_t,
                                                int64_t, const double*, int64_t, int64_t, int, const double*, int64_t,
                                                const double*, const double*, const double*, double*, double*,
                                                double*, hipStream_t);
-template int gpk_kmat_vjp_dense_launch<float>(const int*, const double*, const double*, int, const float*, int64_t,
+template int gpk_kmat_vjp_dense_launch<float>(const int*, const double*, const double*, const double*, int, const float*, int64_t,
                                               int64_t, const float*, int64_t, int64_t, int, const float*, int64_t,
                                               const float*, const float*, const float*, float*, float*, float*,
                                               hipStream_t);
@@ -580,19 +550,15 @@ int64_t gpk_kmat_vjp_blocks_impl(int64_t n) {
     return nt * (nt + 1) / 2;
 }
 
-// partial: gpk_kmat_vjp_blocks(n) * (2 * GPK_MAX_TERMS + 1) elements; diag_g: n elements
-template <typename T, bool SH>
-static int vjp_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
-                      int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
-                      T* partial, T* diag_g, hipStream_t stream) {
+// partial: gpk_kmat_vjp_blocks(n) * (NS * GPK_MAX_TERMS + 1) elements, NS = 3 if some term is RQ or Delta (SH), else 2; diag_g: n elements
+template <typename T>
+int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
+                        int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
+                        T* partial, T* diag_g, hipStream_t stream) {
     if (n <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(3);
-    for (int t = 0; t < nterms; ++t) {
-        if (kinds[t] < VK_EQ || kinds[t] > VK_DELTA) return GPK_ERR_ARG(1);
-        if ((kinds[t] == VK_RQ || kinds[t] == VK_DELTA) && (!SH || shapes == nullptr)) return GPK_ERR_ARG(1);
-        if (kinds[t] == VK_RQ && !(shapes[t] > 0)) return GPK_ERR_ARG(3);
-        if (kinds[t] == VK_DELTA && !(shapes[t] > 0)) return GPK_ERR_ARG(5);       // (the code gpk_kmat_s gives a bad epsilon)
-    }
+    bool shaped;
+    if (const int st = gpk_check_terms(kinds, shapes, nterms, true, GPK_ERR_ARG(3), &shaped)) return st;
     if (C < 1 || C > VMAXC) return GPK_ERR_ARG(11);
     if (n > INT32_MAX) return GPK_ERR_ARG(5);
     VjpArgs<T> a;
@@ -607,39 +573,21 @@ static int vjp_launch(const int* kinds, const double* inv_ls, const double* shap
     }
     a.s = (T)s;
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        a.kind[t] = t < nterms ? kinds[t] : VK_CONST;
+        a.kind[t] = t < nterms ? kinds[t] : GPK_K_CONST;
         a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
-        a.shape[t] = (SH && t < nterms && (kinds[t] == VK_RQ || kinds[t] == VK_DELTA)) ? (T)shapes[t] : T(1);
+        a.shape[t] = (t < nterms && (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA)) ? (T)shapes[t] : T(1);
     }
     const int64_t nb = gpk_kmat_vjp_blocks_impl(n);
-    hipLaunchKernelGGL((kmat_vjp_kernel<T, SH>), dim3((unsigned)nb), dim3(256), 0, stream, a);
+    if (shaped)
+        hipLaunchKernelGGL((kmat_vjp_kernel<T, true>), dim3((unsigned)nb), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((kmat_vjp_kernel<T, false>), dim3((unsigned)nb), dim3(256), 0, stream, a);
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
-
-template <typename T>
-int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, int nterms, const T* X, int64_t n, int64_t ldx,
-                        int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
-                        T* partial, T* diag_g, hipStream_t stream) {
-    return vjp_launch<T, false>(kinds, inv_ls, nullptr, nterms, X, n, ldx, d, Kinv, ldk, A, C, lda, g, partial, diag_g, stream);
-}
-// partial: gpk_kmat_vjp_blocks(n) * (3 * GPK_MAX_TERMS + 1) elements
-template <typename T>
-int gpk_kmat_vjp_s_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
-                          int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
-                          T* partial, T* diag_g, hipStream_t stream) {
-    return vjp_launch<T, true>(kinds, inv_ls, shapes, nterms, X, n, ldx, d, Kinv, ldk, A, C, lda, g, partial, diag_g, stream);
-}
-template int gpk_kmat_vjp_s_launch<double>(const int*, const double*, const double*, int, const double*, int64_t, int64_t, int,
-                                           const double*, int64_t, const double*, int, int64_t, const double*,
-                                           double*, double*, hipStream_t);
-template int gpk_kmat_vjp_s_launch<float>(const int*, const double*, const double*, int, const float*, int64_t, int64_t, int,
-                                          const float*, int64_t, const float*, int, int64_t, const double*, float*,
-                                          float*, hipStream_t);
-
-template int gpk_kmat_vjp_launch<double>(const int*, const double*, int, const double*, int64_t, int64_t, int,
+template int gpk_kmat_vjp_launch<double>(const int*, const double*, const double*, int, const double*, int64_t, int64_t, int,
                                          const double*, int64_t, const double*, int, int64_t, const double*,
                                          double*, double*, hipStream_t);
-template int gpk_kmat_vjp_launch<float>(const int*, const double*, int, const float*, int64_t, int64_t, int,
+template int gpk_kmat_vjp_launch<float>(const int*, const double*, const double*, int, const float*, int64_t, int64_t, int,
                                         const float*, int64_t, const float*, int, int64_t, const double*, float*,
                                         float*, hipStream_t);

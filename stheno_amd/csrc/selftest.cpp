@@ -277,7 +277,7 @@ static void test_kmat_case(std::vector<int> kinds, int n, int m, int d, int batc
     auto dv = randv<T>((size_t)batch * n);
     Dev<T> dX(X.size()), dY(Y.size()), dO(O.size()), dD(dv.size());
     dX.up(X); dY.up(Y); dO.up(O); dD.up(dv);
-    int st = gpk_kmat(DT<T>::v, kinds.data(), var.data(), il.data(), nt, dX.p, n, d, (int64_t)n * d, sym ? dX.p : dY.p, m, d, (int64_t)m * d, d,
+    int st = gpk_kmat(DT<T>::v, kinds.data(), var.data(), il.data(), nullptr, nt, dX.p, n, d, (int64_t)n * d, sym ? dX.p : dY.p, m, d, (int64_t)m * d, d,
                       dO.p, ld, (int64_t)n * ld, batch, lower, sym, sym ? 0.25 : 0.0, dvec ? dD.p : nullptr, n, acc, nullptr);
     HIPCHK(hipDeviceSynchronize());
     auto got = dO.down();
@@ -315,7 +315,7 @@ static void test_kmat_ulp(int kind, double scale, double ilv) {
     Dev<T> dX(X.size()), dY(Y.size()), dO((size_t)n * m);
     dX.up(X); dY.up(Y);
     double var = 1.3, il = ilv;
-    int st = gpk_kmat(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+    int st = gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
     HIPCHK(hipDeviceSynchronize());
     auto got = dO.down();
     double worst = 0, amin = 0;
@@ -360,7 +360,7 @@ static void test_kmat() {
         auto X = randv<T>(n * d);
         Dev<T> dX(X.size()), dO(n);
         dX.up(X);
-        int st = gpk_kdiag(DT<T>::v, kinds.data(), var.data(), il.data(), 2, dX.p, n, d, n * d, d, dO.p, n, 1, nullptr);
+        int st = gpk_kdiag(DT<T>::v, kinds.data(), var.data(), il.data(), nullptr, 2, dX.p, n, d, n * d, d, dO.p, n, 1, nullptr);
         HIPCHK(hipDeviceSynchronize());
         std::vector<double> ref(n);
         for (int i = 0; i < n; ++i) { double nr = 0; for (int k = 0; k < d; ++k) nr += (double)X[i * d + k] * X[i * d + k]; ref[i] = 0.7 + 1.3 * 0.25 * nr; }
@@ -991,7 +991,7 @@ static void test_vjp_dense_case(std::vector<int> kinds, int n, int m, int d, boo
     const int W = 2 * GPK_MAX_TERMS + 1;
     Dev<T> dX(X.size()), dY(Y.size()), dG(G.size()), dcs(m), dw(n), db(m), dP((size_t)rt * nc * W), dC((size_t)rt * m), dGX((size_t)nc * n * d);
     dX.up(X); dY.up(Y); dG.up(G); dcs.up(cs); dw.up(w); db.up(b);
-    int st = gpk_kmat_vjp_dense(DT<T>::v, kinds.data(), var.data(), il.data(), nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg,
+    int st = gpk_kmat_vjp_dense(DT<T>::v, kinds.data(), var.data(), il.data(), nullptr, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg,
                                 scale_rank1 ? dcs.p : nullptr, scale_rank1 ? dw.p : nullptr, scale_rank1 ? db.p : nullptr,
                                 dP.p, dC.p, want_gx ? dGX.p : nullptr, nullptr);
     HIPCHK(hipDeviceSynchronize());
@@ -1037,14 +1037,14 @@ static void test_vjp_dense() {
         Dev<T> z(64);
         std::vector<int> kinds = {GPK_K_EQ};
         std::vector<double> one = {1.0};
-        int st = gpk_kmat_vjp_dense(DT<T>::v, kinds.data(), one.data(), one.data(), 1, z.p, 2, 9, z.p, 2, 9, 9, z.p, 2, nullptr, nullptr, nullptr, z.p, nullptr, z.p, nullptr);
+        int st = gpk_kmat_vjp_dense(DT<T>::v, kinds.data(), one.data(), one.data(), nullptr, 1, z.p, 2, 9, z.p, 2, 9, 9, z.p, 2, nullptr, nullptr, nullptr, z.p, nullptr, z.p, nullptr);
         report(std::string("vjp_dense_refuses_gradx_d9_") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 1.0);
     }
 }
 
 
 // ----------------------------------------------------------------------------
-// rational quadratic: the kind with a shape parameter (gpk_kmat_s / gpk_kdiag_s / gpk_kmat_vjp_s / gpk_kmat_vjp_dense_s)   --rq
+// rational quadratic: the kind with a shape parameter (`shapes` of gpk_kmat / gpk_kdiag / gpk_kmat_vjp / gpk_kmat_vjp_dense)   --rq
 // ----------------------------------------------------------------------------
 // RQ values element by element against the 80-bit reference, in units of eps (1 + alpha log1p(u)), u = q / (2 alpha): the rounding
 // of the squared distance reaches the value multiplied by the exponent alpha log1p(u) (at most, for u >> 1), the rest is the device's
@@ -1061,7 +1061,7 @@ static void test_rq_ulp(double alpha, double scale, double ilv, bool generic) {
     dX.up(X); dY.up(Y);
     int kinds[2] = {GPK_K_RQ, GPK_K_CONST};
     double var[2] = {1.3, 0.0}, il[2] = {ilv, 1.0}, sh[2] = {alpha, 0.0};
-    int st = gpk_kmat_s(DT<T>::v, kinds, var, il, sh, generic ? 2 : 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+    int st = gpk_kmat(DT<T>::v, kinds, var, il, sh, generic ? 2 : 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
     HIPCHK(hipDeviceSynchronize());
     auto got = dO.down();
     double worst = 0, amax = 0;
@@ -1100,28 +1100,28 @@ static void test_rq() {
             }
     }
     gpk_tune(12, 1);
-    {   // the entries with shapes and kinds without one: the same bits as the entries without; an RQ term without alpha is refused
+    {   // kinds without a shape parameter: a non-NULL junk `shapes` array gives the same bits as NULL; an RQ term without alpha is refused
         const int n = 130, d = 3;
         auto X = randv<T>((size_t)n * d);
         Dev<T> dX(X.size()), dA((size_t)n * n), dB((size_t)n * n);
         dX.up(X);
         int kind = GPK_K_EQ, rq = GPK_K_RQ; double var = 0.8, il = 1.1, sh = 7.0, bad = 0.0;
-        int st = gpk_kmat(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
-        st |= gpk_kmat_s(DT<T>::v, &kind, &var, &il, &sh, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dB.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        int st = gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        st |= gpk_kmat(DT<T>::v, &kind, &var, &il, &sh, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dB.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
         HIPCHK(hipDeviceSynchronize());
         auto a = dA.down(), b = dB.down();
-        report(std::string("kmat_s without rq terms == kmat, bit for bit ") + DT<T>::name(), (st == 0 && !memcmp(a.data(), b.data(), a.size() * sizeof(T))) ? 0.0 : INFINITY, 0.0);
-        st = gpk_kmat(DT<T>::v, &rq, &var, &il, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        report(std::string("kmat without rq terms: junk shapes == NULL shapes, bit for bit ") + DT<T>::name(), (st == 0 && !memcmp(a.data(), b.data(), a.size() * sizeof(T))) ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat(DT<T>::v, &rq, &var, &il, nullptr, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
         report(std::string("kmat refuses an rq term (no alpha) ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kmat_s(DT<T>::v, &rq, &var, &il, &bad, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
-        report(std::string("kmat_s refuses alpha <= 0 ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat(DT<T>::v, &rq, &var, &il, &bad, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dA.p, n, 0, 1, 0, 1, 0.1, nullptr, 0, 0, nullptr);
+        report(std::string("kmat refuses alpha <= 0 ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
         Dev<T> dD(n);
         int k2[2] = {GPK_K_RQ, GPK_K_LINEAR}; double v2[2] = {0.7, 1.3}, l2[2] = {1.0, 0.5}, s2[2] = {0.3, 0.0};
-        st = gpk_kdiag_s(DT<T>::v, k2, v2, l2, s2, 2, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        st = gpk_kdiag(DT<T>::v, k2, v2, l2, s2, 2, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
         HIPCHK(hipDeviceSynchronize());
         std::vector<double> ref(n);
         for (int i = 0; i < n; ++i) { double nr = 0; for (int k = 0; k < d; ++k) nr += (double)X[i * d + k] * X[i * d + k]; ref[i] = 0.7 + 1.3 * 0.25 * nr; }
-        report(std::string("kdiag_s rq + linear ") + DT<T>::name(), st ? INFINITY : relerr(dD.down(), ref), DT<T>::eps * 50);
+        report(std::string("kdiag rq + linear ") + DT<T>::name(), st ? INFINITY : relerr(dD.down(), ref), DT<T>::eps * 50);
     }
     {   // explicit-cotangent VJP with RQ terms: three sums per term, column sums, d/dx
         const int n = 130, m = 257, d = 3, nt = 3;
@@ -1135,7 +1135,7 @@ static void test_rq() {
         const int W = 3 * GPK_MAX_TERMS + 1;
         Dev<T> dX(X.size()), dY(Y.size()), dG(G.size()), dcs(m), dw(n), db(m), dP((size_t)rt * nc * W), dC((size_t)rt * m), dGX((size_t)nc * n * d);
         dX.up(X); dY.up(Y); dG.up(G); dcs.up(cs); dw.up(w); db.up(b);
-        int st = gpk_kmat_vjp_dense_s(DT<T>::v, kinds, var, il, sh, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg, dcs.p, dw.p, db.p, dP.p, dC.p, dGX.p, nullptr);
+        int st = gpk_kmat_vjp_dense(DT<T>::v, kinds, var, il, sh, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg, dcs.p, dw.p, db.p, dP.p, dC.p, dGX.p, nullptr);
         HIPCHK(hipDeviceSynchronize());
         auto P = dP.down(), C = dC.down(), GX = dGX.down();
         std::vector<double> rS(3 * nt, 0.0), rC(m, 0.0), rGX((size_t)n * d, 0.0);
@@ -1158,14 +1158,14 @@ static void test_rq() {
         for (int64_t wg = 0; wg < rt * nc; ++wg) for (int t = 0; t < nt; ++t) for (int c = 0; c < 3; ++c) gS[3 * t + c] += P[(size_t)wg * W + 3 * t + c];
         for (int64_t r = 0; r < rt; ++r) for (int j = 0; j < m; ++j) gC[j] += C[(size_t)r * m + j];
         for (int64_t c = 0; c < nc; ++c) for (size_t e = 0; e < (size_t)n * d; ++e) gGX[e] += GX[(size_t)c * n * d + e];
-        std::string nm = std::string("vjp_dense_s_") + DT<T>::name() + " rq+eq+rq n130 m257 d3";
+        std::string nm = std::string("vjp_dense_") + DT<T>::name() + " rq+eq+rq n130 m257 d3";
         report(nm + " sums (S1, S2, S3)", st ? INFINITY : relerr(gS, rS), DT<T>::eps * 50);
         report(nm + " colsum", st ? INFINITY : relerr(gC, rC), DT<T>::eps * 50);
         report(nm + " gradx", st ? INFINITY : relerr(gGX, rGX), DT<T>::eps * 50);
-        st = gpk_kmat_vjp_dense(DT<T>::v, kinds, var, il, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg, dcs.p, dw.p, db.p, dP.p, dC.p, dGX.p, nullptr);
+        st = gpk_kmat_vjp_dense(DT<T>::v, kinds, var, il, nullptr, nt, dX.p, n, d, dY.p, m, d, d, dG.p, ldg, dcs.p, dw.p, db.p, dP.p, dC.p, dGX.p, nullptr);
         report(std::string("vjp_dense refuses an rq term (no alpha) ") + DT<T>::name(), st < 0 ? 0.0 : INFINITY, 0.0);
 
-        // the log-density form (gpk_kmat_vjp_s): G = 1/2 (A diag(g) A^T - sum(g) Kinv) over the lower triangle of a symmetric Kinv
+        // the log-density form (gpk_kmat_vjp): G = 1/2 (A diag(g) A^T - sum(g) Kinv) over the lower triangle of a symmetric Kinv
         const int C2 = 2;
         auto Kh = randv<T>((size_t)n * n), A = randv<T>((size_t)n * C2);
         for (int i = 0; i < n; ++i) for (int j = 0; j < i; ++j) Kh[(size_t)j * n + i] = Kh[(size_t)i * n + j];
@@ -1173,7 +1173,7 @@ static void test_rq() {
         const int64_t nb = gpk_kmat_vjp_blocks(n);
         Dev<T> dK(Kh.size()), dA(A.size()), dP2((size_t)nb * W), dDg(n);
         dK.up(Kh); dA.up(A);
-        st = gpk_kmat_vjp_s(DT<T>::v, kinds, il, sh, nt, dX.p, n, d, d, dK.p, n, dA.p, C2, C2, g, dP2.p, dDg.p, nullptr);
+        st = gpk_kmat_vjp(DT<T>::v, kinds, il, sh, nt, dX.p, n, d, d, dK.p, n, dA.p, C2, C2, g, dP2.p, dDg.p, nullptr);
         HIPCHK(hipDeviceSynchronize());
         auto P2 = dP2.down();
         std::vector<double> rS2(3 * nt + 1, 0.0);
@@ -1197,12 +1197,12 @@ static void test_rq() {
             for (int t = 0; t < 3 * nt; ++t) gS2[t] += P2[(size_t)bk * W + t];
             gS2[3 * nt] += P2[(size_t)bk * W + 3 * GPK_MAX_TERMS];
         }
-        report(std::string("kmat_vjp_s_") + DT<T>::name() + " rq+eq+rq n130 d3 sums (S1, S2, S3, trace)", st ? INFINITY : relerr(gS2, rS2), DT<T>::eps * 50);
+        report(std::string("kmat_vjp_") + DT<T>::name() + " rq+eq+rq n130 d3 sums (S1, S2, S3, trace)", st ? INFINITY : relerr(gS2, rS2), DT<T>::eps * 50);
     }
 }
 
 // ----------------------------------------------------------------------------
-// Delta: 1 where the scaled squared distance is below epsilon, else 0 (gpk_kmat_s / gpk_kdiag_s and the `_s` VJP entries)   --delta
+// Delta: 1 where the scaled squared distance is below epsilon, else 0 (epsilon in `shapes` of gpk_kmat / gpk_kdiag and the VJP entries)   --delta
 // ----------------------------------------------------------------------------
 // Inputs are small integers over 4 with rows of y copied from x: every squared distance is 0 or at least 1/16, computed without
 // rounding in both dtypes, so the host evaluates the kernel EXACTLY and every element has to match bit for bit -- Delta alone, beside
@@ -1234,7 +1234,7 @@ static void test_delta() {
                         std::vector<T> base((size_t)n * m);
                         for (size_t e = 0; e < base.size(); ++e) base[e] = (T)((int)(e % 7) - 3);
                         dO.up(base);
-                        int st = gpk_kmat_s(DT<T>::v, kinds, var, ils, sh, nt, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, acc, nullptr);
+                        int st = gpk_kmat(DT<T>::v, kinds, var, ils, sh, nt, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, acc, nullptr);
                         HIPCHK(hipDeviceSynchronize());
                         auto got = dO.down();
                         size_t bad = 0, ones = 0;
@@ -1261,7 +1261,7 @@ static void test_delta() {
                 for (int i = 100; i < n; ++i) for (int k = 0; k < d; ++k) X[(size_t)i * d + k] = X[(size_t)(i - 100) * d + k];
                 dX.up(X);
                 double one = 1.0;
-                int st = gpk_kmat_s(DT<T>::v, kinds, var, &one, sh, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dS.p, n, 0, 1, 1, 1, 0.5, nullptr, 0, 0, nullptr);
+                int st = gpk_kmat(DT<T>::v, kinds, var, &one, sh, 1, dX.p, n, d, 0, dX.p, n, d, 0, d, dS.p, n, 0, 1, 1, 1, 0.5, nullptr, 0, 0, nullptr);
                 HIPCHK(hipDeviceSynchronize());
                 auto got = dS.down();
                 size_t bad = 0;
@@ -1288,40 +1288,40 @@ static void test_delta() {
         Dev<T> dX(X.size()), dY(Y.size()), dO((size_t)n * m), dD(n);
         dX.up(X); dY.up(Y);
         int kind = GPK_K_DELTA; double var = 1.5, il = 1.0, sh = eps, bad = 0.0;
-        int st = gpk_kmat_s(DT<T>::v, &kind, &var, &il, &sh, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+        int st = gpk_kmat(DT<T>::v, &kind, &var, &il, &sh, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
         HIPCHK(hipDeviceSynchronize());
         auto got = dO.down();
         size_t wrong = 0;
         for (int i = 0; i < n; ++i) for (int j = 0; j < m; ++j) wrong += (i == 5) != (got[(size_t)i * m + j] != got[(size_t)i * m + j]);
-        report(std::string("kmat_s delta: a NaN input row is a NaN row, no other ") + DT<T>::name(), st ? INFINITY : (double)wrong, 0.0);
-        st = gpk_kmat(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+        report(std::string("kmat delta: a NaN input row is a NaN row, no other ") + DT<T>::name(), st ? INFINITY : (double)wrong, 0.0);
+        st = gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
         report(std::string("kmat refuses a delta term (no epsilon) with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kmat_s(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
-        report(std::string("kmat_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kdiag(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        st = gpk_kmat(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, 0, dY.p, m, d, 0, d, dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+        report(std::string("kmat refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kdiag(DT<T>::v, &kind, &var, &il, nullptr, 1, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
         report(std::string("kdiag refuses a delta term with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kdiag_s(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
-        report(std::string("kdiag_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kdiag(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        report(std::string("kdiag refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
         int k2[2] = {GPK_K_DELTA, GPK_K_LINEAR}; double v2[2] = {0.75, 1.5}, l2[2] = {1.0, 0.5}, s2[2] = {eps, 0.0};
         X[5 * d + 1] = (T)0.25;
         dX.up(X);
-        st = gpk_kdiag_s(DT<T>::v, k2, v2, l2, s2, 2, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
+        st = gpk_kdiag(DT<T>::v, k2, v2, l2, s2, 2, dX.p, n, d, 0, d, dD.p, n, 1, nullptr);
         HIPCHK(hipDeviceSynchronize());
         auto dg = dD.down();
         size_t wd = 0;
         for (int i = 0; i < n; ++i) { double nr = 0; for (int k = 0; k < d; ++k) nr += (double)X[i * d + k] * X[i * d + k]; wd += (double)dg[i] != 0.75 + 1.5 * 0.25 * nr; }
-        report(std::string("kdiag_s delta + linear: mismatching elements ") + DT<T>::name(), st ? INFINITY : (double)wd, 0.0);
+        report(std::string("kdiag delta + linear: mismatching elements ") + DT<T>::name(), st ? INFINITY : (double)wd, 0.0);
         // the VJP entries: -1 without shapes, -5 for a bad epsilon
         Dev<T> dG((size_t)n * m), dP((size_t)64 * (3 * GPK_MAX_TERMS + 1)), dK((size_t)n * n), dA(n), dDg(n);
         double g1 = 1.0;
-        st = gpk_kmat_vjp_dense(DT<T>::v, &kind, &var, &il, 1, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, nullptr, nullptr, nullptr);
+        st = gpk_kmat_vjp_dense(DT<T>::v, &kind, &var, &il, nullptr, 1, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, nullptr, nullptr, nullptr);
         report(std::string("vjp_dense refuses a delta term with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kmat_vjp_dense_s(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, nullptr, nullptr, nullptr);
-        report(std::string("vjp_dense_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kmat_vjp(DT<T>::v, &kind, &il, 1, dX.p, n, d, d, dK.p, n, dA.p, 1, 1, &g1, dP.p, dDg.p, nullptr);
+        st = gpk_kmat_vjp_dense(DT<T>::v, &kind, &var, &il, &bad, 1, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, nullptr, nullptr, nullptr);
+        report(std::string("vjp_dense refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_vjp(DT<T>::v, &kind, &il, nullptr, 1, dX.p, n, d, d, dK.p, n, dA.p, 1, 1, &g1, dP.p, dDg.p, nullptr);
         report(std::string("kmat_vjp refuses a delta term with -1 ") + DT<T>::name(), st == -1 ? 0.0 : INFINITY, 0.0);
-        st = gpk_kmat_vjp_s(DT<T>::v, &kind, &il, &bad, 1, dX.p, n, d, d, dK.p, n, dA.p, 1, 1, &g1, dP.p, dDg.p, nullptr);
-        report(std::string("kmat_vjp_s refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
+        st = gpk_kmat_vjp(DT<T>::v, &kind, &il, &bad, 1, dX.p, n, d, d, dK.p, n, dA.p, 1, 1, &g1, dP.p, dDg.p, nullptr);
+        report(std::string("kmat_vjp refuses epsilon <= 0 with -5 ") + DT<T>::name(), st == -5 ? 0.0 : INFINITY, 0.0);
     }
     {   // explicit-cotangent VJP, Delta beside EQ: S1 = sum Geff kappa, S2 = S3 = 0 exactly, kappa in colsum, nothing in gradx
         const int n = 130, m = 259, d = 3, nt = 2;
@@ -1333,7 +1333,7 @@ static void test_delta() {
         const int W = 3 * GPK_MAX_TERMS + 1;
         Dev<T> dX(X.size()), dY(Y.size()), dG(G.size()), dP((size_t)rt * nc * W), dC((size_t)rt * m), dGX((size_t)nc * n * d);
         dX.up(X); dY.up(Y); dG.up(G);
-        int st = gpk_kmat_vjp_dense_s(DT<T>::v, kinds, var, il, sh, nt, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, dC.p, dGX.p, nullptr);
+        int st = gpk_kmat_vjp_dense(DT<T>::v, kinds, var, il, sh, nt, dX.p, n, d, dY.p, m, d, d, dG.p, m, nullptr, nullptr, nullptr, dP.p, dC.p, dGX.p, nullptr);
         HIPCHK(hipDeviceSynchronize());
         auto P = dP.down(), C = dC.down(), GX = dGX.down();
         std::vector<double> rS(2, 0.0), rC(m, 0.0), rGX((size_t)n * d, 0.0);
@@ -1354,7 +1354,7 @@ static void test_delta() {
             zeros = zeros && P[(size_t)wg * W + 4] == T(0) && P[(size_t)wg * W + 5] == T(0);
         }
         for (int64_t r = 0; r < rt; ++r) for (int j = 0; j < m; ++j) gC[j] += C[(size_t)r * m + j];
-        std::string nm = std::string("vjp_dense_s_") + DT<T>::name() + " eq+delta n130 m259 d3";
+        std::string nm = std::string("vjp_dense_") + DT<T>::name() + " eq+delta n130 m259 d3";
         report(nm + " S1", st ? INFINITY : relerr(gS, rS), DT<T>::eps * 50);
         report(nm + " S2 = S3 = 0 for the delta term", zeros ? 0.0 : INFINITY, 0.0);
         report(nm + " colsum", st ? INFINITY : relerr(gC, rC), DT<T>::eps * 50);
@@ -1414,7 +1414,7 @@ static void perf() {
         for (int rep = 0; rep < 2; ++rep) {
             info.zero();
             tm.start();
-            gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+            gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
             ms_k = tm.stop();
             tm.start();
             gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, 0, nullptr);
@@ -1425,7 +1425,7 @@ static void perf() {
         printf("PERF potrf_%s n=%d  %.3f ms  %.2f TFLOP/s (%.1f%% of %.1f) info=%d\n", DT<T>::name(), n, ms_p, tf, 100 * tf / peak, peak, info.down()[0]);
         for (int nbo : {128, 512}) {
             info.zero();
-            gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+            gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
             tm.start();
             gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, nbo, nullptr);
             const float ms = tm.stop();
@@ -1469,7 +1469,7 @@ static void perf() {
         for (int rep = 0; rep < 2; ++rep) {
             info.zero();
             tm.start();
-            gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+            gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
             const float ms_k = tm.stop();
             tm.start();
             gpk_potrf(DT<T>::v, K.p, n, n, (int64_t)n * n, batch, dinv.p, info.p, 0, nullptr);
@@ -1526,7 +1526,7 @@ static void perf_la(int nmax) {
         int kind = GPK_K_EQ; double var = 1.0, il = 1.0;
         for (int rep = 0; rep < 2; ++rep) {
             info.zero();
-            gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+            gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
             tm.start();
             gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, 0, nullptr);
             const float ms = tm.stop();
@@ -1541,7 +1541,7 @@ static void perf_la(int nmax) {
                 float best = 1e30f;
                 for (int rep = 0; rep < 3; ++rep) {
                     info.zero();
-                    gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+                    gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
                     tm.start();
                     gpk_potrf_la(DT<T>::v, K.p, n, n, dinv.p, dbig.p, nb, ws.p, info.p, nullptr);
                     const float ms = tm.stop();
@@ -1571,7 +1571,7 @@ static void perf_la_tail(std::initializer_list<int> ns) {
             float best = 1e30f;
             for (int rep = 0; rep < 3; ++rep) {
                 info.zero();
-                gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+                gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
                 tm.start();
                 call();
                 const float ms = tm.stop();
@@ -1622,7 +1622,7 @@ static void la_one(int n, int nb, int mode, int64_t minrows, int reps, int ldpad
     gpk_tune(7, mode); gpk_tune(6, minrows);
     for (int rep = 0; rep < reps; ++rep) {
         HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st));
-        gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, ld, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
+        gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, ld, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
         hipEventRecord(a, st);
         if (mode >= 0) gpk_potrf_la(DT<T>::v, K.p, n, ld, dinv.p, dbig.p, nb, ws.p, info.p, st);
         else gpk_potrf(DT<T>::v, K.p, n, ld, 0, 1, dinv.p, info.p, 0, st);
@@ -1655,7 +1655,7 @@ static void perf_agg(int n, int nb, int sb, int rounds, const std::vector<int>& 
         for (size_t c = 0; c < ms_list.size(); ++c) {
             gpk_tune(47, ms_list[c]);
             HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st));
-            gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
+            gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
             hipEventRecord(a, st);
             if (sb > 0 && sb < nb) gpk_potrf_la_split(DT<T>::v, K.p, n, n, dinv.p, dbig.p, nb, sb, ws.p, info.p, st);
             else gpk_potrf_la(DT<T>::v, K.p, n, n, dinv.p, dbig.p, nb, ws.p, info.p, st);
@@ -1691,7 +1691,7 @@ static void perf_rows(int n, int extra, int nb, int sb, int rounds) {
     for (int r = 0; r <= rounds; ++r)
         for (int with_rows = 0; with_rows < 2; ++with_rows) {
             HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st));
-            gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
+            gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
             HIPCHK(hipMemcpyAsync(K.p + (size_t)n * n, E.p, sizeof(T) * (size_t)extra * n, hipMemcpyDeviceToDevice, st));
             hipEventRecord(a, st);
             gpk_potrf_rows(DT<T>::v, K.p, n, with_rows ? rows : n, n, dinv.p, dbig.p, nb, (sb > 0 && sb < nb) ? sb : 0, ws.p, info.p, st);
@@ -1725,7 +1725,7 @@ static void la_clock(int n, int nb, int warm = 0) {
     const int kchunks = nb / (int)(128 / sizeof(T));
     for (int which = -2; which < 10; ++which) {      // two warm-up factorisations, then one per stamped update
         HIPCHK(hipMemsetAsync(info.p, 0, sizeof(int), st));
-        gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
+        gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, st);
         if (which >= 0) { prof.zero(); }
         for (int w = 0; w < warm; ++w) {
             gpk_update_t u{15360, 15360, 1024, WP.p, 1024, WP.p, 1024, WC.p, 15360, WC.p, 15360, 1};
@@ -1772,8 +1772,7 @@ static void perf_kmat_case(const char* nm, int nterms, const int* kinds, int64_t
         float best = 1e30f;
         for (int rep = 0; rep < 4; ++rep) {
             tm.start();
-            if (shapes) gpk_kmat_s(DT<T>::v, kinds, var, il, shapes, nterms, X.p, n, d, n * d, sym ? X.p : Y.p, m, d, sym ? n * d : 0, d, K.p, ldk, n * ldk, batch, lower, sym ? 1 : 0, 0.1, nullptr, 0, 0, nullptr);
-            else gpk_kmat(DT<T>::v, kinds, var, il, nterms, X.p, n, d, n * d, sym ? X.p : Y.p, m, d, sym ? n * d : 0, d, K.p, ldk, n * ldk, batch, lower, sym ? 1 : 0, 0.1, nullptr, 0, 0, nullptr);
+            gpk_kmat(DT<T>::v, kinds, var, il, shapes, nterms, X.p, n, d, n * d, sym ? X.p : Y.p, m, d, sym ? n * d : 0, d, K.p, ldk, n * ldk, batch, lower, sym ? 1 : 0, 0.1, nullptr, 0, 0, nullptr);
             const float ms = tm.stop();
             if (rep) best = std::min(best, ms);
         }
@@ -1828,7 +1827,7 @@ static void profile_one(int n, int nbo, int reps) {
     Timer tm;
     for (int rep = 0; rep < reps; ++rep) {
         info.zero();
-        gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+        gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
         tm.start();
         gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, nbo, nullptr);
         const float ms = tm.stop();
@@ -2284,7 +2283,7 @@ static void perf_pipe() {
                 float best = 1e30f;
                 for (int rep = 0; rep < 4; ++rep) {
                     info.zero();
-                    gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+                    gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
                     tm.start();
                     gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, nbo, nullptr);
                     const float ms = tm.stop();
@@ -2307,7 +2306,7 @@ static void perf_trsm(int n, int nrhs) {
     X.up(hx);
     int kind = GPK_K_EQ; double var = 1.0, il = 1.0;
     info.zero();
-    gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, 8, 0, X.p, n, 8, 0, 8, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+    gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, 8, 0, X.p, n, 8, 0, 8, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
     gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, 0, nullptr);
     auto hb = randv<T>((size_t)n * nrhs);
     Timer tm;
@@ -2336,7 +2335,7 @@ static void perf_trsv(int n, std::vector<int> sbs) {
     X.up(hx);
     int kind = GPK_K_EQ; double var = 1.0, il = 1.0;
     info.zero();
-    gpk_kmat(DT<T>::v, &kind, &var, &il, 1, X.p, n, 8, 0, X.p, n, 8, 0, 8, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+    gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, 8, 0, X.p, n, 8, 0, 8, K.p, n, 0, 1, 1, 1, 0.1, nullptr, 0, 0, nullptr);
     gpk_potrf(DT<T>::v, K.p, n, n, 0, 1, dinv.p, info.p, 0, nullptr);
     auto hy = randv<T>((size_t)n);
     Timer tm;
@@ -2382,7 +2381,7 @@ int main(int argc, char** argv) {
                 gpk_tune(53, mode);
                 info.zero();
                 fp.zero();
-                gpk_kmat(GPK_F32, &kind, &var, &il, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+                gpk_kmat(GPK_F32, &kind, &var, &il, nullptr, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
                 gpk_potrf(GPK_F32, K.p, n, n, (int64_t)n * n, batch, dinv.p, info.p, 0, nullptr);
                 hipLaunchKernelGGL(xor_lower_kernel, dim3(n, batch), dim3(256), 0, nullptr, reinterpret_cast<const unsigned*>(K.p), n, (long long)n * n, fp.p);
                 unsigned h = 0;
@@ -2409,7 +2408,7 @@ int main(int argc, char** argv) {
             Timer tm;
             for (int rep = 0; rep < 3; ++rep) {
                 info.zero();
-                gpk_kmat(GPK_F32, &kind, &var, &il, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+                gpk_kmat(GPK_F32, &kind, &var, &il, nullptr, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
                 tm.start();
                 gpk_potrf(GPK_F32, K.p, n, n, (int64_t)n * n, batch, dinv.p, info.p, nbo, nullptr);
                 const float ms = tm.stop();
@@ -2421,7 +2420,7 @@ int main(int argc, char** argv) {
                 for (int mode = 0; mode < 2; ++mode) {
                     gpk_tune(53, mode);
                     info.zero();
-                    gpk_kmat(GPK_F32, &kind, &var, &il, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
+                    gpk_kmat(GPK_F32, &kind, &var, &il, nullptr, 1, X.p, n, d, (int64_t)n * d, X.p, n, d, (int64_t)n * d, d, K.p, n, (int64_t)n * n, batch, 1, 1, 0.1, nullptr, 0, 0, nullptr);
                     gpk_potrf(GPK_F32, K.p, n, n, (int64_t)n * n, batch, dinv.p, info.p, nbo, nullptr);
                     hipDeviceSynchronize();
                     ref[mode].resize((size_t)8 * n * n);

@@ -179,10 +179,8 @@ class Kernel:
         y = None if y is None else uprank(y)
         if isinstance(x, MultiInput) or isinstance(y, MultiInput):
             raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
-        if accumulate:
-            return ops.get_backend().kmat(ops.KTerms(t, self.shapes()), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out,
-                                          accumulate=True)
-        return ops.get_backend().kmat(ops.KTerms(t, self.shapes()), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out)
+        return ops.get_backend().kmat(ops.KTerms(t, self.shapes()), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out,
+                                      accumulate=accumulate)
 
     def elwise(self, x, y=None, *, cache=None):
         """``k(x_i, x_i)`` as a column (..., N, 1)."""

@@ -38,7 +38,7 @@ _SHAPE_NAME = {"rq": "alpha", "delta": "epsilon"}
 class KTerms:
     """A kernel as a sum of ``variance * kind(. / scale)`` terms (host-side descriptor).  ``shapes``: one entry per term, the shape
     parameter of the kinds that have one (``"rq"``: alpha > 0, ``"delta"``: epsilon > 0) and ``None`` for the others; ``self.shapes`` is ``None`` when no term
-    has one -- the calls into the library are then the ones without shapes."""
+    has one -- the library then gets a NULL ``shapes`` array."""
 
     def __init__(self, terms, shapes=None):
         terms = list(terms)
@@ -74,7 +74,9 @@ class KTerms:
         return kinds, var, ils, n
 
     def c_shapes(self):
-        """The ``shapes`` host array of the library's ``_s`` entries (0 where a term has none); only called when ``self.shapes``."""
+        """The ``shapes`` host array of the library's entries (0 where a term has none); ``None`` (NULL) when no term has one."""
+        if self.shapes is None:
+            return None
         n = len(self.terms)
         return (ctypes.c_double * max(n, 1))(*[0.0 if a is None else a for a in self.shapes])
 
@@ -222,10 +224,7 @@ class HipBackend:
         tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
                 _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
                 self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
-        if terms.shapes is not None:      # (a term with a shape parameter: the entry that carries them; everything else calls what it always called)
-            self._st(self.lib.gpk_kmat_s(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, *tail), "gpk_kmat_s")
-            return out
-        code = self.lib.gpk_kmat(_dtype_id(x3), kinds, var, ils, nt, *tail)
+        code = self.lib.gpk_kmat(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, *tail)
         self._st(code, "gpk_kmat")
         return out
 
@@ -236,11 +235,7 @@ class HipBackend:
         B, n, d = x3.shape
         out = torch.empty(bshape + (n,), dtype=x.dtype, device=x.device)
         kinds, var, ils, nt = terms.c_arrays()
-        if terms.shapes is not None:
-            self._st(self.lib.gpk_kdiag_s(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, self._ptr(x3), n, _ld(x3), _bs(x3), d,
-                                          self._ptr(out), n, B, self._stream()), "gpk_kdiag_s")
-            return out
-        code = self.lib.gpk_kdiag(_dtype_id(x3), kinds, var, ils, nt, self._ptr(x3), n, _ld(x3), _bs(x3), d,
+        code = self.lib.gpk_kdiag(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, self._ptr(x3), n, _ld(x3), _bs(x3), d,
                                   self._ptr(out), n, B, self._stream())
         self._st(code, "gpk_kdiag")
         return out
@@ -545,32 +540,23 @@ class HipBackend:
         """Sums for the hyper-parameter gradient of the log-density (see gpk_kmat_vjp):
         returns ``(S, trace_G, diag_G)`` with ``S[t] = (sum G kappa_t, sum G kappa_t' q)``.
         ``x`` (n, d), ``kinv`` (n, n; lower triangle read), ``alpha`` (n, C <= 8), ``g``: C floats.
-        Terms with a shape parameter (``terms.shapes``): ``S`` has a third column, ``sum G d kappa_t / d shape_t`` (``gpk_kmat_vjp_s``)."""
+        Terms with a shape parameter (``terms.shapes``): ``S`` has a third column, ``sum G d kappa_t / d shape_t``."""
         self._check(x, kinv, alpha)
         n, d = x.shape
         C = alpha.shape[1]
         kinds, _, ils, nt = terms.c_arrays()
         nb = int(self.lib.gpk_kmat_vjp_blocks(n))
-        width = 2 * _native.MAX_TERMS + 1
-        partial = torch.zeros((nb, width), dtype=x.dtype, device=x.device)
+        ns = 3 if terms.shapes is not None else 2       # sums per term: the library's partial rows (gpk.h)
+        partial = torch.zeros((nb, ns * _native.MAX_TERMS + 1), dtype=x.dtype, device=x.device)
         diag_g = torch.empty((n,), dtype=x.dtype, device=x.device)
         gs = (ctypes.c_double * max(C, 1))(*[float(v) for v in g])
         alpha = alpha.contiguous()
-        if terms.shapes is not None:
-            width = 3 * _native.MAX_TERMS + 1
-            partial = torch.zeros((nb, width), dtype=x.dtype, device=x.device)
-            code = self.lib.gpk_kmat_vjp_s(_dtype_id(x), kinds, ils, terms.c_shapes(), nt, self._ptr(x), n, x.stride(0), d, self._ptr(kinv),
-                                           kinv.stride(0), self._ptr(alpha), C, alpha.stride(0), gs, self._ptr(partial),
-                                           self._ptr(diag_g), self._stream())
-            self._st(code, "gpk_kmat_vjp_s")
-            tot = partial.sum(0)
-            return tot[: 3 * nt].reshape(nt, 3), tot[3 * _native.MAX_TERMS], diag_g
-        code = self.lib.gpk_kmat_vjp(_dtype_id(x), kinds, ils, nt, self._ptr(x), n, x.stride(0), d, self._ptr(kinv),
+        code = self.lib.gpk_kmat_vjp(_dtype_id(x), kinds, ils, terms.c_shapes(), nt, self._ptr(x), n, x.stride(0), d, self._ptr(kinv),
                                      kinv.stride(0), self._ptr(alpha), C, alpha.stride(0), gs, self._ptr(partial),
                                      self._ptr(diag_g), self._stream())
         self._st(code, "gpk_kmat_vjp")
         tot = partial.sum(0)
-        return tot[: 2 * nt].reshape(nt, 2), tot[2 * _native.MAX_TERMS], diag_g
+        return tot[: ns * nt].reshape(nt, ns), tot[ns * _native.MAX_TERMS], diag_g
 
     @_on_operand_device
     def kmat_vjp_dense(self, terms, x, y, g, colscale=None, w=None, b=None, want_colsum=False, want_gradx=False):
@@ -578,7 +564,7 @@ class HipBackend:
         ``K = k(x, y)`` (see gpk_kmat_vjp_dense): returns ``(S, colsum, gradx)`` with
         ``S[t] = (sum Geff kappa_t, sum Geff kappa_t' q)``, ``colsum[j] = sum_i Geff_ij K_ij`` and
         ``gradx[i] = sum_j Geff_ij dK_ij/dx_i`` (``None`` unless asked for).
-        Terms with a shape parameter: ``S`` has a third column, ``sum Geff d kappa_t / d shape_t`` (``gpk_kmat_vjp_dense_s``)."""
+        Terms with a shape parameter: ``S`` has a third column, ``sum Geff d kappa_t / d shape_t``."""
         self._check(x, y, g, colscale, w, b)
         n, d = x.shape
         m = y.shape[0]
@@ -601,10 +587,7 @@ class HipBackend:
                 m, y.stride(0), d, self._ptr(g), g.stride(0), self._ptr(cs), self._ptr(w),
                 self._ptr(b), self._ptr(partial), self._ptr(colsum), self._ptr(gradx),
                 self._stream())
-        if terms.shapes is not None:
-            self._st(self.lib.gpk_kmat_vjp_dense_s(_dtype_id(x), kinds, var, ils, terms.c_shapes(), nt, *tail), "gpk_kmat_vjp_dense_s")
-        else:
-            self._st(self.lib.gpk_kmat_vjp_dense(_dtype_id(x), kinds, var, ils, nt, *tail), "gpk_kmat_vjp_dense")
+        self._st(self.lib.gpk_kmat_vjp_dense(_dtype_id(x), kinds, var, ils, terms.c_shapes(), nt, *tail), "gpk_kmat_vjp_dense")
         tot = partial.sum(0)
         return (tot[: ns * nt].reshape(nt, ns), colsum.sum(0) if want_colsum else None,
                 gradx.sum(0) if want_gradx else None)

@@ -7,8 +7,8 @@ kinds ``eq``, ``matern12``, ``matern32``, ``matern52``, ``const``, ``rq`` and ``
 (``q / 2``, ``sqrt(c q)``, ``alpha log1p(q / (2 alpha))``; 0 for ``const`` and ``delta``): the unit ``include/gpk.h`` states the accuracy
 of the fused kernel-matrix kernels in.
 
-The kernel-gradient reference of ``tests/vjp_reference.py`` is extended by linearity: every output of ``gpk_kmat_vjp_s`` /
-``gpk_kmat_vjp_dense_s`` is a sum over terms, so the reference of a term list with Delta terms is that module's reference of the other
+The kernel-gradient reference of ``tests/vjp_reference.py`` is extended by linearity: every output of ``gpk_kmat_vjp`` /
+``gpk_kmat_vjp_dense`` is a sum over terms, so the reference of a term list with Delta terms is that module's reference of the other
 terms plus the Delta terms' own contribution from the formulas in ``include/gpk.h`` -- ``S1_t = sum G kappa_t``, ``S2_t = S3_t = 0``,
 ``v_t kappa_t`` in ``colsum``, nothing in ``gradx``.
 

@@ -73,6 +73,7 @@ def test_bad_and_learnable_epsilon_are_refused():
 def test_kterms_validate_epsilon():
     t = ops.KTerms([("eq", 1.0, 2.0), ("delta", 0.1, 1.0)], [None, 1e-6])
     assert t.shapes == [None, 1e-6] and list(t.c_shapes()) == [0.0, 1e-6]
+    assert ops.KTerms([("eq", 1.0, 1.0)]).c_shapes() is None           # no shaped term: the library gets NULL
     assert list(t.c_arrays()[0]) == [_native.K_EQ, _native.K_DELTA] and _native.K_DELTA == 7
     assert "delta" in ops._SHAPED and "delta" not in ops._LEARNABLE_SHAPE
     for bad in ([0.0], [-1e-6], [None], None):
@@ -227,15 +228,15 @@ def test_abi_codes_of_the_delta_kind():
         kdiag_tail = (None, n, d, 0, d, None, n, 1, None)
         vjp_tail = (None, n, d, d, None, n, None, 1, 1, one, None, None, None)
         dense_tail = (None, n, d, None, m, d, d, None, m, None, None, None, None, None, None, None)
-        assert lib.gpk_kmat(dt, kind, one, one, 1, *kmat_tail) == -1
-        assert lib.gpk_kdiag(dt, kind, one, one, 1, *kdiag_tail) == -1
-        assert lib.gpk_kmat_vjp(dt, kind, one, 1, *vjp_tail) == -1
-        assert lib.gpk_kmat_vjp_dense(dt, kind, one, one, 1, *dense_tail) == -1
-        assert lib.gpk_kmat_s(dt, kind, one, one, None, 1, *kmat_tail) == -1            # no shapes array at all
+        # a Delta term and no shapes array at all: no epsilon was given
+        assert lib.gpk_kmat(dt, kind, one, one, None, 1, *kmat_tail) == -1
+        assert lib.gpk_kdiag(dt, kind, one, one, None, 1, *kdiag_tail) == -1
+        assert lib.gpk_kmat_vjp(dt, kind, one, None, 1, *vjp_tail) == -1
+        assert lib.gpk_kmat_vjp_dense(dt, kind, one, one, None, 1, *dense_tail) == -1
         for b in (bad, neg):
-            assert lib.gpk_kmat_s(dt, kind, one, one, b, 1, *kmat_tail) == -5
-            assert lib.gpk_kdiag_s(dt, kind, one, one, b, 1, *kdiag_tail) == -5
-            assert lib.gpk_kmat_vjp_s(dt, kind, one, b, 1, *vjp_tail) == -5
-            assert lib.gpk_kmat_vjp_dense_s(dt, kind, one, one, b, 1, *dense_tail) == -5
+            assert lib.gpk_kmat(dt, kind, one, one, b, 1, *kmat_tail) == -5
+            assert lib.gpk_kdiag(dt, kind, one, one, b, 1, *kdiag_tail) == -5
+            assert lib.gpk_kmat_vjp(dt, kind, one, b, 1, *vjp_tail) == -5
+            assert lib.gpk_kmat_vjp_dense(dt, kind, one, one, b, 1, *dense_tail) == -5
         # an empty problem is fine whatever the table says (nothing to do), as for every other kind
-        assert lib.gpk_kmat_s(dt, kind, one, one, eps, 1, None, 0, d, 0, None, m, d, 0, d, None, m, 0, 1, 0, 0, 0.0, None, 0, 0, None) == 0
+        assert lib.gpk_kmat(dt, kind, one, one, eps, 1, None, 0, d, 0, None, m, d, 0, d, None, m, 0, 1, 0, 0, 0.0, None, 0, 0, None) == 0

@@ -177,14 +177,14 @@ def test_kmat_s_without_rq_terms_is_bit_identical_to_kmat(hip_backend, dtype):
     p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
     for sh in (shapes, None):
         got.fill_(-1.0)
-        code = hip_backend.lib.gpk_kmat_s(_native.GPK_F64 if dtype == torch.float64 else _native.GPK_F32, kinds, var, ils, sh, nt,
-                                          p(x), n, d, 0, p(x), n, d, 0, d, p(got), got.stride(0), 0, 1, 0, 1, 0.1, None, 0, 0,
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        code = hip_backend.lib.gpk_kmat(_native.GPK_F64 if dtype == torch.float64 else _native.GPK_F32, kinds, var, ils, sh, nt,
+                                        p(x), n, d, 0, p(x), n, d, 0, d, p(got), got.stride(0), 0, 1, 0, 1, 0.1, None, 0, 0,
+                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         assert code == 0
         assert torch.equal(got, want)
-    # ... and an RQ term through the entry without shapes is an argument error, not a silent alpha
+    # ... and an RQ term without a shapes array is an argument error, not a silent alpha
     rq = (ctypes.c_int * 1)(_native.K_RQ)
-    code = hip_backend.lib.gpk_kmat(_native.GPK_F64 if dtype == torch.float64 else _native.GPK_F32, rq, var, ils, 1, p(x), n, d, 0,
+    code = hip_backend.lib.gpk_kmat(_native.GPK_F64 if dtype == torch.float64 else _native.GPK_F32, rq, var, ils, None, 1, p(x), n, d, 0,
                                     p(x), n, d, 0, d, p(got), got.stride(0), 0, 1, 0, 1, 0.1, None, 0, 0,
                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert code < 0

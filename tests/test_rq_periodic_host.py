@@ -165,6 +165,7 @@ def test_rq_term_algebra():
 def test_kterms_shapes():
     t = ops.KTerms([("rq", 1.0, 2.0), ("eq", 1.0, 1.0)], [0.5, None])
     assert t.shapes == [0.5, None] and list(t.c_shapes()) == [0.5, 0.0] and t.terms == [("rq", 1.0, 2.0), ("eq", 1.0, 1.0)]
+    assert ops.KTerms([("eq", 1.0, 1.0)]).c_shapes() is None
     assert ops.KTerms([("eq", 1.0, 1.0)]).shapes is None and ops.KTerms([("eq", 1.0, 1.0)], [None]).shapes is None
     for bad in ([0.0], [-1.0], [None], None):
         with pytest.raises(ValueError, match="positive shape"):
@@ -214,9 +215,16 @@ def test_abi_of_the_entries_with_shapes():
 
         g.build()
     lib = _native.load()
-    assert lib.gpk_version() >= 102
-    for name in ("gpk_kmat_s", "gpk_kdiag_s", "gpk_kmat_vjp_s", "gpk_kmat_vjp_dense_s"):
-        assert re.search(r"\b" + name + r"\s*\(", text), f"{name} is not declared in include/gpk.h"
-        assert name in _native.SIGNATURES and hasattr(lib, name)
-        base = name[:-2]
-        assert len(_native.SIGNATURES[name][1]) == len(_native.SIGNATURES[base][1]) + 1      # one more host array: the shapes
+    assert lib.gpk_version() >= 104
+    with open(os.path.join(ROOT, "include", "gpk.h")) as f:
+        whole = f.read()
+    # one entry per operation: `shapes` directly behind `inv_ls` (kinds, [variances,] inv_ls, shapes, nterms), no twin with a suffix
+    for base, at in (("gpk_kmat", 4), ("gpk_kdiag", 4), ("gpk_kmat_vjp", 3), ("gpk_kmat_vjp_dense", 4)):
+        old = base + "_s"
+        assert not re.search(r"\b" + old + r"\b", whole), f"{old} is still named in include/gpk.h"
+        assert old not in _native.SIGNATURES and not hasattr(lib, old)
+        decl = re.search(r"\b" + base + r"\s*\(([^)]*)\)", text).group(1).split(",")
+        assert decl[at - 1].split()[-1] == "inv_ls" and decl[at].split() == ["const", "double*", "shapes"], decl[: at + 2]
+        argtypes = _native.SIGNATURES[base][1]
+        assert argtypes[at - 1] is _native._p_dbl and argtypes[at] is _native._p_dbl and argtypes[at + 1] is _native._c_int
+        assert len(argtypes) == len(decl) and hasattr(lib, base)

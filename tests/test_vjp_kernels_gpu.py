@@ -1,4 +1,4 @@
-"""The kernel-gradient kernels (``gpk_kmat_vjp``, ``gpk_kmat_vjp_dense`` and their ``_s`` forms, ``stheno_amd/csrc/gpk_vjp.hip``) called
+"""The kernel-gradient kernels (``gpk_kmat_vjp``, ``gpk_kmat_vjp_dense``, with and without shaped terms; ``stheno_amd/csrc/gpk_vjp.hip``) called
 directly through ``HipBackend.kmat_vjp`` / ``kmat_vjp_dense`` and compared element by element with the extended-precision reference of
 ``tests/vjp_reference.py``, in fp64 and fp32, at the tile, chunk and dimension edges.
 
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from stheno_amd import ops
+from stheno_amd import _native, ops
 
 from . import vjp_reference as R
 
@@ -133,3 +133,57 @@ def test_gradx_past_eight_dimensions_is_refused(hip_backend, dtype):
         hip_backend.kmat_vjp_dense(ops.KTerms([("eq", 1.0, 1.0)]), x, y, g, want_gradx=True)
     S, _, gx = hip_backend.kmat_vjp_dense(ops.KTerms([("eq", 1.0, 1.0)]), x, y, g, want_gradx=False)
     assert gx is None and float(S[0, 0]) == 35.0
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_unshaped_terms_take_the_two_wide_rows_whatever_shapes_holds(hip_backend, dtype):
+    """The launchers choose the instantiation from the term table, not from ``shapes``: with kinds that have no shape parameter a junk
+    ``shapes`` array and ``NULL`` write the same bits into partial rows of ``2 * GPK_MAX_TERMS + 1`` elements, and nothing behind them
+    (``partial`` is sized for the 3-wide rows and prefilled, so a launch of the shaped kernels would show in its tail)."""
+    lib, T = hip_backend.lib, DTYPES[dtype]
+    terms = ops.KTerms([("eq", 0.8, 1.1), ("linear", 0.5, 2.0)])
+    kinds, var, ils, nt = terms.c_arrays()
+    junk = (ctypes.c_double * 2)(7.0, 7.0)
+    dt = _native.GPK_F64 if T == torch.float64 else _native.GPK_F32
+    n = m = 65
+    d, W2, W3, sentinel = 3, 2 * _native.MAX_TERMS + 1, 3 * _native.MAX_TERMS + 1, -12345.0
+    rng = np.random.default_rng(11)
+    x, y = (torch.as_tensor(rng.standard_normal((k, d)), dtype=T, device="cuda") for k in (n, m))
+    kinv, g = (torch.as_tensor(rng.standard_normal(sh), dtype=T, device="cuda") for sh in ((n, n), (n, m)))
+    alpha = torch.as_tensor(rng.standard_normal((n, 1)), dtype=T, device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    bits = lambda t: t.cpu().view(torch.int64 if T == torch.float64 else torch.int32)   # noqa: E731
+    one = (ctypes.c_double * 1)(1.0)
+
+    # log-density form: two 64-row tiles, 3 blocks of the lower triangle
+    rows = int(lib.gpk_kmat_vjp_blocks(n))
+    assert rows == 3
+    got = []
+    for sh in (junk, None):
+        partial = torch.full((rows * W3,), sentinel, dtype=T, device="cuda")
+        diag_g = torch.empty((n,), dtype=T, device="cuda")
+        assert lib.gpk_kmat_vjp(dt, kinds, ils, sh, nt, p(x), n, d, d, p(kinv), n, p(alpha), 1, 1, one, p(partial), p(diag_g), stream) == 0
+        assert bool((partial[rows * W2:] == sentinel).all()), "something was written behind the 2-wide rows"
+        head = partial[: rows * W2].reshape(rows, W2)
+        assert bool((head[:, : 2 * nt] != sentinel).all()) and bool((head[:, W2 - 1] != sentinel).all())     # sums and trace were written
+        got.append((bits(partial), bits(diag_g)))
+    assert all(torch.equal(a, b) for a, b in zip(*got))
+
+    # explicit-cotangent form: 2 row tiles x 2 chunks
+    rt, nc = ctypes.c_int64(), ctypes.c_int64()
+    assert lib.gpk_kmat_vjp_dense_grid(n, m, ctypes.byref(rt), ctypes.byref(nc)) == 0
+    rt, nc = rt.value, nc.value
+    assert (rt, nc) == (2, 2)
+    rows = rt * nc
+    got = []
+    for sh in (junk, None):
+        partial = torch.full((rows * W3,), sentinel, dtype=T, device="cuda")
+        colsum = torch.full((rt, m), sentinel, dtype=T, device="cuda")
+        gradx = torch.full((nc, n, d), sentinel, dtype=T, device="cuda")
+        assert lib.gpk_kmat_vjp_dense(dt, kinds, var, ils, sh, nt, p(x), n, d, p(y), m, d, d, p(g), m, None, None, None,
+                                      p(partial), p(colsum), p(gradx), stream) == 0
+        assert bool((partial[rows * W2:] == sentinel).all()), "something was written behind the 2-wide rows"
+        assert bool((partial[: rows * W2] != sentinel).all()) and bool((colsum != sentinel).all()) and bool((gradx != sentinel).all())
+        got.append((bits(partial), bits(colsum), bits(gradx)))
+    assert all(torch.equal(a, b) for a, b in zip(*got))

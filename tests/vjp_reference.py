@@ -1,5 +1,5 @@
-"""Extended-precision reference of the two kernel-gradient operations (``gpk_kmat_vjp`` / ``gpk_kmat_vjp_dense`` and their ``_s``
-forms), the cases both test modules run, and the inputs of each case.  Not collected by pytest.
+"""Extended-precision reference of the two kernel-gradient operations (``gpk_kmat_vjp`` / ``gpk_kmat_vjp_dense``, with and without
+shaped terms), the cases both test modules run, and the inputs of each case.  Not collected by pytest.
 
 The reference is written from the formulas in ``include/gpk.h`` in ``np.longdouble`` and works in blocks of at most 256 rows.  For
 every output element it returns the value and ``absum``: the sum of the absolute values of everything the kernels add up for that
