@@ -59,7 +59,8 @@ extern "C" {
 
 #define GPK_DIAG_BLOCK 128 /* order of the diagonal blocks whose inverses gpk_potrf leaves in `dinv` */
 
-/* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104. */
+/* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
+ * 105: gpk_kmat_diff. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -96,6 +97,41 @@ int gpk_kmat(int dtype, const int* kinds, const double* variances, const double*
              int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
              int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
              void* stream);
+
+/* Derivative blocks of the kernel matrix: dim_x >= 0 differentiates w.r.t. x[:, dim_x], dim_y >= 0 w.r.t. y[:, dim_y]; -1: not.
+ * At least one of them is >= 0 (both -1: the argument error for dim_x -- gpk_kmat is the call for that).
+ *   out[i][j] (+)= d/dx_i[a] k(x_i, y_j)   |   d/dy_j[b] k(x_i, y_j)   |   d^2/dx_i[a] dy_j[b] k(x_i, y_j),      k = sum_t variances[t] kappa_t
+ * -- the covariance of a process with its derivative and of two derivatives.  Replaces mlkernels `DerivativeKernel` (autodiff through
+ * `pairwise`) behind `GP.diff`: stheno/model/measure.py:343-360 (mean, kernel and left rule of the derivative process).
+ * Everything from `x` on is gpk_kmat's argument list with gpk_kmat's meaning (leading dimensions, batch strides, lower_only,
+ * diag_add / diag_vec on i == j of a symmetric launch, accumulate).
+ *   Formulas.  A stationary term is v kappa(q), q = c |x - y|^2, c = inv_ls^2; with D_a = x[a] - y[a]:
+ *     d/dx_a = 2 c v kappa'(q) D_a,    d/dy_b = -2 c v kappa'(q) D_b,    d^2/dx_a dy_b = v (-4 c^2 kappa''(q) D_a D_b - 2 c kappa'(q) [a == b])
+ *     GPK_K_EQ         kappa' = -kappa / 2                        kappa'' = kappa / 4
+ *     GPK_K_RQ         kappa' = -(1 + u)^(-alpha - 1) / 2         kappa'' = (alpha + 1) / (4 alpha) (1 + u)^(-alpha - 2),  u = q / (2 alpha)
+ *     GPK_K_MATERN52   kappa' = -(5/6) (1 + s) e^(-s)             kappa'' = (25/12) e^(-s),                                 s = sqrt(5 q)
+ *     GPK_K_MATERN32   kappa' = -(3/2) e^(-s)                     kappa'' = 9 / (4 s) e^(-s),                               s = sqrt(3 q)
+ *     GPK_K_LINEAR (c v <x, y>):  d/dx_a = c v y[a],   d/dy_b = c v x[b],   d^2/dx_a dy_b = c v [a == b];      GPK_K_CONST: 0.
+ *   RQ's powers are exp(-(alpha + 1) log1p(u)) and exp(-(alpha + 2) log1p(u)): every exponent on this path is <= 0, as in gpk_kmat.
+ *   Matern32's kappa'' D_a D_b tends to 0 with the distance (|D_a D_b| <= |x - y|^2): at coincident points the second derivative is
+ *   exactly -2 c v kappa'(0) [a == b] and the one-sided derivatives of every stationary table are exactly 0, in both dtypes; NaN inputs
+ *   give NaN values in their row / column only.  GPK_K_MATERN12 and GPK_K_DELTA are not differentiable and are refused.
+ *   Numerics: squared distances and D_a, D_b from direct differences; element by element within a few eps of
+ *   sum_t |v_t| (|first addend| + |second addend|) (1 + |argument of the exponential|) (csrc/selftest.cpp, `--diff`; tests/test_diff_gpu.py).
+ *   Two launch shapes like gpk_kmat: the row-band walk for d <= 8, the chunked one-tile kernel beyond; one term-table program.
+ *   Every argument is checked before an empty problem (n, m or batch <= 0) returns 0.  Returns -k for argument k:
+ *     -6  nterms outside 0 .. GPK_MAX_TERMS;      -2  a kind without a derivative (GPK_K_MATERN12, GPK_K_DELTA) or an unknown kind;
+ *     `shapes` exactly as for gpk_kmat (it may be NULL exactly when no term is GPK_K_RQ): -1 for a GPK_K_RQ term with shapes == NULL -- the
+ *         one code here that is no argument position, kept equal to the sibling entry's --, -5 for an alpha <= 0;
+ *     -17 d < 0;      -7  dim_x outside [-1, d), or dim_x and dim_y both -1;      -8  dim_y outside [-1, d);
+ *     -23 `symmetric` or `lower_only` set although dim_x != dim_y or one of them is -1 (the one-sided blocks are not symmetric, and the
+ *         mixed block of two different dimensions is not either);
+ *     -10 / -14 / -21  n (more than 2^31 - 1 rows, or more than 65535 row tiles of 32), m, batch (> 65535) too large. */
+int gpk_kmat_diff(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                  int dim_x, int dim_y, const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
+                  int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
+                  int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
+                  void* stream);
 
 /* Kernel diagonal  out[i] = k(x_i, x_i).  Replaces mlkernels `elwise`:
  * stheno/model/fdd.py:66, stheno/model/observations.py:304.
@@ -411,7 +447,7 @@ int gpk_mfma_peak(int dtype, double min_ms, int waves_per_simd, double* tflops, 
  * (`gpk_selftest --set KEY VALUE`).  key 1: use 64x64 GEMM tiles below this many 128-tiles; 6: look-ahead overlaps while the
  * trailing matrix has at least this many rows; 7: 0 = look-ahead algorithm on one stream, 1 = with the helper stream; 8: the
  * persistent update takes 64x64 tiles below this many 128-tiles; 9: gpk_potrf_la finishes the last this-many rows with the plain
- * algorithm (0 = 6144); 12: 1 = row-band kernel-matrix kernel, 0 = one tile per workgroup; 17: 1 = one-workgroup-per-matrix TRSV
+ * algorithm (0 = 6144); 12: 1 = row-band kernel-matrix kernel, 0 = one tile per workgroup (gpk_kmat and gpk_kmat_diff); 17: 1 = one-workgroup-per-matrix TRSV
  * for batches of small factors; 20: gpk_tune_tile_prof stamps only the v-th persistent launch since this knob was set (-1 = every launch); 31: quarter tiles for
  * the last partial round of a 128-tile GEMM launch; 32: fused panel-step kernel (batched / fallback path); 34: compact 1-D grid for
  * lower-triangle kernel matrices; 36: triangular-operand fragment skipping in panel solves; 37: 1 = one pipelined launch per panel

@@ -5,7 +5,7 @@ kernels (``stheno_amd/csrc``, C ABI in ``include/gpk.h``) behind the ``stheno.to
 API surface for that path (``stheno/__init__.py:1-28``)."""
 from . import B  # noqa: F401
 from .kernels import (  # noqa: F401
-    EQ, RQ, Delta, Exp, Kernel, Linear, Matern12, Matern32, Matern52, OneKernel, OneMean, Periodic, PosteriorKernel,
+    EQ, RQ, Delta, DiffKernel, DiffMean, Exp, Kernel, Linear, Matern12, Matern32, Matern52, OneKernel, OneMean, Periodic, PosteriorKernel,
     PosteriorMean, SubspaceKernel, ZeroKernel, ZeroMean,
 )
 from .lazy import LazyMatrix, LazyVector  # noqa: F401

@@ -34,6 +34,13 @@ SIGNATURES = {
          _c_i64, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
          _c_ptr],
     ),
+    # (dim_x, dim_y between nterms and x; everything from x on as gpk_kmat)
+    "gpk_kmat_diff": (
+        _c_int,
+        [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_int, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
+         _c_i64, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
+         _c_ptr],
+    ),
     "gpk_kdiag": (
         _c_int,
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64,

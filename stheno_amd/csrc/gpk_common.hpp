@@ -192,6 +192,7 @@ void gpk_prof_end(void* slot, hipStream_t stream);
 void gpk_tune_gemm(int key, int64_t value);
 void gpk_tune_potrf(int key, int64_t value);
 void gpk_tune_kmat(int key, int64_t value);
+void gpk_tune_kdiff(int key, int64_t value);
 void gpk_tune_solve(int key, int64_t value);
 void gpk_set_diag_prof(long long* dev_buf);
 void gpk_set_tile_prof(long long* dev_buf);
@@ -257,6 +258,13 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
                     hipStream_t stream);
+// derivative blocks of the kernel matrix (gpk_kmat_diff in gpk.h; gpk_kdiff.hip): status codes are that entry's argument positions
+template <typename T>
+int gpk_kmat_diff_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                         int dim_x, int dim_y, const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
+                         int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
+                         int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
+                         hipStream_t stream);
 template <typename T>
 int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                      const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,

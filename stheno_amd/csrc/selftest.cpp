@@ -5,6 +5,7 @@
 //     ./gpk_selftest --perf     + timings (HIP events) of the hot kernels
 //     ./gpk_selftest --rq       only the checks of the term kind with a shape parameter (rational quadratic)
 //     ./gpk_selftest --delta    only the checks of the Delta term kind
+//     ./gpk_selftest --diff     only the checks of the derivative blocks of the kernel matrix (gpk_kmat_diff)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -1202,6 +1203,156 @@ static void test_rq() {
 }
 
 // ----------------------------------------------------------------------------
+// Derivative blocks of the kernel matrix (gpk_kmat_diff)   --diff
+// ----------------------------------------------------------------------------
+// Element by element against the closed forms of include/gpk.h in long double, on the inputs as the dtype holds them:
+// |got - ref| <= DIFF_TOL eps absum, absum = sum_t |v_t| (|first addend| + |second addend|) (1 + |argument of the exponential|).
+// DIFF_TOL = 8: ~2.5 eps (1 + |arg|) for an exponential (gpk_kmat's own figure), one rounding each for the scaled distance, the
+// difference D_a, the products with c, v and the profile's constant, and the sum over terms.
+static const double DIFF_TOL = 8.0;
+struct DiffTable { const char* name; int nt; int kinds[8]; double var[8], scale[8], shape[8]; bool shaped; };
+static const DiffTable DIFF_TABLES[] = {
+    {"eq", 1, {GPK_K_EQ}, {1.5}, {0.75}, {0}, false},
+    {"matern32", 1, {GPK_K_MATERN32}, {0.75}, {1.25}, {0}, false},
+    {"rq0.7", 1, {GPK_K_RQ}, {1.25}, {1.5}, {0.7}, true},
+    {"eq+linear+const", 3, {GPK_K_EQ, GPK_K_LINEAR, GPK_K_CONST}, {1.0, 0.5, 0.25}, {1.5, 2.0, 1.0}, {0, 0, 0}, false},
+    {"all8", 8, {GPK_K_EQ, GPK_K_MATERN32, GPK_K_MATERN52, GPK_K_RQ, GPK_K_LINEAR, GPK_K_CONST, GPK_K_EQ, GPK_K_RQ},
+     {1.0, 0.5, 0.75, 1.25, 0.25, 2.0, 0.5, 0.375}, {1.0, 2.0, 1.5, 0.75, 4.0, 1.0, 3.0, 2.5}, {0, 0, 0, 0.7, 0, 0, 0, 3.0}, true},
+};
+// value and absum of one element; mode 0: d/dx_a, 1: d/dy_b, 2: d2/dx_a dy_b
+template <typename T>
+static void diff_ref(const DiffTable& tb, const T* x, const T* y, int d, int a, int b, int mode, long double* val, long double* absum) {
+    long double r2 = 0;
+    for (int k = 0; k < d; ++k) { const long double df = (long double)x[k] - (long double)y[k]; r2 += df * df; }
+    const long double da = a >= 0 ? (long double)x[a] - (long double)y[a] : 0, db = b >= 0 ? (long double)x[b] - (long double)y[b] : 0;
+    long double v = 0, ab = 0;
+    for (int t = 0; t < tb.nt; ++t) {
+        const long double il = (long double)(1.0 / tb.scale[t]), c = il * il, var = tb.var[t], q = c * r2;
+        long double k1 = 0, k2dd = 0, arg = 0;
+        switch (tb.kinds[t]) {
+            case GPK_K_CONST: continue;
+            case GPK_K_LINEAR: {
+                const long double term = mode == 0 ? c * var * (long double)y[a] : mode == 1 ? c * var * (long double)x[b] : (a == b ? c * var : 0);
+                v += term; ab += fabsl(term);
+                continue;
+            }
+            case GPK_K_EQ: { const long double e = expl(-q / 2); k1 = -e / 2; k2dd = e / 4 * da * db; arg = q / 2; break; }
+            case GPK_K_RQ: {
+                const long double al = tb.shape[t], l = log1pl(q / (2 * al));
+                k1 = -expl(-(al + 1) * l) / 2; k2dd = (al + 1) / (4 * al) * expl(-(al + 2) * l) * da * db; arg = (al + 2) * l; break;
+            }
+            case GPK_K_MATERN52: { const long double sd = sqrtl(5 * q), e = expl(-sd); k1 = -5.0L / 6 * (1 + sd) * e; k2dd = 25.0L / 12 * e * da * db; arg = sd; break; }
+            default: { const long double sd = sqrtl(3 * q), e = expl(-sd); k1 = -1.5L * e; k2dd = sd > 0 ? 2.25L * e * da * db / sd : 0; arg = sd; break; }
+        }
+        long double first, second = 0;
+        if (mode == 0) first = 2 * c * var * k1 * da;
+        else if (mode == 1) first = -2 * c * var * k1 * db;
+        else { first = -4 * c * c * var * k2dd; second = a == b ? -2 * c * var * k1 : 0; }
+        v += first + second;
+        ab += (fabsl(first) + fabsl(second)) * (1 + arg);
+    }
+    *val = v; *absum = ab;
+}
+template <typename T>
+static void test_diff() {
+    const double eps = (double)std::numeric_limits<T>::epsilon();
+    for (int band = 1; band >= 0; --band) {
+        gpk_tune(12, band);
+        const char* kn = band ? "row-band" : "tile";
+        for (const DiffTable& tb : DIFF_TABLES) {
+            double ils[8];
+            for (int t = 0; t < tb.nt; ++t) ils[t] = 1.0 / tb.scale[t];
+            for (int d : {1, 3, 8, 9}) {                   // (d = 9: past one staged chunk -- the tile kernel whatever the knob says)
+                double worst[3] = {0, 0, 0};
+                int status = 0;
+                size_t nonzero_coincident = 0, nans = 0;
+                for (int shape = 0; shape < 3; ++shape) {
+                    const int n = shape == 0 ? 1 : shape == 1 ? 33 : 97, m = shape == 0 ? 1 : shape == 1 ? 65 : 259;
+                    auto X = randv<T>((size_t)n * d, 1.0 / sqrt((double)d)), Y = randv<T>((size_t)m * d, 1.0 / sqrt((double)d));
+                    for (int j = 0; j < m; j += 5) for (int k = 0; k < d; ++k) Y[(size_t)j * d + k] = X[(size_t)((j * 7) % n) * d + k];      // coincident points
+                    Dev<T> dX(X.size()), dY(Y.size()), dO((size_t)n * m);
+                    dX.up(X); dY.up(Y);
+                    const int dimsets[4][2] = {{0, 0}, {d - 1, 0}, {0, d - 1}, {d - 1, d - 1}};
+                    for (int ds = 0; ds < (d > 1 ? 4 : 1); ++ds)
+                        for (int mode = 0; mode < 3; ++mode) {
+                            const int a = mode == 1 ? -1 : dimsets[ds][0], b = mode == 0 ? -1 : dimsets[ds][1];
+                            status |= gpk_kmat_diff(DT<T>::v, tb.kinds, tb.var, ils, tb.shaped ? tb.shape : nullptr, tb.nt, a, b, dX.p, n, d, 0, dY.p, m, d, 0, d,
+                                                    dO.p, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+                            HIPCHK(hipDeviceSynchronize());
+                            auto got = dO.down();
+                            for (int i = 0; i < n; ++i)
+                                for (int j = 0; j < m; ++j) {
+                                    long double v, ab;
+                                    diff_ref<T>(tb, &X[(size_t)i * d], &Y[(size_t)j * d], d, a, b, mode, &v, &ab);
+                                    const long double g = got[(size_t)i * m + j];
+                                    if (g != g) { ++nans; continue; }
+                                    const double e = ab > 0 ? (double)(fabsl(g - v) / ab) / eps : (g == 0 ? 0.0 : INFINITY);
+                                    worst[mode] = std::max(worst[mode], e);
+                                    // one-sided blocks of a stationary table are exactly 0 at coincident points
+                                    if (mode < 2 && j % 5 == 0 && i == (j * 7) % n && strcmp(tb.name, "eq+linear+const") && strcmp(tb.name, "all8")) nonzero_coincident += g != 0;
+                                }
+                        }
+                }
+                char nm[200];
+                snprintf(nm, sizeof nm, "kmat_diff_%s %s %s d%d: worst |err| / (eps absum) dx %.2f dy %.2f dxy %.2f (%zu NaN, %zu nonzero coincident) st%d", DT<T>::name(), tb.name, kn,
+                         d, worst[0], worst[1], worst[2], nans, nonzero_coincident, status);
+                report(nm, (status || nans || nonzero_coincident) ? INFINITY : std::max(worst[0], std::max(worst[1], worst[2])), DIFF_TOL);
+            }
+        }
+        // symmetric, lower-only, diag_add + diag_vec, n = 130: the lower triangle bit for bit the full launch's, skipped tiles untouched
+        for (int d : {3, 9}) {
+            const DiffTable& tb = DIFF_TABLES[4];
+            double ils[8];
+            for (int t = 0; t < tb.nt; ++t) ils[t] = 1.0 / tb.scale[t];
+            const int n = 130, a = d - 1;
+            auto X = randv<T>((size_t)n * d, 1.0 / sqrt((double)d));
+            std::vector<T> dv(n);
+            for (int i = 0; i < n; ++i) dv[i] = (T)((i % 16) / 8.0);
+            Dev<T> dX(X.size()), dV(n), dF((size_t)n * n), dL((size_t)n * n);
+            dX.up(X); dV.up(dv);
+            std::vector<T> fill((size_t)n * n, (T)-7);
+            dL.up(fill);
+            int st = gpk_kmat_diff(DT<T>::v, tb.kinds, tb.var, ils, tb.shape, tb.nt, a, a, dX.p, n, d, 0, dX.p, n, d, 0, d, dF.p, n, 0, 1, 0, 1, 0.25, dV.p, 0, 0, nullptr);
+            st |= gpk_kmat_diff(DT<T>::v, tb.kinds, tb.var, ils, tb.shape, tb.nt, a, a, dX.p, n, d, 0, dX.p, n, d, 0, d, dL.p, n, 0, 1, 1, 1, 0.25, dV.p, 0, 0, nullptr);
+            HIPCHK(hipDeviceSynchronize());
+            auto full = dF.down(), low = dL.down();
+            size_t bad = 0;
+            double worst = 0;
+            const int TN = 64 * (16 / (int)sizeof(T));
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) {
+                    if (j <= i) bad += memcmp(&full[(size_t)i * n + j], &low[(size_t)i * n + j], sizeof(T)) != 0;
+                    else if ((j / TN) * TN > (i / 32) * 32 + 31) bad += low[(size_t)i * n + j] != (T)-7;      // a skipped tile
+                    long double v, ab;
+                    diff_ref<T>(tb, &X[(size_t)i * d], &X[(size_t)j * d], d, a, a, 2, &v, &ab);
+                    if (i == j) { v += 0.25L + (long double)dv[i]; ab += 0.25L + (long double)dv[i]; }
+                    worst = std::max(worst, (double)(fabsl((long double)full[(size_t)i * n + j] - v) / ab) / eps);
+                }
+            char nm[200];
+            snprintf(nm, sizeof nm, "kmat_diff_%s all8 %s d%d symmetric n130 + diag: %zu lower-only mismatches st%d", DT<T>::name(), kn, d, bad, st);
+            report(nm, (st || bad) ? INFINITY : worst, DIFF_TOL);
+        }
+    }
+    gpk_tune(12, 1);
+    {   // the argument codes (include/gpk.h)
+        int eq = GPK_K_EQ, m12 = GPK_K_MATERN12, rq = GPK_K_RQ;
+        double one = 1.0, zero = 0.0;
+        Dev<T> dX(8), dO(16);
+        auto call = [&](const int* kind, const double* shapes, int nt, int a, int b, int d, int lower, int sym) {
+            return gpk_kmat_diff(DT<T>::v, kind, &one, &one, shapes, nt, a, b, dX.p, 2, d, 0, dX.p, 2, d, 0, d, dO.p, 2, 0, 1, lower, sym, 0.0, nullptr, 0, 0, nullptr);
+        };
+        const int got[] = {call(&m12, nullptr, 1, 0, 0, 2, 0, 0), call(&rq, nullptr, 1, 0, 0, 2, 0, 0), call(&rq, &zero, 1, 0, 0, 2, 0, 0), call(&eq, nullptr, 9, 0, 0, 2, 0, 0),
+                           call(&eq, nullptr, 1, 2, 0, 2, 0, 0), call(&eq, nullptr, 1, -1, -1, 2, 0, 0), call(&eq, nullptr, 1, 0, 2, 2, 0, 0),
+                           call(&eq, nullptr, 1, 0, 1, 2, 0, 1), call(&eq, nullptr, 1, 0, -1, 2, 1, 0), call(&eq, nullptr, 1, 1, 1, 2, 1, 1)};
+        const int want[] = {-2, -1, -5, -6, -7, -7, -8, -23, -23, 0};
+        HIPCHK(hipDeviceSynchronize());
+        int bad = 0;
+        for (int i = 0; i < 10; ++i) bad += got[i] != want[i];
+        report(std::string("kmat_diff_") + DT<T>::name() + " argument codes", (double)bad, 0.0);
+    }
+}
+
+// ----------------------------------------------------------------------------
 // Delta: 1 where the scaled squared distance is below epsilon, else 0 (epsilon in `shapes` of gpk_kmat / gpk_kdiag and the VJP entries)   --delta
 // ----------------------------------------------------------------------------
 // Inputs are small integers over 4 with rows of y copied from x: every squared distance is 0 or at least 1/16, computed without
@@ -1810,6 +1961,29 @@ static void perf_kmat() {
     const double eqds[2] = {0.0, 1e-6};
     perf_kmat_case<double>("N=16384 D=8 EQ+Delta lower", 2, eqd, 16384, 0, 8, 1, 1, 0, eqds);
     perf_kmat_case<float>("N=16384 D=8 EQ+Delta lower", 2, eqd, 16384, 0, 8, 1, 1, 0, eqds);
+}
+
+// the mixed-derivative launch beside the plain kernel-matrix launch of the same shape (both write the same bytes)   --perf-diff
+template <typename T>
+static void perf_diff_case(int64_t n, int d, int lower) {
+    auto hx = randv<T>((size_t)n * d);
+    Dev<T> X(hx.size()), K((size_t)n * n);
+    X.up(hx);
+    int kind = GPK_K_EQ; double var = 1.0, il = 1.0;
+    Timer tm;
+    for (int which = 0; which < 2; ++which) {
+        float best = 1e30f;
+        for (int rep = 0; rep < 5; ++rep) {
+            tm.start();
+            if (which) gpk_kmat_diff(DT<T>::v, &kind, &var, &il, nullptr, 1, 0, 0, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, lower, 1, 0.1, nullptr, 0, 0, nullptr);
+            else gpk_kmat(DT<T>::v, &kind, &var, &il, nullptr, 1, X.p, n, d, 0, X.p, n, d, 0, d, K.p, n, 0, 1, lower, 1, 0.1, nullptr, 0, 0, nullptr);
+            const float ms = tm.stop();
+            if (rep) best = std::min(best, ms);
+        }
+        const double bytes = (lower ? 0.5 : 1.0) * (double)n * n * sizeof(T);
+        printf("PERFDIFF N=%lld D=%d EQ %s %s %-34s %.3f ms  %.2f TB/s\n", (long long)n, d, lower ? "lower" : "full ", DT<T>::name(),
+               which ? "gpk_kmat_diff d2/dx0 dy0" : "gpk_kmat (compile-time EQ program)", best, bytes / best * 1e-9);
+    }
 }
 
 // one problem, for rocprofv3: kmat + potrf (+ trsv, merge, trsm) at order n
@@ -2480,6 +2654,10 @@ int main(int argc, char** argv) {
         }
         if (!strcmp(argv[i], "--census")) { census(); return 0; }
         if (!strcmp(argv[i], "--perf-kmat")) { perf_kmat(); return 0; }
+        if (!strcmp(argv[i], "--perf-diff")) {                 // the derivative launch against the plain one, N = 16384, D = 8
+            for (int lower = 1; lower >= 0; --lower) { perf_diff_case<double>(16384, 8, lower); perf_diff_case<float>(16384, 8, lower); }
+            return 0;
+        }
         if (!strcmp(argv[i], "--perf-fill") && i + 1 < argc) {      // --perf-fill N: plain POTRF at N for several splits of the workers between panel tasks and fill tiles
             const int n = atoi(argv[i + 1]);
             for (int wg : {-1, 16, 32, 48, 64, 85, 128, 170}) {
@@ -2503,6 +2681,11 @@ int main(int argc, char** argv) {
         }
         if (!strcmp(argv[i], "--rq")) {                        // only the checks of the kind with a shape parameter (rational quadratic)
             test_rq<double>(); test_rq<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
+        if (!strcmp(argv[i], "--diff")) {                      // only the checks of the derivative blocks (gpk_kmat_diff), both kernels
+            test_diff<double>(); test_diff<float>();
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
@@ -2583,6 +2766,7 @@ int main(int argc, char** argv) {
         test_vjp_dense<double>(); test_vjp_dense<float>();
         test_rq<double>(); test_rq<float>();
         test_delta<double>(); test_delta<float>();
+        test_diff<double>(); test_diff<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

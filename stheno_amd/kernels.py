@@ -7,6 +7,8 @@ dependency that ``stheno/model/*.py`` uses:
   ``readme_example1_simple_regression.py``);
 * ``pairwise`` (``k(x, y)``) and ``elwise`` (``k.elwise(x)``) evaluation -- one fused HIP
   kernel launch per call for any sum of primitives (``gpk_kmat`` / ``gpk_kdiag``);
+* ``k.diff(dim)`` / ``m.diff(dim)`` (``DiffKernel``, ``DiffMean``; mlkernels' ``DerivativeKernel`` behind ``GP.diff``,
+  ``stheno/model/measure.py:343-360``): first derivatives in either argument, one fused launch per block (``gpk_kmat_diff``);
 * ``PosteriorKernel``, ``PosteriorMean``, ``SubspaceKernel`` (constructed at
   ``stheno/model/observations.py:148-168,256-277``) and ``mean_var`` / ``mean_var_diag``
   (``stheno/model/fdd.py:69,73``), which share one ``L^{-1} k(z, x)`` between the mean and
@@ -25,7 +27,7 @@ __all__ = [
     "Kernel", "EQ", "RQ", "Delta", "Periodic", "Exp", "Matern12", "Matern32", "Matern52", "Linear", "OneKernel", "ZeroKernel",
     "Mean", "ZeroMean", "OneMean", "PosteriorKernel", "PosteriorMean", "SubspaceKernel",
     "mean_var", "mean_var_diag", "uprank", "num_elements",
-    "MultiInput", "MultiOutputKernel", "MultiOutputMean", "InputScaled",
+    "MultiInput", "MultiOutputKernel", "MultiOutputMean", "InputScaled", "DiffKernel", "DiffMean",
 ]
 
 
@@ -233,6 +235,16 @@ class Kernel:
         """``k.periodic(p)``: ``k`` on ``(sin(2 pi x / p), cos(2 pi x / p))`` (mlkernels' ``Periodic``).  ``p``: a positive scalar,
         or one period per input dimension."""
         return Periodic(self, period)
+
+    def diff(self, *dims):
+        """``k.diff(dim)``: the derivative with respect to input dimension ``dim`` of BOTH arguments, ``d^2 k / dx[dim] dy[dim]`` -- the
+        kernel of ``f.diff(dim)``; ``k.diff(dim_x, dim_y)``: either may be ``None`` (that argument is not differentiated) --
+        ``k.diff(dim, None)`` is the covariance of ``f.diff(dim)`` with ``f``."""
+        if len(dims) == 1:
+            dims = (dims[0], dims[0])
+        if len(dims) != 2:
+            raise TypeError("diff(dim) or diff(dim_x, dim_y)")
+        return _diff_kernel(self, *(None if v is None else _as_dim(v) for v in dims))
 
     def __reversed__(self):
         # sums of (stretched / scaled) primitives are symmetric, the zero kernel included -- and so are they behind input maps
@@ -789,14 +801,155 @@ class Reversed(Kernel):
 
 
 # ---------------------------------------------------------------------------
+# derivatives (mlkernels' DerivativeKernel behind GP.diff: stheno/model/measure.py:343-360)
+# ---------------------------------------------------------------------------
+#: kinds the fused derivative launch knows, with the value of ``-2 kappa'(0)``: what ``d^2 k / dx_a dy_a`` is at coincident points per unit
+#: ``variance / scale^2`` (``include/gpk.h``, gpk_kmat_diff)
+_DIFF_AT_ZERO = {"eq": 1.0, "rq": 1.0, "matern32": 3.0, "matern52": 5.0 / 3.0, "linear": 1.0, "const": 0.0}
+
+
+class PosteriorDerivativeError(NotImplementedError):
+    """A posterior mean / kernel was asked for its derivative: differentiate the prior process, then look the derivative up under the
+    posterior (``post(f.diff())``)."""
+
+
+def _as_dim(v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+        raise ValueError(f"a derivative is taken with respect to an input dimension (a non-negative integer), got {v!r}")
+    return int(v)
+
+
+def _diff_kernel(k, a, b):
+    """``d k / dx[a] dy[b]`` (``None``: that argument as it is) as a kernel; refuses, loudly, what the derivative launch does not cover."""
+    if a is None and b is None:
+        return k
+    if isinstance(k, ZeroKernel):
+        return ZeroKernel()
+    if isinstance(k, DiffKernel):
+        if (a is not None and k.dim_x is not None) or (b is not None and k.dim_y is not None):
+            raise NotImplementedError("second derivatives in one argument (f.diff().diff()) are not implemented: they need the third and "
+                                      "fourth derivatives of the kernels' profiles")
+        return DiffKernel(k.k, k.dim_x if a is None else a, k.dim_y if b is None else b)
+    view = k.input_scaled_view()
+    if view is not None:
+        kern, imap = view
+        if isinstance(imap, _PeriodMap):
+            raise NotImplementedError("derivatives of kernels behind a periodic map are not implemented")
+        if imap is not None and not isinstance(imap, _ScaleMap):
+            raise NotImplementedError(f"derivatives behind the input map {type(imap).__name__} are not implemented")
+        bad = sorted({kind for kind, _, _ in kern.terms() if kind not in _DIFF_AT_ZERO})
+        if bad:
+            raise NotImplementedError(f"kernels of the kind {', '.join(bad)} are not differentiable (Matern12 has a kink at distance 0, "
+                                      "Delta is piecewise constant)")
+        return DiffKernel(k, a, b)
+    if isinstance(k, Sum):
+        if _map_groups(k) is not None:
+            raise NotImplementedError("derivatives of sums whose parts sit behind different input maps are not implemented")
+        return _diff_kernel(k.a, a, b) + _diff_kernel(k.b, a, b)
+    if isinstance(k, Scaled):
+        return k.v * _diff_kernel(k.k, a, b)
+    if isinstance(k, Reversed):
+        return reversed(_diff_kernel(k.k, b, a))
+    if isinstance(k, (PosteriorKernel, SubspaceKernel)):
+        raise PosteriorDerivativeError("derivatives of posterior kernels are not implemented: differentiate the prior process and look its "
+                                       "derivative up under the posterior (`post(f.diff())`)")
+    raise NotImplementedError(f"derivatives are not implemented for {type(k).__name__}")
+
+
+class DiffKernel(Kernel):
+    """``d k(x, y) / dx[dim_x] dy[dim_y]`` for a (symmetric) kernel ``k`` that is a sum of primitives, possibly behind per-dimension
+    length scales; ``None`` in a slot: not differentiated in that argument.  ``DiffKernel(k, a, b)`` is the covariance of
+    ``f.diff(a)`` with ``f.diff(b)``, ``DiffKernel(k, a, None)`` that of ``f.diff(a)`` with ``f``.  Built by ``Kernel.diff``.
+
+    Every block is ONE fused launch (``gpk_kmat_diff``) written straight into the caller's view, lower-triangle-only and with the
+    diagonal additions where the block is symmetric (``dim_x == dim_y``) -- it is assembled and factorised in place like a plain kernel
+    matrix.  Behind per-dimension length scales the launch runs on the divided inputs and the chain-rule factors ``1 / l_a``, ``1 / l_b``
+    ride in the variances.  ``terms()`` is None: this is no sum of primitives, nobody may add its "terms" to a plain launch."""
+
+    def __init__(self, k, dim_x, dim_y):
+        if dim_x is None and dim_y is None:
+            raise ValueError("a derivative kernel differentiates at least one argument")
+        self.k, self.dim_x, self.dim_y = k, dim_x, dim_y
+        self.stationary = k.stationary
+
+    def _parts(self, x):
+        """``(terms, shapes, imap, fa, fb)``: the term table behind the map and the chain-rule factors of the two slots."""
+        kern, imap = self.k.input_scaled_view()
+        fa = fb = 1.0
+        if imap is not None:
+            scales = imap.param.detach().to(dtype=torch.float64, device="cpu")
+            for dim in (self.dim_x, self.dim_y):
+                if dim is not None and dim >= scales.numel():
+                    raise ValueError(f"dimension {dim} outside the kernel's {scales.numel()} length scales")
+            fa = 1.0 if self.dim_x is None else 1.0 / float(scales[self.dim_x])
+            fb = 1.0 if self.dim_y is None else 1.0 / float(scales[self.dim_y])
+        return kern.terms(), kern.shapes(), imap, fa, fb
+
+    def _check_dims(self, x):
+        d = x.shape[-1]
+        for dim in (self.dim_x, self.dim_y):
+            if dim is not None and dim >= d:
+                raise ValueError(f"derivative with respect to dimension {dim} of inputs with {d} dimensions")
+
+    def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None, out=None, accumulate=False):
+        x = uprank(x)
+        sym = y is None
+        y = None if sym else uprank(y)
+        if isinstance(x, MultiInput) or isinstance(y, MultiInput):
+            raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
+        self._check_dims(x)
+        terms, shapes, imap, fa, fb = self._parts(x)
+        if fa * fb != 1.0:
+            terms = [(kind, var * (fa * fb), scale) for kind, var, scale in terms]
+        xm = x.detach() if imap is None else imap.values(x)
+        ym = None if sym else (y.detach() if imap is None else imap.values(y))
+        be, kt = ops.get_backend(), ops.KTerms(terms, shapes)
+        if sym and self.dim_x == self.dim_y:       # symmetric: lower-triangle-only and the diagonal additions in the same pass
+            return be.kmat_diff(kt, xm, None, self.dim_x, self.dim_y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out,
+                                accumulate=accumulate)
+        res = be.kmat_diff(kt, xm, xm if sym else ym, self.dim_x, self.dim_y, out=out, accumulate=accumulate)
+        return _add_diag(res, diag_add, diag_vec) if sym else res
+
+    def elwise(self, x, y=None, *, cache=None):
+        """No launch: at coincident points a stationary term contributes ``v / scale^2`` times ``-2 kappa'(0)`` to ``d^2 / dx_a dy_a`` and
+        nothing to any other derivative; a linear term ``v / scale^2`` times ``[a == b]``, ``x[a]`` or ``x[b]``."""
+        if y is not None and y is not x:
+            raise NotImplementedError("elwise is implemented for identical inputs")
+        x = uprank(x)
+        if isinstance(x, MultiInput):
+            raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
+        self._check_dims(x)
+        terms, _, imap, fa, fb = self._parts(x)
+        shape = tuple(x.shape[:-1]) + (1,)
+        if self.dim_x is not None and self.dim_y is not None:
+            if self.dim_x != self.dim_y:
+                return torch.zeros(shape, dtype=x.dtype, device=x.device)
+            value = sum(var / scale ** 2 * _DIFF_AT_ZERO[kind] for kind, var, scale in terms) * fa * fb
+            return torch.full(shape, value, dtype=x.dtype, device=x.device)
+        lin = sum(var / scale ** 2 for kind, var, scale in terms if kind == "linear") * fa * fb
+        if lin == 0.0:
+            return torch.zeros(shape, dtype=x.dtype, device=x.device)
+        dim = self.dim_x if self.dim_y is None else self.dim_y
+        xm = x.detach() if imap is None else imap.values(x)
+        return lin * xm[..., dim:dim + 1]
+
+    def __reversed__(self):
+        return DiffKernel(self.k, self.dim_y, self.dim_x)       # (k itself is symmetric: _diff_kernel admits nothing else)
+
+    def __repr__(self):
+        dims = f"{self.dim_x}" if self.dim_x == self.dim_y else f"{self.dim_x}, {self.dim_y}"
+        return f"d({dims}) {self.k!r}"
+
+
+# ---------------------------------------------------------------------------
 # Cartesian products of processes (stheno/mo/kernel.py, stheno/mo/mean.py, measure.py:404-423)
 # ---------------------------------------------------------------------------
 def _eval_into(k, x, y, view, lower=False):
     """Write ``k(x, y)`` (``y is None``: symmetric) into the matrix view ``view``: a sum of
-    primitives goes straight into the block (one fused launch, no temporary)."""
+    primitives -- or a derivative of one (``DiffKernel``) -- goes straight into the block (one fused launch, no temporary)."""
     if isinstance(k, ZeroKernel):
         view.zero_()
-    elif k.terms() is not None and not isinstance(y, MultiInput):
+    elif (k.terms() is not None or isinstance(k, DiffKernel)) and not isinstance(y, MultiInput):
         k.pairwise(x, y, lower=lower, out=view)
     else:
         view.copy_(k.pairwise(x, y))
@@ -930,11 +1083,18 @@ class Mean:
 
     __rmul__ = __mul__
 
+    def diff(self, dim=0):
+        """``dm / dx[dim]`` as a mean (the mean of ``f.diff(dim)``, ``measure.py:357``)."""
+        raise NotImplementedError(f"derivatives are not implemented for {type(self).__name__}")
+
 
 class ZeroMean(Mean):
     def __call__(self, x, cache=None):
         x = uprank(x)
         return torch.zeros(x.shape[:-1] + (1,), dtype=x.dtype, device=x.device)
+
+    def diff(self, dim=0):
+        return ZeroMean()
 
     def __repr__(self):
         return "0"
@@ -944,6 +1104,9 @@ class OneMean(Mean):
     def __call__(self, x, cache=None):
         x = uprank(x)
         return torch.ones(x.shape[:-1] + (1,), dtype=x.dtype, device=x.device)
+
+    def diff(self, dim=0):
+        return ZeroMean()
 
     def __repr__(self):
         return "1"
@@ -958,8 +1121,42 @@ class FunctionMean(Mean):
     def __call__(self, x, cache=None):
         return uprank(self.f(uprank(x)))
 
+    def diff(self, dim=0):
+        return DiffMean(self, _as_dim(dim))
+
     def __repr__(self):
         return getattr(self.f, "__name__", "f")
+
+
+class DiffMean(Mean):
+    """``dm / dx[dim]`` of a function mean, by ``torch.autograd.grad`` on a detached copy of the inputs (the reference differentiates
+    the mean function by autodiff as well).  The function acts point by point: row ``i`` of ``m(x)`` depends on row ``i`` of ``x`` only.
+    While the caller records a graph the derivative stays part of it (``create_graph``): a mean function with learnable parameters
+    hands on a derivative that still depends on them, never a detached value."""
+
+    def __init__(self, m, dim):
+        self.m, self.dim = m, dim
+
+    def __call__(self, x, cache=None):
+        x = uprank(x)
+        if self.dim >= x.shape[-1]:
+            raise ValueError(f"derivative with respect to dimension {self.dim} of inputs with {x.shape[-1]} dimensions")
+        recording = torch.is_grad_enabled()
+        with torch.enable_grad():
+            xg = x.detach().clone().requires_grad_(True)
+            out = _call_mean(self.m, xg, None)
+            if not (torch.is_tensor(out) and out.requires_grad):       # a mean that does not depend on its inputs
+                return torch.zeros(x.shape[:-1] + (1,), dtype=x.dtype, device=x.device)
+            (g,) = torch.autograd.grad(out.sum(), xg, create_graph=recording, allow_unused=True)
+            if g is None:                                              # ... or on its parameters only
+                return torch.zeros(x.shape[:-1] + (1,), dtype=x.dtype, device=x.device)
+        return g[..., self.dim:self.dim + 1].contiguous()
+
+    def diff(self, dim=0):
+        raise NotImplementedError("second derivatives (f.diff().diff()) are not implemented")
+
+    def __repr__(self):
+        return f"d({self.dim}) {self.m!r}"
 
 
 class ScaledMean(Mean):
@@ -968,6 +1165,9 @@ class ScaledMean(Mean):
 
     def __call__(self, x, cache=None):
         return self.v * self.m(x, cache)
+
+    def diff(self, dim=0):
+        return ScaledMean(self.m.diff(dim), self.v)
 
     def __repr__(self):
         return f"{self.v} * {self.m!r}"
@@ -979,6 +1179,9 @@ class SumMean(Mean):
 
     def __call__(self, x, cache=None):
         return self.a(x, cache) + self.b(x, cache)
+
+    def diff(self, dim=0):
+        return self.a.diff(dim) + self.b.diff(dim)
 
     def __repr__(self):
         return f"{self.a!r} + {self.b!r}"
@@ -1175,6 +1378,10 @@ class PosteriorMean(Mean):
         self._w = None
         self._r = None
         self._r_detached = False         # the residual was formed under torch.no_grad() (cut off from a learnable mean / y)
+
+    def diff(self, dim=0):
+        raise PosteriorDerivativeError("derivatives of posterior means are not implemented: differentiate the prior process and look its "
+                                       "derivative up under the posterior (`post(f.diff())`)")
 
     def _residual(self):
         if self._r is None:

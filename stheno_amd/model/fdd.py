@@ -76,8 +76,8 @@ class FDD(Normal):
 
         def var():
             k = p.kernel
-            if k.input_scaled_view() is not None or isinstance(k, _k.MultiOutputKernel):
-                return KernelDense(k, xr, nz)      # K + noise fused, factorised in place
+            if k.input_scaled_view() is not None or isinstance(k, (_k.MultiOutputKernel, _k.DiffKernel)):
+                return KernelDense(k, xr, nz)      # K + noise fused, factorised in place (a derivative kernel: one gpk_kmat_diff launch)
             return k(xr) + nz
 
         Normal.__init__(self, lambda: p.mean(xr), var, var_diag=var_diag, mean_var=mean_var,

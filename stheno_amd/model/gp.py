@@ -51,6 +51,7 @@ class GP(RandomProcess):
         # and the Cholesky factor it owns -- dies with its last user handle, not with the prior GP.
         self._measure0 = None
         self._backrefs = weakref.WeakSet()
+        self._refused_by = weakref.WeakSet()      # posteriors conditioned before this (derivative) process existed: see `diff`
         self._parents = ()      # processes this one is derived from (kept alive: rules refer to their ids)
         if len(args) == 0:
             return
@@ -134,6 +135,22 @@ class GP(RandomProcess):
         res._parents = (self,)
         for measure in self._measures:
             measure.mul(res, self, other)
+        return res
+
+    def diff(self, dim=0):
+        """The derivative process ``df / dx[dim]`` (``gp.py:218``), jointly Gaussian with ``self``: observe it, condition on it,
+        predict it (``post(df)``).  It is registered in every measure that knows ``self``, as in the reference -- except posteriors
+        conditioned EARLIER: a posterior mean / kernel has no derivative (``PosteriorDerivativeError``, nothing else is caught), so
+        such a measure is remembered on the new process and ``post(df)`` there refuses with that reason.  Differentiate first,
+        condition then."""
+        res = GP()
+        res._parents = (self,)
+        self.measure.diff(res, self, dim)
+        for measure in list(self._backrefs):
+            try:
+                measure.diff(res, self, dim)
+            except _k.PosteriorDerivativeError:
+                res._refused_by.add(measure)
         return res
 
     @property

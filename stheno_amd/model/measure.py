@@ -115,6 +115,10 @@ class Measure:
         re-bound under this measure (``measure.py:139-154``)."""
         if isinstance(p, FDD):
             return self(p.p)(p.x, p.noise)
+        if self in p._refused_by:
+            raise _k.PosteriorDerivativeError(
+                "this posterior was conditioned before the derivative process was created and cannot take it (a posterior mean / "
+                "kernel has no derivative): call `f.diff()` first, condition then, and look the derivative up as `post(df)`")
         p_copy = GP()
         p_copy._parents = (p,)
         wself, pid = weakref.ref(self), id(p)
@@ -144,6 +148,13 @@ class Measure:
         v = float(other)
         wself, pid = weakref.ref(self), id(p)
         return self._update(p_mul, self.means[p] * v, self.kernels[p] * v**2, lambda j: wself().kernels[pid, j] * v)
+
+    def diff(self, p_diff, p, dim=0):
+        """Register ``p_diff`` as the derivative of ``p`` with respect to input dimension ``dim`` (``measure.py:343-360``): mean and
+        kernel differentiated in that dimension, the cross-kernel with any other process in its first argument."""
+        wself, pid = weakref.ref(self), id(p)
+        return self._update(p_diff, self.means[p].diff(dim), self.kernels[p].diff(dim),
+                            lambda j: wself().kernels[pid, j].diff(dim, None))
 
     def cross(self, p_cross, *ps):
         """Register ``p_cross`` as the Cartesian product of ``ps`` (``measure.py:404-423``): its

@@ -229,6 +229,34 @@ class HipBackend:
         return out
 
     @_on_operand_device
+    def kmat_diff(self, terms, x, y, dim_x, dim_y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        """Derivative blocks of the kernel matrix (``gpk_kmat_diff``): ``out[b, i, j] (+)=`` the derivative of ``k(x[b, i], y[b, j])`` with
+        respect to ``x[b, i, dim_x]`` and / or ``y[b, j, dim_y]`` (``None``: not differentiated in that argument; at least one is given).
+        ``y is None``: the symmetric case, which needs ``dim_x == dim_y`` (``lower``, ``diag_add`` / ``diag_vec`` as for :meth:`kmat`)."""
+        symmetric = y is None
+        dx, dy = (-1 if v is None else int(v) for v in (dim_x, dim_y))
+        x3, bshape = _as3(x)
+        y3 = x3 if symmetric else _as3(y)[0]
+        self._check(x3, y3, diag_vec, out)
+        B, n, d = x3.shape
+        m = y3.shape[1]
+        if y3.shape[0] != B or y3.shape[2] != d:
+            raise ValueError("x and y must agree in batch size and input dimension")
+        if out is None:
+            out = _alloc(bshape, n, m, x.dtype, x.device)
+        o3, _ = _as3_out(out)
+        dv = None
+        if diag_vec is not None:
+            dv = diag_vec.reshape(B, n).contiguous()
+        kinds, var, ils, nt = terms.c_arrays()
+        tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
+                _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
+                self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
+        code = self.lib.gpk_kmat_diff(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, dx, dy, *tail)
+        self._st(code, "gpk_kmat_diff")
+        return out
+
+    @_on_operand_device
     def kdiag(self, terms, x):
         x3, bshape = _as3(x)
         self._check(x3)
@@ -658,8 +686,9 @@ class HipBackend:
 
 class _HostDelta:
     """Around a backend that is not the HIP one (the checker backends of ``tests/``, built on an oracle that predates the ``"delta"``
-    kind): ``"delta"`` terms are evaluated here, in NumPy, and every other term is handed on unchanged.  ``HipBackend`` is never
-    wrapped: there the Delta terms are terms of the fused HIP kernels like any other."""
+    kind): ``"delta"`` terms are evaluated here, in NumPy, and every other term is handed on unchanged; so are the derivative blocks of
+    ``kmat_diff``, which that oracle does not know either.  ``HipBackend`` is never wrapped: there both are launches of the fused HIP
+    kernels."""
 
     def __init__(self, inner):
         self._inner = inner
@@ -696,6 +725,78 @@ class _HostDelta:
         res = self._inner.kmat(rest, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec)
         for _, (_, var, scale), eps in delta:
             res = res + self._t(var * self._kappa(x, x if y is None else y, scale, eps), res)
+        if out is None:
+            return res
+        if accumulate:
+            out += res
+        else:
+            out.copy_(res)
+        return out
+
+    def kmat_diff(self, terms, x, y, dim_x, dim_y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        """``HipBackend.kmat_diff`` in NumPy (fp64, rounded to the inputs' dtype), from the closed forms in ``include/gpk.h``: the
+        checker backends know no derivative blocks, so the host logic of ``DiffKernel`` runs on this."""
+        import numpy as np
+
+        if dim_x is None and dim_y is None:
+            raise ValueError("a derivative block differentiates at least one argument")
+        if y is None and dim_x != dim_y:
+            raise ValueError("the symmetric form needs the same dimension in both arguments")
+        a = x.detach().cpu().numpy().astype(np.float64)
+        b = a if y is None else y.detach().cpu().numpy().astype(np.float64)
+        for dim in (dim_x, dim_y):
+            if dim is not None and not 0 <= dim < a.shape[-1]:
+                raise ValueError(f"dimension {dim} outside the {a.shape[-1]} input dimensions")
+        df = a[..., :, None, :] - b[..., None, :, :]
+        r2 = (df ** 2).sum(-1)
+        da = df[..., dim_x] if dim_x is not None else None
+        db = df[..., dim_y] if dim_y is not None else None
+        res = np.zeros_like(r2)
+        for (kind, v, scale), alpha in zip(terms.terms, terms.shapes or [None] * len(terms)):
+            c = (1.0 / scale) ** 2
+            if kind == "const":
+                continue
+            if kind == "linear":
+                if dim_y is None:
+                    res += c * v * b[..., None, :, dim_x]
+                elif dim_x is None:
+                    res += c * v * a[..., :, None, dim_y]
+                elif dim_x == dim_y:
+                    res += c * v
+                continue
+            q = c * r2
+            if kind == "eq":
+                k1 = -0.5 * np.exp(-0.5 * q)
+                k2dd = 0.25 * np.exp(-0.5 * q) * (da * db) if db is not None and da is not None else None
+            elif kind == "rq":
+                u = q / (2.0 * alpha)
+                k1 = -0.5 * np.exp(-(alpha + 1.0) * np.log1p(u))
+                k2dd = (alpha + 1.0) / (4.0 * alpha) * np.exp(-(alpha + 2.0) * np.log1p(u)) * (da * db) if db is not None and da is not None else None
+            elif kind == "matern52":
+                sd = np.sqrt(5.0 * q)
+                k1 = -(5.0 / 6.0) * (1.0 + sd) * np.exp(-sd)
+                k2dd = (25.0 / 12.0) * np.exp(-sd) * (da * db) if db is not None and da is not None else None
+            elif kind == "matern32":
+                sd = np.sqrt(3.0 * q)
+                k1 = -1.5 * np.exp(-sd)
+                k2dd = None
+                if da is not None and db is not None:      # kappa'' D_a D_b -> 0 with the distance: 0 at coincident points
+                    pos = sd > 0
+                    k2dd = 2.25 * np.exp(-sd) * np.where(pos, (da * db) / np.where(pos, sd, 1.0), np.where(np.isnan(sd), np.nan, 0.0))
+            else:
+                raise NotImplementedError(f"a {kind!r} term has no derivative")
+            if dim_y is None:
+                res += 2.0 * c * v * k1 * da
+            elif dim_x is None:
+                res += -2.0 * c * v * k1 * db
+            else:
+                res += v * (-4.0 * c * c * k2dd - (2.0 * c * k1 if dim_x == dim_y else 0.0))
+        if y is None:
+            idx = np.arange(res.shape[-1])
+            res[..., idx, idx] += diag_add
+            if diag_vec is not None:
+                res[..., idx, idx] += diag_vec.detach().cpu().numpy().reshape(res.shape[:-2] + (res.shape[-1],))
+        res = self._t(res, x)
         if out is None:
             return res
         if accumulate:
