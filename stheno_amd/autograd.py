@@ -13,6 +13,12 @@ Gradients w.r.t. the inputs ``x`` (learnt input warps, latent inputs, per-dimens
 ``k.stretch(vector)`` divides the inputs) take one more pass: the explicit symmetric cotangent
 ``G`` is formed in the buffer of ``K^{-1}`` (a rank-C GEMM update) and ``gpk_kmat_vjp_dense`` reduces it
 against ``dK_ij/dx_i``; both arguments of ``k(x, x)`` move with ``x``, hence the factor two.
+
+A kernel enters every function here as GROUPS of terms that see the same inputs (``kernels._map_groups``): ``k(x, y) = sum_g
+k_g(u_g(x), u_g(y))`` with ``k_g`` a sum of primitives and ``u_g`` a differentiable map of the inputs (none, the division by
+per-dimension length scales, the periodic embedding), formed in torch by the caller.  The cotangent of ``K`` is the same for every group;
+the reductions against it run once per group, on that group's term table and mapped inputs, and each group's input gradient goes back to
+torch, which carries it through the map to its parameter and to ``x``.  One group is the plain case: the same launches as ever.
 """
 import math
 
@@ -41,6 +47,34 @@ def _pack(tt, shapes):
                 raise ValueError(f"the shape parameter of a {k!r} term is not learnable")
         params += [_as_t(0.0 if a is None else a) for a in shapes]
     return kinds, params
+
+
+def _pack_groups(kernels):
+    """``(layout, params)`` of the groups' kernels: ``layout`` = one ``(kinds, number of parameters)`` per group, ``params`` = the flat
+    parameter lists (``_pack``) group after group."""
+    layout, params = [], []
+    for kern in kernels:
+        kinds, pr = _pack(kern.tensor_terms(), kern.tensor_shapes())
+        layout.append((kinds, len(pr)))
+        params.extend(pr)
+    return tuple(layout), params
+
+
+def _split_groups(layout, tensors, per_group=1):
+    """The tensors behind ``layout`` in an autograd function's arguments: ``per_group`` input tensors per group first, then the flat
+    parameters group after group.  Returns ``[(kinds, inputs, params)]``."""
+    pos = per_group * len(layout)
+    out = []
+    for i, (kinds, npar) in enumerate(layout):
+        out.append((kinds, tensors[per_group * i: per_group * (i + 1)], tensors[pos: pos + npar]))
+        pos += npar
+    return out
+
+
+def _check_input_dims(u):
+    if u.shape[-1] > 8:
+        raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
+                                  "are implemented for at most 8 input dimensions")
 
 
 def _unpack(kinds, params):
@@ -84,51 +118,78 @@ def _grad_inputs(be, terms, x, G):
 
 class _GPLogpdf(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, r, noise_vec, noise_mat, kinds, *params):
-        """``params`` = variances, scales (and shape parameters: ``_pack``; scalar tensors, any device); ``noise_vec`` (n,)
-        or None; ``noise_mat`` (n, n) dense noise covariance or None; ``r = y - mean`` (n, C).  Returns (C,)."""
+    def forward(ctx, r, noise_vec, noise_mat, layout, *tensors):
+        """``layout`` = one ``(kinds, number of parameters)`` per group of terms; ``tensors`` = the groups' inputs ``u_g`` (n, D_g),
+        then their parameters group after group -- variances, scales (and shape parameters: ``_pack``; scalar tensors, any device);
+        ``noise_vec`` (n,) or None; ``noise_mat`` (n, n) dense noise covariance or None; ``r = y - mean`` (n, C).  Returns (C,)."""
         be = ops.get_backend()
-        nt = len(kinds)
-        terms, values = _unpack(kinds, params)
+        groups, metas = [], []
+        for kinds, (u,), params in _split_groups(layout, tensors):
+            terms, values = _unpack(kinds, params)
+            groups.append((kinds, terms, values, u))
+            metas.append([(p.device, p.dtype) for p in params])
         n, C = r.shape
-        k = be.kmat(terms, x, None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
+        # the first group writes the lower triangle with the diagonal additions, the others add to it (as `Sum.pairwise` does)
+        k = be.kmat(groups[0][1], groups[0][3], None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
+        for _, terms, _, u in groups[1:]:
+            be.kmat(terms, u, None, lower=True, out=k, accumulate=True)
         if noise_mat is not None:
             k += noise_mat                                       # (only the lower triangle is read from here on)
         chol = Chol.factor_(k)
         w = chol.solve(r)                                        # L^{-1} r
         _, ss = be.colreduce(w, want_ss=True)
         out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
-        ctx.chol, ctx.w, ctx.x, ctx.terms = chol, w, x, terms
-        ctx.nt, ctx.has_noise = nt, noise_vec is not None
-        ctx.has_noise_mat = noise_mat is not None
-        ctx.param_meta = [(p.device, p.dtype) for p in params]
-        ctx.values, ctx.kinds = values, kinds
+        ctx.chol, ctx.w, ctx.groups, ctx.param_metas = chol, w, groups, metas
+        ctx.has_noise, ctx.has_noise_mat = noise_vec is not None, noise_mat is not None
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         be = ops.get_backend()
-        chol, w, x, terms, nt = ctx.chol, ctx.w, ctx.x, ctx.terms, ctx.nt
+        chol, w, groups = ctx.chol, ctx.w, ctx.groups
         n, C = w.shape
+        ng = len(groups)
         if C > 8:
             raise NotImplementedError("backward through logpdf supports at most 8 columns of y")
+        need_u = [ctx.needs_input_grad[4 + i] for i in range(ng)]
+        need_nm = ctx.has_noise_mat and ctx.needs_input_grad[2]
+        for (_, _, _, u), need in zip(groups, need_u):
+            if need:
+                _check_input_dims(u)
         g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
         # W = L^{-1} (lower triangular), K^{-1} = W^T W, A = K^{-1} r = W^T w
         W = chol.inverse_lower()                                              # N^3/3 flops
         kinv = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)   # N^3/3 flops
         alpha = torch.stack([be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(C)], dim=1)
-        S, trace_g, diag_g = be.kmat_vjp(terms, x, kinv, alpha, g)
-        grads = _param_grads(ctx.kinds, ctx.values, S, ctx.param_meta)
+        # several groups of which one passes a gradient to its inputs: every group reads the explicit cotangent once, its sums and its
+        # input gradient out of the same pass; otherwise the implicit form, one pass over the lower triangle of K^{-1} per group
+        dense = ng > 1 and any(need_u)
+        S, grad_us, diag_g = [None] * ng, [None] * ng, None
+        if not dense:
+            for i, (_, terms, _, u) in enumerate(groups):
+                S[i], _, dg = be.kmat_vjp(terms, u, kinv, alpha, g)
+                if i == 0:
+                    diag_g = dg                                  # (the cotangent's diagonal: the same from every group)
+        grad_nm = None
+        if any(need_u) or need_nm:
+            G = _cotangent(be, kinv, alpha, g)                   # explicit, in the buffer of K^{-1}
+            for i, (_, terms, _, u) in enumerate(groups):
+                if dense:
+                    S[i], _, gx = be.kmat_vjp_dense(terms, u, u, G, want_gradx=need_u[i])
+                    if need_u[i]:
+                        grad_us[i] = 2.0 * gx
+                elif need_u[i]:
+                    grad_us[i] = _grad_inputs(be, terms, u, G)
+            if dense:
+                diag_g = torch.diagonal(G).clone()
+            if need_nm:
+                grad_nm = G                                      # d/d noise matrix: the cotangent of K itself
+        grads = []
+        for (kinds, _, values, _), S_g, meta in zip(groups, S, ctx.param_metas):
+            grads += _param_grads(kinds, values, S_g, meta)
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype))
         grad_noise = diag_g if ctx.has_noise else None
-        grad_x = grad_nm = None
-        if ctx.needs_input_grad[0] or (ctx.has_noise_mat and ctx.needs_input_grad[3]):
-            G = _cotangent(be, kinv, alpha, g)                   # explicit, in the buffer of K^{-1}
-            if ctx.needs_input_grad[0]:
-                grad_x = _grad_inputs(be, terms, x, G)
-            if ctx.has_noise_mat and ctx.needs_input_grad[3]:
-                grad_nm = G                                      # d/d noise matrix: the cotangent of K itself
-        return (grad_x, grad_r, grad_noise, grad_nm, None, *grads)
+        return (grad_r, grad_noise, grad_nm, None, *grad_us, *grads)
 
 
 class _GPLogpdfBatched(torch.autograd.Function):
@@ -184,15 +245,18 @@ class _GPLogpdfBatched(torch.autograd.Function):
 class _JointLogpdf(torch.autograd.Function):
     """Log-density of SEVERAL processes of one measure observed jointly (``measure.logpdf((f1(x1), y1), (f2(x2), y2))``,
     ``f(x).logpdf(y)`` of a product process): the variance is the block matrix of ``MultiOutputKernel``, block (i, j) =
-    ``kernels[p_i, p_j](x_i, x_j)``, every block a sum of primitives.  Forward = the plain HIP path (blocks written into one
-    buffer, factorised in place).  Backward: the explicit cotangent ``G = 1/2 (alpha diag(g) alpha^T - sum(g) K^{-1})`` once, then one
-    ``gpk_kmat_vjp_dense`` pass per block of the lower block triangle over its view of ``G`` (off-diagonal blocks count twice: ``G`` and
-    the block matrix are symmetric).  ``layout`` = [(i, j, number of terms, number of parameters)], ``params`` = the variances, scales
-    (and shape parameters, for a block that has any: ``_pack``) of block after block: autograd carries them back to the user's
-    leaves through whatever kernel algebra produced them."""
+    ``kernels[p_i, p_j](x_i, x_j)``, every block a sum of groups of primitives behind input maps.  Forward = the plain HIP path (blocks
+    written into one buffer, factorised in place).  Backward: the explicit cotangent ``G = 1/2 (alpha diag(g) alpha^T - sum(g) K^{-1})``
+    once, then one ``gpk_kmat_vjp_dense`` pass per group of every block of the lower block triangle over the block's view of ``G``
+    (off-diagonal blocks count twice: ``G`` and the block matrix are symmetric).  ``layout`` = [(i, j, kinds, number of parameters, a,
+    b)], ``a`` / ``b`` the positions of the group's row / column inputs among the ``nu`` mapped inputs that lead ``tensors``; behind
+    them the variances, scales (and shape parameters, for a group that has any: ``_pack``) of group after group: autograd carries them
+    back to the user's leaves through whatever kernel algebra produced them.  A mapped input that requires a gradient (a learnable
+    period, learnable per-dimension scales) gets it from the same pass where it is the row input, and from one more pass over the
+    transposed view ``G[j-block, i-block]`` where it is the column input of an off-diagonal block; either way twice the reduction."""
 
     @staticmethod
-    def forward(ctx, r, noise_vec, build, parts, layout, kinds, *params):
+    def forward(ctx, r, noise_vec, build, sizes, layout, nu, *tensors):
         be = ops.get_backend()
         n = r.shape[0]
         k = build()                                              # lower block triangle + eps + noise on the diagonal
@@ -200,7 +264,8 @@ class _JointLogpdf(torch.autograd.Function):
         w = chol.solve(r)
         _, ss = be.colreduce(w, want_ss=True)
         out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
-        ctx.chol, ctx.w, ctx.parts, ctx.layout, ctx.kinds = chol, w, parts, layout, kinds
+        params = tensors[nu:]
+        ctx.chol, ctx.w, ctx.sizes, ctx.layout, ctx.us = chol, w, sizes, layout, tensors[:nu]
         ctx.has_noise = noise_vec is not None
         ctx.param_meta = [(p.device, p.dtype) for p in params]
         ctx.values = [float(p) for p in params]
@@ -209,57 +274,87 @@ class _JointLogpdf(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         be = ops.get_backend()
-        chol, w = ctx.chol, ctx.w
+        chol, w, us = ctx.chol, ctx.w, ctx.us
+        nu = len(us)
+        need_u = [ctx.needs_input_grad[6 + a] for a in range(nu)]
+        for u, need in zip(us, need_u):
+            if need:
+                _check_input_dims(u)
         g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
         W = chol.inverse_lower()
         G = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)      # K^{-1}, lower triangle
         alpha = torch.stack([be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(w.shape[1])], dim=1)
         G = _cotangent(be, G, alpha, g)
         offs = [0]
-        for _, xi in ctx.parts:
-            offs.append(offs[-1] + xi.shape[0])
-        grads, pos, kpos = [None] * len(ctx.values), 0, 0
-        for (i, j, nt, npar) in ctx.layout:
-            kinds = ctx.kinds[kpos: kpos + nt]
+        for rows in ctx.sizes:
+            offs.append(offs[-1] + rows)
+        grads, grad_us, pos = [None] * len(ctx.values), [None] * nu, 0
+
+        def add(a, gx):
+            grad_us[a] = 2.0 * gx if grad_us[a] is None else grad_us[a] + 2.0 * gx
+
+        for (i, j, kinds, npar, a, b) in ctx.layout:
             terms, values = _unpack(kinds, ctx.values[pos: pos + npar])
             gb = G[offs[i]: offs[i + 1], offs[j]: offs[j + 1]]
-            S, _, _ = be.kmat_vjp_dense(terms, ctx.parts[i][1], ctx.parts[j][1], gb)
+            S, _, gx = be.kmat_vjp_dense(terms, us[a], us[b], gb, want_gradx=need_u[a])
             grads[pos: pos + npar] = _param_grads(kinds, values, S, ctx.param_meta[pos: pos + npar], 1.0 if i == j else 2.0)
+            if need_u[a]:
+                add(a, gx)
+            if i != j and need_u[b]:                             # (the block's mirror image: G is symmetric, explicitly)
+                _, _, gx = be.kmat_vjp_dense(terms, us[b], us[a], G[offs[j]: offs[j + 1], offs[i]: offs[i + 1]], want_gradx=True)
+                add(b, gx)
             pos += npar
-            kpos += nt
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype)) if ctx.needs_input_grad[0] else None
         grad_noise = torch.diagonal(G).clone() if ctx.has_noise else None
-        return (grad_r, grad_noise, None, None, None, None, *grads)
+        return (grad_r, grad_noise, None, None, None, None, *grad_us, *grads)
 
 
 def joint_logpdf(mok, x, noise_vec, r, eps):
     """Differentiable joint log-density under ``MultiOutputKernel`` ``mok`` at the multi-input ``x``; None when a block of the
-    lower block triangle is not a sum of primitives with scalar hyper-parameters (the caller then refuses)."""
+    lower block triangle is not a sum of primitives behind input maps with scalar hyper-parameters (the caller then refuses)."""
+    from . import kernels as _k
+
     kernels = mok.kernels
     parts = [(pid, xi) for pid, xi in mok._split(x)]
     if any((not torch.is_tensor(xi)) or xi.dim() != 2 or kernels[pid].num_outputs(xi) != xi.shape[0] for pid, xi in parts):
         return None                                   # batched inputs / nested product processes: not covered
     if any(xi.requires_grad for _, xi in parts):
         return None                                   # d/dx through the block matrix: not covered (the caller refuses)
-    layout, kinds, variances_scales = [], [], []
+    layout, params, us, where = [], [], [], {}
+
+    def mapped(i, imap):
+        """Position of ``imap(x_i)`` among the mapped inputs (formed once per part and map, in torch: the graph reaches the map's
+        parameter)."""
+        key = (i, id(imap))
+        if key not in where:
+            where[key] = len(us)
+            us.append(parts[i][1] if imap is None else imap(parts[i][1]))
+        return where[key]
+
     for i, (pi, _) in enumerate(parts):
         for j in range(i + 1):
             kern = kernels[pi] if i == j else kernels[pi, parts[j][0]]
-            tt = kern.tensor_terms() if hasattr(kern, "tensor_terms") else None
-            if tt is None:
+            groups = _k._map_groups(kern) if isinstance(kern, _k.Kernel) else None
+            if groups is None:
                 return None
-            kd, pr = _pack(tt, kern.tensor_shapes() if hasattr(kern, "tensor_shapes") else None)
-            layout.append((i, j, len(tt), len(pr)))
-            kinds.extend(kd)
-            variances_scales.extend(pr)
-    if not torch.is_grad_enabled() or not (any(p.requires_grad for p in variances_scales) or r.requires_grad
+            for kg, imap in groups:
+                tt = kg.tensor_terms()
+                if tt is None:
+                    return None
+                kd, pr = _pack(tt, kg.tensor_shapes())
+                layout.append((i, j, kd, len(pr), mapped(i, imap), mapped(j, imap)))
+                params.extend(pr)
+    if not torch.is_grad_enabled() or not (any(p.requires_grad for p in params) or any(u.requires_grad for u in us) or r.requires_grad
                                             or (noise_vec is not None and noise_vec.requires_grad)):
         return None
+    for u in us:
+        if u.requires_grad:
+            _check_input_dims(u)
 
     def build():
         return mok.pairwise(x, None, lower=True, diag_add=eps, diag_vec=noise_vec)
 
-    return _JointLogpdf.apply(r, noise_vec, build, parts, tuple(layout), tuple(kinds), *variances_scales)
+    return _JointLogpdf.apply(r, noise_vec, build, tuple(xi.shape[0] for _, xi in parts), tuple(layout), len(us), *us, *params)
 
 
 def _any_shape_grad(shapes):
@@ -303,12 +398,20 @@ def kernel_requires_grad(kernel, _depth=0):
     return False
 
 
-def gp_logpdf(kernel, x, noise_vec, r, noise_mat=None):
-    """Differentiable log-density of ``r = y - m(x)`` under ``N(0, k(x) + diag(noise_vec) + noise_mat + eps I)``."""
-    kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
-    if x.dim() == 3:
+def groups_need_grad(groups, noise_vec, r, noise_mat=None):
+    """``needs_grad`` for a kernel given as groups ``[(k_g, u_g)]``: any group's terms, shape parameters or mapped inputs."""
+    return any(needs_grad(kern.tensor_terms(), noise_vec, r, u, noise_mat, kern.tensor_shapes()) for kern, u in groups)
+
+
+def gp_logpdf(groups, noise_vec, r, noise_mat=None):
+    """Differentiable log-density of ``r = y - m(x)`` under ``N(0, sum_g k_g(u_g) + diag(noise_vec) + noise_mat + eps I)``; ``groups``
+    = ``[(k_g, u_g)]``, every ``k_g`` a sum of primitives on its (mapped) inputs ``u_g``.  Batched inputs: one group."""
+    if groups[0][1].dim() == 3:
+        (kernel, x), = groups
+        kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
         return _GPLogpdfBatched.apply(x, r, noise_vec, kinds, *params)
-    return _GPLogpdf.apply(x, r, noise_vec, noise_mat, kinds, *params)
+    layout, params = _pack_groups([kern for kern, _ in groups])
+    return _GPLogpdf.apply(r, noise_vec, noise_mat, layout, *[u for _, u in groups], *params)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -489,18 +592,21 @@ def sparse_elbo(kernel, x, z, noise_vec, r, method):
 # ---------------------------------------------------------------------------------------------
 class _PosteriorMarginals(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, xs, r, noise_vec, run, kinds, *params):
+    def forward(ctx, r, noise_vec, run, layout, *tensors):
         """``run()`` -> ``(chol, w, v, mu, s)``: the plain HIP path of the posterior (``kernels._posterior_parts``: the factor a
         preceding log-density left, or the one whose factorisation carried the cross-covariance as rows under the matrix); ``v`` is
-        ``L^{-1} k(x, xs)`` (N, N*) or its transpose as a ``WhitenedT``.  ``x`` / ``xs``: the inputs the fused kernels see (divided by
-        per-dimension length scales); ``r`` (N, 1) or None (marginal variances only: ``mu`` comes back as zeros)."""
+        ``L^{-1} k(x, xs)`` (N, N*) or its transpose as a ``WhitenedT``.  ``layout`` = one ``(kinds, number of parameters)`` per group of
+        terms; ``tensors`` = per group ``x`` / ``xs`` as its fused kernels see them (behind the group's input map), then the groups'
+        parameters; ``r`` (N, 1) or None (marginal variances only: ``mu`` comes back as zeros)."""
         chol, w, v, mu, s = run()
-        nt = len(kinds)
-        ctx.terms, ctx.values = _unpack(kinds, params)
-        ctx.kinds = kinds
-        ctx.chol, ctx.w, ctx.v, ctx.x, ctx.xs = chol, w, v, x, xs
-        ctx.nt, ctx.has_noise, ctx.has_r = nt, noise_vec is not None, r is not None
-        ctx.param_meta = [(p.device, p.dtype) for p in params]
+        groups, metas = [], []
+        for kinds, (x, xs), params in _split_groups(layout, tensors, 2):
+            terms, values = _unpack(kinds, params)
+            groups.append((kinds, terms, values, x, xs))
+            metas.append([(p.device, p.dtype) for p in params])
+        ctx.groups, ctx.param_metas = groups, metas
+        ctx.chol, ctx.w, ctx.v = chol, w, v
+        ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
         ctx.set_materialize_grads(False)
         if mu is None:
             mu = torch.zeros_like(s)
@@ -509,16 +615,23 @@ class _PosteriorMarginals(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_mu, g_s):
         be = ops.get_backend()
-        chol, v, x, xs, terms, nt = ctx.chol, ctx.v, ctx.x, ctx.xs, ctx.terms, ctx.nt
-        n, ns = x.shape[0], xs.shape[0]
-        dt, dev = x.dtype, x.device
+        chol, v, groups = ctx.chol, ctx.v, ctx.groups
+        ng = len(groups)
+        x0, xs0 = groups[0][3], groups[0][4]
+        n, ns = x0.shape[0], xs0.shape[0]
+        dt, dev = x0.dtype, x0.device
         gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
         gs = g_s.to(dt).contiguous() if g_s is not None else None
         if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
             gs = None
-        need_x, need_xs = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_x = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
+        need_xs = [ctx.needs_input_grad[5 + 2 * i] for i in range(ng)]
+        npar = sum(len(m) for m in ctx.param_metas)
         if gm is None and gs is None:
-            return (None,) * (6 + len(ctx.param_meta))
+            return (None,) * (4 + 2 * ng + npar)
+        for (_, _, _, x, _), nx, nxs in zip(groups, need_x, need_xs):
+            if nx or nxs:
+                _check_input_dims(x)
         transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
         alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
         bm = beta = None
@@ -534,23 +647,23 @@ class _PosteriorMarginals(torch.autograd.Function):
         def zeros(rows, cols):          # an all-zero operand read through a zero row stride (no rows x cols buffer)
             return torch.zeros((1, cols), dtype=dt, device=dev).expand(rows, cols)
 
-        # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs)
+        # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs), the same for every group
         cs = 2.0 * gs if gs is not None else None
-        S, _, grad_x = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
-                                         want_gradx=need_x)
-        grad_xs = None
-        if need_xs:
-            if x.shape[-1] > 8:
-                raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
-                                          "are implemented for at most 8 input dimensions")
-            if bm is not None:
-                g_t = be.copy(bm)
-                be.scale_cols_(g_t, cs)
-                g_t = g_t.t().contiguous()                               # (N*, N): 2 diag(gs) B^T, explicit
-            else:
-                g_t = zeros(ns, n)
-            _, _, grad_xs = be.kmat_vjp_dense(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
-            del g_t
+        S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
+        g_t = None
+        for i, (_, terms, _, x, xs) in enumerate(groups):
+            S[i], _, grad_x[i] = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
+                                                   want_gradx=need_x[i])
+            if need_xs[i]:
+                if g_t is None:
+                    if bm is not None:
+                        g_t = be.copy(bm)
+                        be.scale_cols_(g_t, cs)
+                        g_t = g_t.t().contiguous()                       # (N*, N): 2 diag(gs) B^T, explicit
+                    else:
+                        g_t = zeros(ns, n)
+                _, _, grad_xs[i] = be.kmat_vjp_dense(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
+        del g_t
         # through K: -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T) = 1/2 (A diag(g) A^T - sum(g) S)
         cols, g = [], []
         if gm is not None:
@@ -561,21 +674,31 @@ class _PosteriorMarginals(torch.autograd.Function):
             be.scale_cols_(bs, gs)
             kinv = be.gemm(bs, bm, a_kmajor=True, b_kmajor=True, lower_only=True)      # S = B diag(gs) B^T (lower triangle)
             del bs, bm
-            cols.append(torch.zeros_like(x[:, 0]))
+            cols.append(torch.zeros_like(x0[:, 0]))
             g.append(2.0)
         else:
             kinv = zeros(n, n)
         A = torch.stack(cols, dim=1)
-        S_k, _, diag_g = be.kmat_vjp(terms, x, kinv, A, g)
-        S = S + S_k
-        if need_x:
+        diag_g = None
+        for i, (_, terms, _, x, _) in enumerate(groups):
+            S_k, _, dg = be.kmat_vjp(terms, x, kinv, A, g)
+            S[i] = S[i] + S_k
+            if i == 0:
+                diag_g = dg                                           # (the cotangent's diagonal: the same from every group)
+        if any(need_x):
             if kinv.stride(0) == 0:
                 kinv = torch.zeros((n, n), dtype=dt, device=dev)
-            grad_x = grad_x + _grad_inputs(be, terms, x, _cotangent(be, kinv, A, g))
-        grads = _param_grads(ctx.kinds, ctx.values, S, ctx.param_meta)
-        grad_r = beta[:, None] if (beta is not None and ctx.needs_input_grad[2]) else None
-        grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[3]) else None
-        return (grad_x, grad_xs, grad_r, grad_noise, None, None, *grads)
+            G = _cotangent(be, kinv, A, g)                            # once, in the buffer of S
+            for i, (_, terms, _, x, _) in enumerate(groups):
+                if need_x[i]:
+                    grad_x[i] = grad_x[i] + _grad_inputs(be, terms, x, G)
+        grads = []
+        for (kinds, _, values, _, _), S_g, meta in zip(groups, S, ctx.param_metas):
+            grads += _param_grads(kinds, values, S_g, meta)
+        grad_r = beta[:, None] if (beta is not None and ctx.needs_input_grad[0]) else None
+        grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[1]) else None
+        inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
+        return (grad_r, grad_noise, None, None, *inputs, *grads)
 
 
 def kdiag_terms(tensor_terms, x):
@@ -591,8 +714,8 @@ def kdiag_terms(tensor_terms, x):
     return out
 
 
-def posterior_marginals(kernel, x, xs, r, noise_vec, run):
-    """Differentiable ``(mu, s)`` of ``_PosteriorMarginals`` for a sum of primitives ``kernel`` evaluated on ``x`` / ``xs`` (already
-    divided by per-dimension length scales, so torch carries those)."""
-    kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
-    return _PosteriorMarginals.apply(x, xs, r, noise_vec, run, kinds, *params)
+def posterior_marginals(groups, r, noise_vec, run):
+    """Differentiable ``(mu, s)`` of ``_PosteriorMarginals``; ``groups`` = ``[(k_g, x_g, xs_g)]``, every ``k_g`` a sum of primitives
+    evaluated on ``x_g`` / ``xs_g`` (already behind the group's input map, so torch carries the map's parameter)."""
+    layout, params = _pack_groups([kern for kern, _, _ in groups])
+    return _PosteriorMarginals.apply(r, noise_vec, run, layout, *[t for _, x, xs in groups for t in (x, xs)], *params)

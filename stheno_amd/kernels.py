@@ -1460,7 +1460,7 @@ def _learnable_marginals(pm, pk, x, cache):
     ``autograd._PosteriorMarginals``: ``(mean column or None, marginal-variance column or None)`` for the posterior mean ``pm`` and /
     or the posterior kernel ``pk`` at the test inputs ``x``.  None when nothing learnable is behind them, when grad is off, or when the
     call is outside that path (pseudo-point posteriors, several processes, chained conditioning, batched inputs, a kernel that is no
-    scaled sum of primitives, dense noise): the plain path then runs exactly as before."""
+    sum of primitives behind input maps, dense noise): the plain path then runs exactly as before."""
     if not torch.is_grad_enabled():
         return None
     src = pm if pm is not None else pk
@@ -1479,12 +1479,8 @@ def _learnable_marginals(pm, pk, x, cache):
     noise_vec = K_z.differentiable_noise()
     if noise_vec is NotImplemented or (noise_vec is not None and noise_vec.dim() != 1):
         return None
-    view = k.input_scaled_view()
-    if view is None:
-        return None
-    kern, imap = view
-    tt = kern.tensor_terms()
-    if not tt:
+    groups = _map_groups(k)              # terms behind the same input map: one group is the plain case
+    if groups is None or not all(kern.tensor_terms() for kern, _ in groups):
         return None
     from . import autograd as _ag
 
@@ -1499,23 +1495,23 @@ def _learnable_marginals(pm, pk, x, cache):
                  or (noise_vec is not None and noise_vec.requires_grad) or (r is not None and r.requires_grad))
     if not learnable:
         return None
-    zin = z if imap is None else imap(z)
-    xin = x if imap is None else imap(x)
-    if (zin.requires_grad or xin.requires_grad) and xin.shape[-1] > 8:       # (behind a periodic map: twice the input dimension)
-        raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
-                                  "are implemented for at most 8 input dimensions")
+    mapped = [(kern, z if imap is None else imap(z), x if imap is None else imap(x)) for kern, imap in groups]
+    for _, zin, xin in mapped:
+        if (zin.requires_grad or xin.requires_grad) and xin.shape[-1] > 8:       # (behind a periodic map: twice the input dimension)
+            raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
+                                      "are implemented for at most 8 input dimensions")
     xd = x.detach()                  # (the plain path sees values only: the rows path stays open, one whitening serves mean and variance)
     own_cross = src.own_cross
 
     def run():
         return _posterior_parts(pm, K_z, k, z, xd, cache, own_cross)
 
-    mu, s = _ag.posterior_marginals(kern, zin, xin, r, noise_vec, run)
+    mu, s = _ag.posterior_marginals(mapped, r, noise_vec, run)
     mean = pm.m_i(x) + mu[..., None] if pm is not None else None
     vd = None
     if pk is not None:
         # the value of k(x, x) from the fused launch (the plain path's bits), its gradient from the same sum written in torch
-        kt = _ag.kdiag_terms(tt, xin)
+        kt = sum(_ag.kdiag_terms(kern.tensor_terms(), xin) for kern, _, xin in mapped)
         vd = (k.elwise(xd) + (kt - kt.detach())[..., None]) - s[..., None]
     return mean, vd
 

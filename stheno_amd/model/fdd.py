@@ -78,6 +78,8 @@ class FDD(Normal):
             k = p.kernel
             if k.input_scaled_view() is not None or isinstance(k, (_k.MultiOutputKernel, _k.DiffKernel)):
                 return KernelDense(k, xr, nz)      # K + noise fused, factorised in place (a derivative kernel: one gpk_kmat_diff launch)
+            if torch.is_tensor(xr) and xr.dim() == 2 and _k._map_groups(k) is not None:
+                return KernelDense(k, xr, nz)      # terms behind different input maps: one launch per group into the same buffer
             return k(xr) + nz
 
         Normal.__init__(self, lambda: p.mean(xr), var, var_diag=var_diag, mean_var=mean_var,

@@ -108,6 +108,8 @@ def _kernel_matrix(kernel, x, noise, round_once=False):
         return Dense(k64.to(torch.float32)) + noise
     if kernel.input_scaled_view() is not None or isinstance(kernel, _k.MultiOutputKernel):
         return KernelDense(kernel, x, noise)
+    if torch.is_tensor(x) and x.dim() == 2 and _k._map_groups(kernel) is not None:
+        return KernelDense(kernel, x, noise)       # (terms behind different input maps: built group by group into one buffer)
     return kernel(x) + noise
 
 

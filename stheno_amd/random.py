@@ -257,18 +257,22 @@ class Normal(RandomVector):
                 noise_vec, noise_mat = None, var.noise.mat       # a dense noise covariance: its cotangent is that of K
             if noise_vec is not None and noise_vec is not NotImplemented and noise_vec.dim() != r.dim() - 1:
                 noise_vec = NotImplemented
-            # k(x) = k0(m(x)) with k0 a sum of primitives (m: the division by per-dimension length scales, the periodic embedding, or
-            # none): the fused path runs k0 on the mapped inputs; torch differentiates the map (d/dl, d/dperiod, d/dx)
-            view = var.kernel.input_scaled_view() if torch.is_tensor(var.x) else None
-            if noise_vec is not NotImplemented and view is not None:
-                kern, imap = view
-                xin = var.x if imap is None else imap(var.x)
-                tt = kern.tensor_terms()
-                if tt is not None and _ag.needs_grad(tt, noise_vec, r, xin, noise_mat, kern.tensor_shapes()):
-                    if xin.requires_grad and torch.is_grad_enabled() and xin.shape[-1] > 8:
-                        raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
-                                                  "are implemented for at most 8 input dimensions")
-                    lp = _ag.gp_logpdf(kern, xin, noise_vec, r, noise_mat)
+            # k(x) = sum_g k_g(m_g(x)) with every k_g a sum of primitives (m_g: the division by per-dimension length scales, the periodic
+            # embedding, or none): the fused path runs k_g on the mapped inputs; torch differentiates the maps (d/dl, d/dperiod, d/dx).
+            # One group is the plain case; several go group by group through the unbatched log-density only.
+            from .kernels import _map_groups
+
+            groups = _map_groups(var.kernel) if torch.is_tensor(var.x) else None
+            if groups is not None and len(groups) > 1 and r.dim() != 2:
+                groups = None
+            if noise_vec is not NotImplemented and groups is not None and all(kern.tensor_terms() is not None for kern, _ in groups):
+                mapped = [(kern, var.x if imap is None else imap(var.x)) for kern, imap in groups]
+                if _ag.groups_need_grad(mapped, noise_vec, r, noise_mat):
+                    for _, xin in mapped:
+                        if xin.requires_grad and torch.is_grad_enabled() and xin.shape[-1] > 8:
+                            raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
+                                                      "are implemented for at most 8 input dimensions")
+                    lp = _ag.gp_logpdf(mapped, noise_vec, r, noise_mat)
                     if r.dim() == 3:
                         return lp, True
                     return (lp[0] if lp.shape[0] == 1 else lp), True
