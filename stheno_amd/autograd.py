@@ -20,6 +20,7 @@ per-dimension length scales, the periodic embedding), formed in torch by the cal
 the reductions against it run once per group, on that group's term table and mapped inputs, and each group's input gradient goes back to
 torch, which carries it through the map to its parameter and to ``x``.  One group is the plain case: the same launches as ever.
 """
+import collections
 import math
 
 import torch
@@ -37,15 +38,15 @@ def _as_t(v):
     return v if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
 
 
-def _pack(tt, shapes):
-    """``(kinds, params)`` of tensor terms and their shapes (``Kernel.tensor_terms()`` / ``tensor_shapes()``)."""
-    kinds = tuple(k for k, _, _ in tt)
-    params = [_as_t(v) for _, v, _ in tt] + [_as_t(s) for _, _, s in tt]
-    if shapes is not None and any(a is not None for a in shapes):
-        for k, a in zip(kinds, shapes):
+def _pack(rows):
+    """``(kinds, params)`` of a term table in its tensor view (``Kernel.tensor_table()``: rows ``(kind, variance, scale, shape)``)."""
+    kinds = tuple(row[0] for row in rows)
+    params = [_as_t(v) for _, v, _, _ in rows] + [_as_t(s) for _, _, s, _ in rows]
+    if any(a is not None for _, _, _, a in rows):
+        for k, _, _, a in rows:
             if k not in ops._LEARNABLE_SHAPE and torch.is_tensor(a) and a.requires_grad:
                 raise ValueError(f"the shape parameter of a {k!r} term is not learnable")
-        params += [_as_t(0.0 if a is None else a) for a in shapes]
+        params += [_as_t(0.0 if a is None else a) for _, _, _, a in rows]
     return kinds, params
 
 
@@ -54,24 +55,31 @@ def _pack_groups(kernels):
     parameter lists (``_pack``) group after group."""
     layout, params = [], []
     for kern in kernels:
-        kinds, pr = _pack(kern.tensor_terms(), kern.tensor_shapes())
+        kinds, pr = _pack(kern.tensor_table())
         layout.append((kinds, len(pr)))
         params.extend(pr)
     return tuple(layout), params
 
 
+#: one group inside an autograd function: its kinds, the host descriptor for the fused kernels and the parameters' values (``_unpack``),
+#: the parameters' ``(device, dtype)`` and the group's input tensors
+_Group = collections.namedtuple("_Group", "kinds terms values meta inputs")
+
+
 def _split_groups(layout, tensors, per_group=1):
     """The tensors behind ``layout`` in an autograd function's arguments: ``per_group`` input tensors per group first, then the flat
-    parameters group after group.  Returns ``[(kinds, inputs, params)]``."""
+    parameters group after group.  Returns one ``_Group`` per group."""
     pos = per_group * len(layout)
     out = []
     for i, (kinds, npar) in enumerate(layout):
-        out.append((kinds, tensors[per_group * i: per_group * (i + 1)], tensors[pos: pos + npar]))
+        params = tensors[pos: pos + npar]
+        out.append(_Group(kinds, *_unpack(kinds, params), [(p.device, p.dtype) for p in params], tensors[per_group * i: per_group * (i + 1)]))
         pos += npar
     return out
 
 
-def _check_input_dims(u):
+def check_input_dims(u):
+    """The input-gradient kernels cover at most 8 input dimensions (as the fused kernels see them: behind a periodic map, twice)."""
     if u.shape[-1] > 8:
         raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
                                   "are implemented for at most 8 input dimensions")
@@ -110,10 +118,18 @@ def _cotangent(be, kinv_lower, alpha, g):
 def _grad_inputs(be, terms, x, G):
     """``d logpdf / dx`` (n, D) from the explicit cotangent: ``dx_i = 2 sum_j G_ij dk(x_i, x_j)/dx_i`` (both arguments of
     ``k(x, x)`` move with ``x``)."""
-    if x.shape[-1] > 8:
-        raise NotImplementedError("gradients with respect to the inputs are implemented for at most 8 input dimensions")
+    check_input_dims(x)
     _, _, gx = be.kmat_vjp_dense(terms, x, x, G, want_gradx=True)
     return 2.0 * gx
+
+
+def _inverse_parts(be, chol, w):
+    """``(W, lower triangle of K^{-1}, alpha)`` from the stored factor and ``w = L^{-1} r`` (n, C): ``W = L^{-1}`` (lower triangular),
+    ``K^{-1} = W^T W``, ``alpha = K^{-1} r = W^T w``."""
+    W = chol.inverse_lower()                                                             # N^3/3 flops
+    kinv = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)    # N^3/3 flops
+    cols = [be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(w.shape[1])]
+    return W, kinv, (cols[0][:, None] if len(cols) == 1 else torch.stack(cols, dim=1))
 
 
 class _GPLogpdf(torch.autograd.Function):
@@ -123,23 +139,19 @@ class _GPLogpdf(torch.autograd.Function):
         then their parameters group after group -- variances, scales (and shape parameters: ``_pack``; scalar tensors, any device);
         ``noise_vec`` (n,) or None; ``noise_mat`` (n, n) dense noise covariance or None; ``r = y - mean`` (n, C).  Returns (C,)."""
         be = ops.get_backend()
-        groups, metas = [], []
-        for kinds, (u,), params in _split_groups(layout, tensors):
-            terms, values = _unpack(kinds, params)
-            groups.append((kinds, terms, values, u))
-            metas.append([(p.device, p.dtype) for p in params])
+        groups = _split_groups(layout, tensors)
         n, C = r.shape
         # the first group writes the lower triangle with the diagonal additions, the others add to it (as `Sum.pairwise` does)
-        k = be.kmat(groups[0][1], groups[0][3], None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
-        for _, terms, _, u in groups[1:]:
-            be.kmat(terms, u, None, lower=True, out=k, accumulate=True)
+        k = be.kmat(groups[0].terms, groups[0].inputs[0], None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
+        for grp in groups[1:]:
+            be.kmat(grp.terms, grp.inputs[0], None, lower=True, out=k, accumulate=True)
         if noise_mat is not None:
             k += noise_mat                                       # (only the lower triangle is read from here on)
         chol = Chol.factor_(k)
         w = chol.solve(r)                                        # L^{-1} r
         _, ss = be.colreduce(w, want_ss=True)
         out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
-        ctx.chol, ctx.w, ctx.groups, ctx.param_metas = chol, w, groups, metas
+        ctx.chol, ctx.w, ctx.groups = chol, w, groups
         ctx.has_noise, ctx.has_noise_mat = noise_vec is not None, noise_mat is not None
         return out
 
@@ -153,40 +165,38 @@ class _GPLogpdf(torch.autograd.Function):
             raise NotImplementedError("backward through logpdf supports at most 8 columns of y")
         need_u = [ctx.needs_input_grad[4 + i] for i in range(ng)]
         need_nm = ctx.has_noise_mat and ctx.needs_input_grad[2]
-        for (_, _, _, u), need in zip(groups, need_u):
+        for grp, need in zip(groups, need_u):
             if need:
-                _check_input_dims(u)
+                check_input_dims(grp.inputs[0])
         g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
-        # W = L^{-1} (lower triangular), K^{-1} = W^T W, A = K^{-1} r = W^T w
-        W = chol.inverse_lower()                                              # N^3/3 flops
-        kinv = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)   # N^3/3 flops
-        alpha = torch.stack([be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(C)], dim=1)
+        _, kinv, alpha = _inverse_parts(be, chol, w)
         # several groups of which one passes a gradient to its inputs: every group reads the explicit cotangent once, its sums and its
         # input gradient out of the same pass; otherwise the implicit form, one pass over the lower triangle of K^{-1} per group
         dense = ng > 1 and any(need_u)
         S, grad_us, diag_g = [None] * ng, [None] * ng, None
         if not dense:
-            for i, (_, terms, _, u) in enumerate(groups):
-                S[i], _, dg = be.kmat_vjp(terms, u, kinv, alpha, g)
+            for i, grp in enumerate(groups):
+                S[i], _, dg = be.kmat_vjp(grp.terms, grp.inputs[0], kinv, alpha, g)
                 if i == 0:
                     diag_g = dg                                  # (the cotangent's diagonal: the same from every group)
         grad_nm = None
         if any(need_u) or need_nm:
             G = _cotangent(be, kinv, alpha, g)                   # explicit, in the buffer of K^{-1}
-            for i, (_, terms, _, u) in enumerate(groups):
+            for i, grp in enumerate(groups):
+                u = grp.inputs[0]
                 if dense:
-                    S[i], _, gx = be.kmat_vjp_dense(terms, u, u, G, want_gradx=need_u[i])
+                    S[i], _, gx = be.kmat_vjp_dense(grp.terms, u, u, G, want_gradx=need_u[i])
                     if need_u[i]:
                         grad_us[i] = 2.0 * gx
                 elif need_u[i]:
-                    grad_us[i] = _grad_inputs(be, terms, u, G)
+                    grad_us[i] = _grad_inputs(be, grp.terms, u, G)
             if dense:
                 diag_g = torch.diagonal(G).clone()
             if need_nm:
                 grad_nm = G                                      # d/d noise matrix: the cotangent of K itself
         grads = []
-        for (kinds, _, values, _), S_g, meta in zip(groups, S, ctx.param_metas):
-            grads += _param_grads(kinds, values, S_g, meta)
+        for grp, S_g in zip(groups, S):
+            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype))
         grad_noise = diag_g if ctx.has_noise else None
         return (grad_r, grad_noise, grad_nm, None, *grad_us, *grads)
@@ -199,38 +209,35 @@ class _GPLogpdfBatched(torch.autograd.Function):
     backward walks the batch: ``K_b^{-1}`` from the stored factor of entry b, one ``gpk_kmat_vjp`` pass, sums over b."""
 
     @staticmethod
-    def forward(ctx, x, r, noise_vec, kinds, *params):
+    def forward(ctx, r, noise_vec, layout, *tensors):
+        """``layout`` / ``tensors`` as in ``_GPLogpdf``, ONE group: its inputs ``x`` (B, N, D), then its parameters."""
         be = ops.get_backend()
-        nt = len(kinds)
-        terms, values = _unpack(kinds, params)
+        (grp,) = _split_groups(layout, tensors)
+        x, terms = grp.inputs[0], grp.terms
         n = r.shape[-2]
         k = be.kmat(terms, x, None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
         chol = Chol.factor_(k)
         w = chol.solve(r)                                        # (B, N, 1)
         _, ss = be.colreduce(w, want_ss=True)                    # (B, 1)
         out = -(chol.logdet() + n * LOG_2_PI + ss[..., 0]) / 2   # (B,)
-        ctx.chol, ctx.w, ctx.x, ctx.terms = chol, w, x, terms
-        ctx.nt, ctx.has_noise = nt, noise_vec is not None
-        ctx.param_meta = [(p.device, p.dtype) for p in params]
-        ctx.values, ctx.kinds = values, kinds
+        ctx.chol, ctx.w, ctx.group, ctx.has_noise = chol, w, grp, noise_vec is not None
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         be = ops.get_backend()
-        chol, w, x, terms, nt = ctx.chol, ctx.w, ctx.x, ctx.terms, ctx.nt
+        chol, w, grp = ctx.chol, ctx.w, ctx.group
+        x, terms = grp.inputs[0], grp.terms
         B = x.shape[0]
         g_host = [float(v) for v in grad_out.reshape(-1).tolist()]            # host sync: B scalars
         S_tot = None
         grad_r = torch.empty_like(w)
         grad_noise = torch.empty(w.shape[:-1], dtype=w.dtype, device=w.device) if ctx.has_noise else None
-        grad_x = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        grad_x = torch.empty_like(x) if ctx.needs_input_grad[3] else None
         for b in range(B):
             sl = lambda t: None if t is None else t[b:b + 1]      # noqa: E731
             cb = Chol(chol.l[b], sl(chol.dinv), sl(chol.info))                 # entry b as an unbatched factor (views)
-            W = cb.inverse_lower()
-            kinv = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)
-            alpha = be.colreduce(W, w[b, :, 0], want_dot=True, want_ss=False)[0][:, None]
+            _, kinv, alpha = _inverse_parts(be, cb, w[b])
             S, _, diag_g = be.kmat_vjp(terms, x[b], kinv, alpha, [g_host[b]])
             S_tot = S if S_tot is None else S_tot + S
             grad_r[b] = -alpha * g_host[b]
@@ -238,8 +245,7 @@ class _GPLogpdfBatched(torch.autograd.Function):
                 grad_noise[b] = diag_g
             if grad_x is not None:
                 grad_x[b] = _grad_inputs(be, terms, x[b], _cotangent(be, kinv, alpha, [g_host[b]]))
-        grads = _param_grads(ctx.kinds, ctx.values, S_tot, ctx.param_meta)
-        return (grad_x, grad_r, grad_noise, None, *grads)
+        return (grad_r, grad_noise, None, grad_x, *_param_grads(grp.kinds, grp.values, S_tot, grp.meta))
 
 
 class _JointLogpdf(torch.autograd.Function):
@@ -279,12 +285,10 @@ class _JointLogpdf(torch.autograd.Function):
         need_u = [ctx.needs_input_grad[6 + a] for a in range(nu)]
         for u, need in zip(us, need_u):
             if need:
-                _check_input_dims(u)
+                check_input_dims(u)
         g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
-        W = chol.inverse_lower()
-        G = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)      # K^{-1}, lower triangle
-        alpha = torch.stack([be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(w.shape[1])], dim=1)
-        G = _cotangent(be, G, alpha, g)
+        _, kinv, alpha = _inverse_parts(be, chol, w)
+        G = _cotangent(be, kinv, alpha, g)
         offs = [0]
         for rows in ctx.sizes:
             offs.append(offs[-1] + rows)
@@ -338,10 +342,10 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
             if groups is None:
                 return None
             for kg, imap in groups:
-                tt = kg.tensor_terms()
-                if tt is None:
+                rows = kg.tensor_table()
+                if rows is None:
                     return None
-                kd, pr = _pack(tt, kg.tensor_shapes())
+                kd, pr = _pack(rows)
                 layout.append((i, j, kd, len(pr), mapped(i, imap), mapped(j, imap)))
                 params.extend(pr)
     if not torch.is_grad_enabled() or not (any(p.requires_grad for p in params) or any(u.requires_grad for u in us) or r.requires_grad
@@ -349,7 +353,7 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
         return None
     for u in us:
         if u.requires_grad:
-            _check_input_dims(u)
+            check_input_dims(u)
 
     def build():
         return mok.pairwise(x, None, lower=True, diag_add=eps, diag_vec=noise_vec)
@@ -357,24 +361,9 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
     return _JointLogpdf.apply(r, noise_vec, build, tuple(xi.shape[0] for _, xi in parts), tuple(layout), len(us), *us, *params)
 
 
-def _any_shape_grad(shapes):
-    return shapes is not None and any(torch.is_tensor(a) and a.requires_grad for a in shapes)
-
-
-def needs_grad(tensor_terms, noise_vec, r, x=None, noise_mat=None, shapes=None):
-    """``shapes``: the shape parameters beside ``tensor_terms`` (``Kernel.tensor_shapes()``), learnable like the scales."""
-    if not torch.is_grad_enabled():
-        return False
-    if _any_shape_grad(shapes):
-        return True
-    if x is not None and torch.is_tensor(x) and x.requires_grad:
-        return True
-    if noise_mat is not None and noise_mat.requires_grad:
-        return True
-    for _, v, s in tensor_terms:
-        if (torch.is_tensor(v) and v.requires_grad) or (torch.is_tensor(s) and s.requires_grad):
-            return True
-    return (noise_vec is not None and noise_vec.requires_grad) or r.requires_grad
+def table_requires_grad(rows):
+    """Does a term table in its tensor view (``Kernel.tensor_table()``) carry a gradient -- on a variance, a scale or a shape parameter?"""
+    return torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for row in rows for p in row[1:])
 
 
 def kernel_requires_grad(kernel, _depth=0):
@@ -384,9 +373,9 @@ def kernel_requires_grad(kernel, _depth=0):
 
     if _depth > 16:
         return False
-    tt = kernel.tensor_terms() if isinstance(kernel, _k.Kernel) else None
-    if tt is not None:
-        return _any_shape_grad(kernel.tensor_shapes()) or any((torch.is_tensor(v) and v.requires_grad) or (torch.is_tensor(s) and s.requires_grad) for _, v, s in tt)
+    rows = kernel.tensor_table() if isinstance(kernel, _k.Kernel) else None
+    if rows is not None:
+        return table_requires_grad(rows)
     if isinstance(kernel, _k.MultiOutputKernel):
         ks = kernel.kernels
         return any(kernel_requires_grad(ks[p], _depth + 1) for p in kernel.pids)
@@ -398,19 +387,22 @@ def kernel_requires_grad(kernel, _depth=0):
     return False
 
 
-def groups_need_grad(groups, noise_vec, r, noise_mat=None):
-    """``needs_grad`` for a kernel given as groups ``[(k_g, u_g)]``: any group's terms, shape parameters or mapped inputs."""
-    return any(needs_grad(kern.tensor_terms(), noise_vec, r, u, noise_mat, kern.tensor_shapes()) for kern, u in groups)
+def groups_need_grad(groups, *others):
+    """Does anything behind a kernel given as groups ``[(k_g, u_g)]`` require a gradient: a group's term table or mapped inputs, or one
+    of the ``others`` (noise, residual, inducing inputs; ``None`` entries are skipped)?"""
+    if not torch.is_grad_enabled():
+        return False
+    return (any(table_requires_grad(kern.tensor_table()) or (torch.is_tensor(u) and u.requires_grad) for kern, u in groups)
+            or any(t is not None and t.requires_grad for t in others))
 
 
 def gp_logpdf(groups, noise_vec, r, noise_mat=None):
     """Differentiable log-density of ``r = y - m(x)`` under ``N(0, sum_g k_g(u_g) + diag(noise_vec) + noise_mat + eps I)``; ``groups``
     = ``[(k_g, u_g)]``, every ``k_g`` a sum of primitives on its (mapped) inputs ``u_g``.  Batched inputs: one group."""
-    if groups[0][1].dim() == 3:
-        (kernel, x), = groups
-        kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
-        return _GPLogpdfBatched.apply(x, r, noise_vec, kinds, *params)
     layout, params = _pack_groups([kern for kern, _ in groups])
+    if groups[0][1].dim() == 3:
+        (x,) = [u for _, u in groups]
+        return _GPLogpdfBatched.apply(r, noise_vec, layout, x, *params)
     return _GPLogpdf.apply(r, noise_vec, noise_mat, layout, *[u for _, u in groups], *params)
 
 
@@ -433,12 +425,14 @@ def gp_logpdf(groups, noise_vec, r, noise_mat=None):
 # ---------------------------------------------------------------------------------------------
 class _SparseELBO(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, z, r, noise_vec, tau, kinds, *params):
+    def forward(ctx, r, noise_vec, tau, layout, *tensors):
+        """``layout`` / ``tensors`` as in ``_PosteriorMarginals``, ONE group: its inputs ``x`` (N, D) and ``z`` (M, D), then its
+        parameters; ``tau``: 1 (VFE), 0 (DTC), -1 (FITC)."""
         from .model.observations import _syrk_lower
 
         be = ops.get_backend()
-        nt = len(kinds)
-        terms, values = _unpack(kinds, params)
+        (grp,) = _split_groups(layout, tensors, 2)
+        (x, z), terms = grp.inputs, grp.terms
         n, m = x.shape[0], z.shape[0]
         d = noise_vec.detach()
         v = be.kmat(terms, z, x)                                               # K_zx
@@ -463,19 +457,16 @@ class _SparseELBO(torch.autograd.Function):
         _, uu = be.colreduce(u, want_ss=True)
         elbo = -0.5 * (torch.log(2 * math.pi * d).sum() + chol_a.logdet() + (r[:, 0] ** 2 / d).sum() - uu[0]
                        + tau * (corr / d).sum())
-        ctx.saved = dict(x=x, z=z, r=r, d=d, s=s, v=v, q=q, corr=corr, a=a, u=u, chol_z=chol_z, chol_a=chol_a,
-                         terms=terms, tau=tau, nt=nt, fitc=fitc)
-        ctx.param_meta = [(p_.device, p_.dtype) for p_ in params]
-        ctx.values = values
-        ctx.kinds = kinds
+        ctx.saved = dict(r=r, d=d, s=s, v=v, q=q, corr=corr, a=a, u=u, chol_z=chol_z, chol_a=chol_a, tau=tau, fitc=fitc)
+        ctx.group = grp
         return elbo
 
     @staticmethod
     def backward(ctx, grad_out):
         be = ops.get_backend()
-        sv = ctx.saved
-        x, z, r, d, s, v, q, corr = sv["x"], sv["z"], sv["r"], sv["d"], sv["s"], sv["v"], sv["q"], sv["corr"]
-        terms, tau, nt = sv["terms"], sv["tau"], sv["nt"]
+        sv, grp = ctx.saved, ctx.group
+        r, d, s, v, q, corr, tau = sv["r"], sv["d"], sv["s"], sv["v"], sv["q"], sv["corr"], sv["tau"]
+        (x, z), terms, kinds, nt = grp.inputs, grp.terms, grp.kinds, len(grp.kinds)
         m = z.shape[0]
         eye = torch.eye(m, dtype=x.dtype, device=x.device)
         w_a = sv["chol_a"].inverse_lower()                                     # L_A^{-1}
@@ -488,7 +479,7 @@ class _SparseELBO(torch.autograd.Function):
         h = be.gemm(w_z, tau * eye - a_inv, a_kmajor=False, b_kmajor=True)     # L^{-T} (tau I - A^{-1})
         w = be.colreduce(w_z, c, want_dot=True, want_ss=False)[0]              # L^{-T} c
         g_k = be.gemm(h, v, a_kmajor=True, b_kmajor=False)                     # M x N, the one big GEMM
-        need_z, need_x = ctx.needs_input_grad[1], ctx.needs_input_grad[0]
+        need_x, need_z = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
         fitc = sv["fitc"]
         s_k, colsum, gz_k = be.kmat_vjp_dense(terms, z, x, g_k, colscale=s, w=w, b=b, want_colsum=True,
                                               want_gradx=need_z and not fitc)
@@ -525,50 +516,35 @@ class _SparseELBO(torch.autograd.Function):
         S = s_k + s_kz
         # through k(x_j, x_j) (VFE: trace term; FITC: the effective noise): stationary terms are constant there
         g_kd = g_d if fitc else -0.5 * tau / d
-        variances, scales, alphas = ctx.values
+        variances, scales, _ = grp.values
         go = grad_out.to(x.dtype)
-        grads_v, grads_s = [], []
-        for t in range(nt):
-            gv, gs = S[t, 0], -2.0 * variances[t] / scales[t] * S[t, 1]
-            if tau or fitc:
-                if ctx.kinds[t] == "linear":
+        # through the kernel matrices: the sums' own formulas, left where they were computed -- the diagonal's share is added term by
+        # term BEFORE the output cotangent multiplies (the order the sums have always been taken in); shape parameters get none: every
+        # stationary kind is 1 on the diagonal, whatever its shape
+        gr = _param_grads(kinds, grp.values, S, [(S.device, S.dtype)] * len(grp.meta))
+        if tau or fitc:
+            for t in range(nt):
+                if kinds[t] == "linear":
                     xx = ((x * x).sum(-1) * g_kd).sum() / scales[t] ** 2
-                    gv, gs = gv + xx, gs - 2.0 * variances[t] / scales[t] * xx
+                    gr[t], gr[nt + t] = gr[t] + xx, gr[nt + t] - 2.0 * variances[t] / scales[t] * xx
                     if need_x:      # k(x_j, x_j) = v |x_j|^2 / l^2 moves with x_j (stationary terms are constant there)
                         gx_k = gx_k + (2.0 * variances[t] / scales[t] ** 2) * g_kd[:, None] * x
                 else:
-                    gv = gv + g_kd.sum()
-            grads_v.append(gv * go)
-            grads_s.append(gs * go)
-        # (shape parameters: through the kernel matrices only -- every stationary kind is 1 on the diagonal, whatever its shape)
-        grads_a = [] if alphas is None else [(variances[t] * S[t, 2] * go) if ctx.kinds[t] in ops._LEARNABLE_SHAPE else None for t in range(nt)]
-        grads = [None if g_ is None else g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(grads_v + grads_s + grads_a, ctx.param_meta)]
+                    gr[t] = gr[t] + g_kd.sum()
+        grads = [None if g_ is None else (g_ * go).to(device=dev, dtype=dt) for g_, (dev, dt) in zip(gr, grp.meta)]
         grad_z = (gz_k + 2.0 * gz_kz) * go if need_z else None
         grad_x = gx_k * go if need_x else None
-        grad_r = (-b * go)[:, None] if ctx.needs_input_grad[2] else None
-        grad_noise = g_d * go if ctx.needs_input_grad[3] else None
-        return (grad_x, grad_z, grad_r, grad_noise, None, None, *grads)
-
-
-def elbo_needs_grad(tensor_terms, noise_vec, z, r, x=None, shapes=None):
-    if not torch.is_grad_enabled():
-        return False
-    if _any_shape_grad(shapes):
-        return True
-    if x is not None and torch.is_tensor(x) and x.requires_grad:
-        return True
-    for _, v, s in tensor_terms:
-        if (torch.is_tensor(v) and v.requires_grad) or (torch.is_tensor(s) and s.requires_grad):
-            return True
-    return bool(noise_vec.requires_grad or z.requires_grad or r.requires_grad)
+        grad_r = (-b * go)[:, None] if ctx.needs_input_grad[0] else None
+        grad_noise = g_d * go if ctx.needs_input_grad[1] else None
+        return (grad_r, grad_noise, None, None, grad_x, grad_z, *grads)
 
 
 def sparse_elbo(kernel, x, z, noise_vec, r, method):
     """Differentiable VFE / FITC / DTC bound for ``r = y - m(x)`` with inducing inputs ``z``."""
     if method not in ("vfe", "fitc", "dtc"):
         raise ValueError(f'Invalid approximation method "{method}".')
-    kinds, params = _pack(kernel.tensor_terms(), kernel.tensor_shapes())
-    return _SparseELBO.apply(x, z, r, noise_vec, {"vfe": 1.0, "dtc": 0.0, "fitc": -1.0}[method], kinds, *params)
+    layout, params = _pack_groups([kernel])
+    return _SparseELBO.apply(r, noise_vec, {"vfe": 1.0, "dtc": 0.0, "fitc": -1.0}[method], layout, x, z, *params)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -599,12 +575,7 @@ class _PosteriorMarginals(torch.autograd.Function):
         terms; ``tensors`` = per group ``x`` / ``xs`` as its fused kernels see them (behind the group's input map), then the groups'
         parameters; ``r`` (N, 1) or None (marginal variances only: ``mu`` comes back as zeros)."""
         chol, w, v, mu, s = run()
-        groups, metas = [], []
-        for kinds, (x, xs), params in _split_groups(layout, tensors, 2):
-            terms, values = _unpack(kinds, params)
-            groups.append((kinds, terms, values, x, xs))
-            metas.append([(p.device, p.dtype) for p in params])
-        ctx.groups, ctx.param_metas = groups, metas
+        ctx.groups = _split_groups(layout, tensors, 2)
         ctx.chol, ctx.w, ctx.v = chol, w, v
         ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
         ctx.set_materialize_grads(False)
@@ -617,7 +588,7 @@ class _PosteriorMarginals(torch.autograd.Function):
         be = ops.get_backend()
         chol, v, groups = ctx.chol, ctx.v, ctx.groups
         ng = len(groups)
-        x0, xs0 = groups[0][3], groups[0][4]
+        x0, xs0 = groups[0].inputs
         n, ns = x0.shape[0], xs0.shape[0]
         dt, dev = x0.dtype, x0.device
         gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
@@ -626,12 +597,12 @@ class _PosteriorMarginals(torch.autograd.Function):
             gs = None
         need_x = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
         need_xs = [ctx.needs_input_grad[5 + 2 * i] for i in range(ng)]
-        npar = sum(len(m) for m in ctx.param_metas)
+        npar = sum(len(grp.meta) for grp in groups)
         if gm is None and gs is None:
             return (None,) * (4 + 2 * ng + npar)
-        for (_, _, _, x, _), nx, nxs in zip(groups, need_x, need_xs):
+        for grp, nx, nxs in zip(groups, need_x, need_xs):
             if nx or nxs:
-                _check_input_dims(x)
+                check_input_dims(grp.inputs[0])
         transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
         alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
         bm = beta = None
@@ -651,7 +622,8 @@ class _PosteriorMarginals(torch.autograd.Function):
         cs = 2.0 * gs if gs is not None else None
         S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
         g_t = None
-        for i, (_, terms, _, x, xs) in enumerate(groups):
+        for i, grp in enumerate(groups):
+            terms, (x, xs) = grp.terms, grp.inputs
             S[i], _, grad_x[i] = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
                                                    want_gradx=need_x[i])
             if need_xs[i]:
@@ -680,8 +652,8 @@ class _PosteriorMarginals(torch.autograd.Function):
             kinv = zeros(n, n)
         A = torch.stack(cols, dim=1)
         diag_g = None
-        for i, (_, terms, _, x, _) in enumerate(groups):
-            S_k, _, dg = be.kmat_vjp(terms, x, kinv, A, g)
+        for i, grp in enumerate(groups):
+            S_k, _, dg = be.kmat_vjp(grp.terms, grp.inputs[0], kinv, A, g)
             S[i] = S[i] + S_k
             if i == 0:
                 diag_g = dg                                           # (the cotangent's diagonal: the same from every group)
@@ -689,12 +661,12 @@ class _PosteriorMarginals(torch.autograd.Function):
             if kinv.stride(0) == 0:
                 kinv = torch.zeros((n, n), dtype=dt, device=dev)
             G = _cotangent(be, kinv, A, g)                            # once, in the buffer of S
-            for i, (_, terms, _, x, _) in enumerate(groups):
+            for i, grp in enumerate(groups):
                 if need_x[i]:
-                    grad_x[i] = grad_x[i] + _grad_inputs(be, terms, x, G)
+                    grad_x[i] = grad_x[i] + _grad_inputs(be, grp.terms, grp.inputs[0], G)
         grads = []
-        for (kinds, _, values, _, _), S_g, meta in zip(groups, S, ctx.param_metas):
-            grads += _param_grads(kinds, values, S_g, meta)
+        for grp, S_g in zip(groups, S):
+            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
         grad_r = beta[:, None] if (beta is not None and ctx.needs_input_grad[0]) else None
         grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[1]) else None
         inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]

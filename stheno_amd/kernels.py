@@ -118,6 +118,11 @@ def _is_vector_scale(scale):
     return np.ndim(scale) > 0 and np.size(scale) > 1
 
 
+def _as_is(v):
+    """The conversion of the tensor views (``Kernel._table``): parameters are stored as ``_as_param`` left them."""
+    return v
+
+
 def _as_param(v):
     """Keep scalar tensors (they may carry an autograd graph: learnable hyper-parameters),
     turn everything else into a float."""
@@ -132,30 +137,48 @@ def _as_param(v):
 # kernels
 # ---------------------------------------------------------------------------
 class Kernel:
-    """Base class.  A kernel that is a sum of stretched/scaled primitives exposes it as
-    ``terms()`` -> list of ``(kind, variance, scale)``; other kernels override
-    ``pairwise`` / ``elwise``.  Shape parameters (``RQ``'s alpha, ``Delta``'s epsilon) travel beside the terms: ``shapes()`` has one entry per term,
-    ``None`` for the kinds without one."""
+    """Base class.  A kernel that is a sum of stretched/scaled primitives describes itself in ONE method, ``_table(conv)`` -> rows
+    ``(kind, variance, scale, shape)`` (``shape``: ``RQ``'s alpha, ``Delta``'s epsilon, ``None`` for the kinds without one); other
+    kernels leave it at ``None`` and override ``pairwise`` / ``elwise``.  ``conv`` is applied to the node's OWN parameter before it is
+    combined with its children's: ``_as_float`` for the float views (Python doubles: what the fused launches are handed),
+    ``_as_is`` for the tensor views (the caller's tensors, so gradients can flow back to them).  The four public views below are
+    columns of that table; one call visits every leaf of the expression once."""
 
     stationary = False
 
-    def terms(self):
+    def _table(self, conv):
         return None
 
+    def terms(self):
+        """``[(kind, variance, scale)]`` in floats; None when the kernel is no sum of primitives, ``[]`` for the zero kernel."""
+        rows = self._table(_as_float)
+        return None if rows is None else [row[:3] for row in rows]
+
+    def tensor_table(self):
+        """The whole table in its tensor view (what the differentiable paths pack: ``autograd._pack``), or None."""
+        return self._table(_as_is)
+
     def tensor_terms(self):
-        """Like ``terms()`` but variances / scales stay scalar tensors where the user gave
-        tensors (so gradients can flow back to them)."""
-        return self.terms()
+        """Like ``terms()`` but variances / scales stay scalar tensors where the user gave tensors."""
+        rows = self.tensor_table()
+        return None if rows is None else [row[:3] for row in rows]
 
     def shapes(self):
         """One shape parameter per entry of ``terms()`` (a float; ``None`` for kinds without one), or None like ``terms()``."""
-        t = self.terms()
-        return None if t is None else [None] * len(t)
+        rows = self._table(_as_float)
+        return None if rows is None else [row[3] for row in rows]
 
     def tensor_shapes(self):
         """Like ``shapes()``, beside ``tensor_terms()``: a tensor the user gave stays that tensor."""
-        t = self.tensor_terms()
-        return None if t is None else [None] * len(t)
+        rows = self.tensor_table()
+        return None if rows is None else [row[3] for row in rows]
+
+    def _kterms(self, factor=1.0):
+        """The float view as the backends' descriptor, every variance times ``factor``; None when the kernel is no sum of primitives."""
+        rows = self._table(_as_float)
+        if rows is None:
+            return None
+        return ops.KTerms([(kind, var * factor, s) for kind, var, s, _ in rows], [row[3] for row in rows])
 
     def num_outputs(self, x):
         return num_elements(x)
@@ -174,24 +197,23 @@ class Kernel:
         ``diag_add`` / ``diag_vec`` are added to the diagonal in the same pass.  ``out``: a
         (strided) matrix view to write into (blocks of a multi-output kernel matrix); ``accumulate``: add to it
         (the groups of a sum whose terms see differently mapped inputs)."""
-        t = self.terms()
-        if t is None:
+        kt = self._kterms()
+        if kt is None:
             raise NotImplementedError(f"pairwise evaluation is not implemented for {type(self).__name__}")
         x = uprank(x)
         y = None if y is None else uprank(y)
         if isinstance(x, MultiInput) or isinstance(y, MultiInput):
             raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
-        return ops.get_backend().kmat(ops.KTerms(t, self.shapes()), x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out,
-                                      accumulate=accumulate)
+        return ops.get_backend().kmat(kt, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out, accumulate=accumulate)
 
     def elwise(self, x, y=None, *, cache=None):
         """``k(x_i, x_i)`` as a column (..., N, 1)."""
         if y is not None and y is not x:
             raise NotImplementedError("elwise is implemented for identical inputs")
-        t = self.terms()
-        if t is None:
+        kt = self._kterms()
+        if kt is None:
             raise NotImplementedError(f"elwise evaluation is not implemented for {type(self).__name__}")
-        return ops.get_backend().kdiag(ops.KTerms(t, self.shapes()), uprank(x))[..., None]
+        return ops.get_backend().kdiag(kt, uprank(x))[..., None]
 
     def __call__(self, x, y=None):
         """``k(x)`` / ``k(x, y)`` as a ``Dense`` matrix (lazily materialised for ``k(x)``)."""
@@ -261,9 +283,10 @@ class Kernel:
 
 class _Primitive(Kernel):
     kind = None
+    shape = None          # the kind's shape parameter, for those that have one
 
-    def terms(self):
-        return [(self.kind, 1.0, 1.0)]
+    def _table(self, conv):
+        return [(self.kind, 1.0, 1.0, None if self.shape is None else conv(self.shape))]
 
     def __repr__(self):
         return f"{type(self).__name__}()"
@@ -291,11 +314,7 @@ class RQ(_Primitive):
         if not _as_float(self.alpha) > 0:
             raise ValueError("the shape parameter alpha of RQ must be positive")
 
-    def shapes(self):
-        return [_as_float(self.alpha)]
-
-    def tensor_shapes(self):
-        return [self.alpha]
+    shape = property(lambda self: self.alpha)
 
     def __repr__(self):
         return f"RQ({_as_float(self.alpha):g})"
@@ -315,11 +334,7 @@ class Delta(_Primitive):
         if not self.epsilon > 0:
             raise ValueError("the epsilon of Delta must be positive")
 
-    def shapes(self):
-        return [self.epsilon]
-
-    def tensor_shapes(self):
-        return [self.epsilon]
+    shape = property(lambda self: self.epsilon)
 
     def __repr__(self):
         return f"Delta({self.epsilon:g})"
@@ -357,7 +372,7 @@ class OneKernel(_Primitive):
 class ZeroKernel(Kernel):
     stationary = True
 
-    def terms(self):
+    def _table(self, conv):
         return []
 
     def pairwise(self, x, y=None, *, out=None, diag_add=0.0, diag_vec=None, **kw):
@@ -389,19 +404,9 @@ class Scaled(Kernel):
     def num_outputs(self, x):
         return self.k.num_outputs(x)
 
-    def terms(self):
-        t = self.k.terms()
-        return None if t is None else [(kind, var * _as_float(self.v), s) for kind, var, s in t]
-
-    def tensor_terms(self):
-        t = self.k.tensor_terms()
-        return None if t is None else [(kind, var * self.v, s) for kind, var, s in t]
-
-    def shapes(self):
-        return self.k.shapes()
-
-    def tensor_shapes(self):
-        return self.k.tensor_shapes()
+    def _table(self, conv):
+        rows = self.k._table(conv)
+        return None if rows is None else [(kind, var * conv(self.v), s, a) for kind, var, s, a in rows]
 
     def input_scaled_view(self):
         v = self.k.input_scaled_view()
@@ -436,17 +441,8 @@ class Stretched(Kernel):
         self.k, self.scale = k, scale
         self.stationary = k.stationary
 
-    def terms(self):
-        return [(kind, var, s * _as_float(self.scale)) for kind, var, s in self.k.terms()]
-
-    def tensor_terms(self):
-        return [(kind, var, s * self.scale) for kind, var, s in self.k.tensor_terms()]
-
-    def shapes(self):
-        return self.k.shapes()
-
-    def tensor_shapes(self):
-        return self.k.tensor_shapes()
+    def _table(self, conv):
+        return [(kind, var, s * conv(self.scale), a) for kind, var, s, a in self.k._table(conv)]
 
     def __repr__(self):
         return f"({self.k!r} > {self.scale})"
@@ -618,25 +614,18 @@ def _same_param(a, b):
     return (a is b) if (torch.is_tensor(a) or torch.is_tensor(b)) else (a == b)
 
 
-def _merge(terms, shapes):
-    """Add up the variances of terms with the same primitive, the same length scale and the same shape parameter (``p + p``
-    has the kernel ``4 k``, not four terms; the fused kernels take at most 8 distinct terms).  Returns ``(terms, shapes)``."""
-    out, osh = [], []
-    for (kind, var, scale), shp in zip(terms, shapes):
-        for i, (k2, v2, s2) in enumerate(out):
-            if k2 == kind and _same_param(scale, s2) and _same_param(shp, osh[i]):
-                out[i] = (k2, v2 + var, s2)
+def _merge(rows):
+    """Add up the variances of rows with the same primitive, the same length scale and the same shape parameter (``p + p``
+    has the kernel ``4 k``, not four terms; the fused kernels take at most 8 distinct terms)."""
+    out = []
+    for kind, var, scale, shp in rows:
+        for i, (k2, v2, s2, a2) in enumerate(out):
+            if k2 == kind and _same_param(scale, s2) and _same_param(shp, a2):
+                out[i] = (k2, v2 + var, s2, a2)
                 break
         else:
-            out.append((kind, var, scale))
-            osh.append(shp)
-    return out, osh
-
-
-def _merge_terms(terms):
-    """``_merge`` for terms without shape parameters."""
-    terms = list(terms)
-    return _merge(terms, [None] * len(terms))[0]
+            out.append((kind, var, scale, shp))
+    return out
 
 
 def _scale_stamp(t):
@@ -690,29 +679,9 @@ class Sum(Kernel):
     def num_outputs(self, x):
         return self.a.num_outputs(x)
 
-    def terms(self):
-        ta, tb = self.a.terms(), self.b.terms()
-        if ta is None or tb is None:
-            return None
-        return _merge(ta + tb, self.a.shapes() + self.b.shapes())[0]
-
-    def tensor_terms(self):
-        ta, tb = self.a.tensor_terms(), self.b.tensor_terms()
-        if ta is None or tb is None:
-            return None
-        return _merge(ta + tb, self.a.tensor_shapes() + self.b.tensor_shapes())[0]
-
-    def shapes(self):
-        ta, tb = self.a.terms(), self.b.terms()
-        if ta is None or tb is None:
-            return None
-        return _merge(ta + tb, self.a.shapes() + self.b.shapes())[1]
-
-    def tensor_shapes(self):
-        ta, tb = self.a.tensor_terms(), self.b.tensor_terms()
-        if ta is None or tb is None:
-            return None
-        return _merge(ta + tb, self.a.tensor_shapes() + self.b.tensor_shapes())[1]
+    def _table(self, conv):
+        ra, rb = self.a._table(conv), self.b._table(conv)
+        return None if ra is None or rb is None else _merge(ra + rb)
 
     def input_scaled_view(self):
         # asked several times per FDD / log-density: the comparison of the two length-scale vectors (a device-to-host
@@ -779,17 +748,8 @@ class Reversed(Kernel):
     def num_outputs(self, x):
         return self.k.num_outputs(x)
 
-    def terms(self):
-        return self.k.terms()   # sums of primitives are symmetric
-
-    def tensor_terms(self):
-        return self.k.tensor_terms()
-
-    def shapes(self):
-        return self.k.shapes()
-
-    def tensor_shapes(self):
-        return self.k.tensor_shapes()
+    def _table(self, conv):
+        return self.k._table(conv)   # sums of primitives are symmetric
 
     def pairwise(self, x, y=None, **kw):
         if self.terms() is not None or y is None:
@@ -873,7 +833,7 @@ class DiffKernel(Kernel):
         self.stationary = k.stationary
 
     def _parts(self, x):
-        """``(terms, shapes, imap, fa, fb)``: the term table behind the map and the chain-rule factors of the two slots."""
+        """``(kern, imap, fa, fb)``: the sum of primitives behind the map and the chain-rule factors of the two slots."""
         kern, imap = self.k.input_scaled_view()
         fa = fb = 1.0
         if imap is not None:
@@ -883,7 +843,7 @@ class DiffKernel(Kernel):
                     raise ValueError(f"dimension {dim} outside the kernel's {scales.numel()} length scales")
             fa = 1.0 if self.dim_x is None else 1.0 / float(scales[self.dim_x])
             fb = 1.0 if self.dim_y is None else 1.0 / float(scales[self.dim_y])
-        return kern.terms(), kern.shapes(), imap, fa, fb
+        return kern, imap, fa, fb
 
     def _check_dims(self, x):
         d = x.shape[-1]
@@ -898,12 +858,10 @@ class DiffKernel(Kernel):
         if isinstance(x, MultiInput) or isinstance(y, MultiInput):
             raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
         self._check_dims(x)
-        terms, shapes, imap, fa, fb = self._parts(x)
-        if fa * fb != 1.0:
-            terms = [(kind, var * (fa * fb), scale) for kind, var, scale in terms]
+        kern, imap, fa, fb = self._parts(x)
         xm = x.detach() if imap is None else imap.values(x)
         ym = None if sym else (y.detach() if imap is None else imap.values(y))
-        be, kt = ops.get_backend(), ops.KTerms(terms, shapes)
+        be, kt = ops.get_backend(), kern._kterms(fa * fb)
         if sym and self.dim_x == self.dim_y:       # symmetric: lower-triangle-only and the diagonal additions in the same pass
             return be.kmat_diff(kt, xm, None, self.dim_x, self.dim_y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out,
                                 accumulate=accumulate)
@@ -919,7 +877,8 @@ class DiffKernel(Kernel):
         if isinstance(x, MultiInput):
             raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
         self._check_dims(x)
-        terms, _, imap, fa, fb = self._parts(x)
+        kern, imap, fa, fb = self._parts(x)
+        terms = kern.terms()
         shape = tuple(x.shape[:-1]) + (1,)
         if self.dim_x is not None and self.dim_y is not None:
             if self.dim_x != self.dim_y:
@@ -1497,9 +1456,8 @@ def _learnable_marginals(pm, pk, x, cache):
         return None
     mapped = [(kern, z if imap is None else imap(z), x if imap is None else imap(x)) for kern, imap in groups]
     for _, zin, xin in mapped:
-        if (zin.requires_grad or xin.requires_grad) and xin.shape[-1] > 8:       # (behind a periodic map: twice the input dimension)
-            raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
-                                      "are implemented for at most 8 input dimensions")
+        if zin.requires_grad or xin.requires_grad:
+            _ag.check_input_dims(xin)
     xd = x.detach()                  # (the plain path sees values only: the rows path stays open, one whitening serves mean and variance)
     own_cross = src.own_cross
 

@@ -228,7 +228,7 @@ class AbstractPseudoObservations(AbstractObservations):
         if view is None or isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
             return autograd.kernel_requires_grad(k) or self.y.requires_grad
         kern, imap = view
-        return (autograd.elbo_needs_grad(kern.tensor_terms(), noise_x.diag(), z, self.y - measure.means[p_x](x), x, kern.tensor_shapes())
+        return (autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, self.y - measure.means[p_x](x))
                 or (imap is not None and imap.requires_grad))
 
     def _differentiable(self, measure):
@@ -245,9 +245,8 @@ class AbstractPseudoObservations(AbstractObservations):
         if view is None:
             return None
         kern, imap = view                         # k(a, b) = kern(imap(a), imap(b))
-        tt = kern.tensor_terms()
         y_bar = self.y - measure.means[p_x](x)
-        if not (autograd.elbo_needs_grad(tt, noise_x.diag(), z, y_bar, x, kern.tensor_shapes()) or (imap is not None and imap.requires_grad)):
+        if not (autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, y_bar) or (imap is not None and imap.requires_grad)):
             return None
         if not (measure.kernels[p_x] is k and measure.kernels[p_z, p_x] is k and isinstance(noise_z, Zero)
                 and x.dim() == 2 and z.dim() == 2):
@@ -257,9 +256,8 @@ class AbstractPseudoObservations(AbstractObservations):
             )
         if imap is not None:                      # torch differentiates the map (d/d scales or period, d/dx, d/dz)
             x, z = imap(x), imap(z)
-        if x.requires_grad and x.shape[-1] > 8:
-            raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) are "
-                                      "implemented for at most 8 input dimensions")
+        if x.requires_grad:
+            autograd.check_input_dims(x)
         return autograd.sparse_elbo(kern, x, z, noise_x.diag(), y_bar, self.method)
 
     def mu(self, measure):

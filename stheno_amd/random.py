@@ -269,9 +269,8 @@ class Normal(RandomVector):
                 mapped = [(kern, var.x if imap is None else imap(var.x)) for kern, imap in groups]
                 if _ag.groups_need_grad(mapped, noise_vec, r, noise_mat):
                     for _, xin in mapped:
-                        if xin.requires_grad and torch.is_grad_enabled() and xin.shape[-1] > 8:
-                            raise NotImplementedError("gradients with respect to the inputs (or per-dimension length scales) "
-                                                      "are implemented for at most 8 input dimensions")
+                        if xin.requires_grad:
+                            _ag.check_input_dims(xin)
                     lp = _ag.gp_logpdf(mapped, noise_vec, r, noise_mat)
                     if r.dim() == 3:
                         return lp, True

@@ -65,9 +65,9 @@ def test_bad_and_learnable_epsilon_are_refused():
     # the autograd packing refuses one that got past the constructor
     e = torch.tensor(1e-6, dtype=torch.float64, requires_grad=True)
     with pytest.raises(ValueError, match="not learnable"):
-        autograd._pack([("delta", 1.0, 1.0)], [e])
+        autograd._pack([("delta", 1.0, 1.0, e)])
     a = torch.tensor(0.5, dtype=torch.float64, requires_grad=True)
-    assert len(autograd._pack([("rq", 1.0, 1.0)], [a])[1]) == 3
+    assert len(autograd._pack([("rq", 1.0, 1.0, a)])[1]) == 3
 
 
 def test_kterms_validate_epsilon():
