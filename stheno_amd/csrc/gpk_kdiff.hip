@@ -7,14 +7,14 @@
 // Replaces: mlkernels `DerivativeKernel` (autodiff of `pairwise`) behind `GP.diff` -- stheno/model/measure.py:343-360: the
 // covariance blocks of a process with its derivative and of two derivatives.  Formulas in include/gpk.h (gpk_kmat_diff).
 //
-// Same memory profile as gpk_kmat.hip -- N x M values written once, HBM-write-bound -- and the same two launch shapes, laid out the
-// same way: a 32 x (64*VEC) tile per workgroup pass, X rows in LDS read as wave-uniform broadcasts, squared distances from direct
-// differences; the row-band walk (d <= 8: Y tiles staged through LDS, 8 KiB contiguous per row and workgroup, non-temporal stores)
-// and the chunked one-tile kernel (d > 8).  On top of r^2 an element keeps the differences in the selected dimensions,
+// Same memory profile as gpk_kmat.hip -- N x M values written once, HBM-write-bound -- and the same two launch shapes on the same
+// launch geometry (gpk_kmat_plan.hpp) and tile helpers (gpk_kmat_tile.hpp): the row-band walk (d <= 8: Y tiles staged through LDS,
+// 8 KiB contiguous per row and workgroup, non-temporal stores) and the chunked one-tile kernel (d > 8); X rows in LDS, squared
+// distances from direct differences.  On top of r^2 an element keeps the differences in the selected dimensions,
 // x[a] - y[a] and x[b] - y[b] (for Linear terms: y[a] or x[b] themselves).  One term-table program; the mode and "some term has a
 // shape parameter" are template parameters (the one-sided modes never evaluate kappa'', tables without RQ never the logarithm).
 #include "gpk_common.hpp"
-#include "gpk_kmat_math.hpp"
+#include "gpk_kmat_tile.hpp"
 
 GPK_KNOB(int, g_kdiff_band, 1);      // tuning knob (gpk_tune(12, v), shared with gpk_kmat): 1 = row-band kernel, 0 = the one-tile-per-workgroup kernel
 GPK_KNOB(int, g_kdiff_compact, 1);   // tuning knob (gpk_tune(34, v), shared with gpk_kmat): 1-D compact grid for the lower triangle of a square matrix
@@ -24,10 +24,6 @@ void gpk_tune_kdiff(int key, int64_t value) {
 }
 
 namespace {
-
-constexpr int TM = 32;   // tile rows
-constexpr int RW = 8;    // rows per wave
-constexpr int CT_MAX = 8;    // row-band kernel: column tiles per workgroup
 
 enum { MODE_DX = 0, MODE_DY = 1, MODE_DXY = 2 };
 
@@ -96,7 +92,7 @@ __device__ __forceinline__ T diff_terms(const KdiffArgs<T>& p, T r2, T da, T db,
     return same ? val + (lin - T(2) * s1) : val;
 }
 
-// One tile per workgroup, the input dimensions in chunks of DC (any d): kmat_kernel of gpk_kmat.hip with the selected coordinates beside it.
+// One tile per workgroup, the input dimensions in chunks of DC (any d); the selected coordinates are fetched beside the chunks.
 template <typename T, int MODE, bool SH, int DC>
 __global__ __launch_bounds__(256) void kdiff_kernel(KdiffArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
@@ -180,10 +176,7 @@ __global__ __launch_bounds__(256) void kdiff_kernel(KdiffArgs<T> p) {
         for (int v = 0; v < VEC; ++v) {
             const int col = colb + v;
             T val = diff_terms<T, MODE, SH>(p, r2[r][v], xa - ya[v], xb - yb[v], MODE == MODE_DX ? ya[v] : xb, same);
-            if (p.symmetric && col == row) {
-                val += p.diag_add;
-                if (p.diag_vec != nullptr) val += p.diag_vec[b * p.sDiag + row];
-            }
+            if (p.symmetric && col == row) kmat_add_diag(p, b, row, val);
             vals[v] = val;
         }
         T* o = out + (int64_t)row * p.ld + colb;
@@ -206,7 +199,7 @@ __global__ __launch_bounds__(256) void kdiff_kernel(KdiffArgs<T> p) {
     }
 }
 
-// Row-band kernel (d <= DC <= 8): kmat_band_kernel of gpk_kmat.hip -- the band's X rows staged once, Y tiles double-buffered through
+// Row-band kernel (d <= DC <= 8), the walk of kmat_band_kernel: the band's X rows staged once, Y tiles double-buffered through
 // LDS (dimension-major), the next tile's Y in flight under this tile's arithmetic, CT back-to-back wave-stores per row.  The selected
 // coordinates are already there: x[a], x[b] in the staged rows, y[a], y[b] as two more vector reads of the staged Y tile.
 template <typename T, int MODE, bool SH, int DC>
@@ -223,18 +216,7 @@ __global__ __launch_bounds__(256) void kdiff_band_kernel(KdiffArgs<T> p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int by = blockIdx.y, bx = blockIdx.x;
     if (p.compact) {
-        // 1-D grid over the (row band, column chunk) pairs on or below the diagonal: the bands of chunk-group g (G = p.compact
-        // consecutive row bands) have g + 1 chunks each.  Groups are laid out from the bottom of the matrix up (full chunks first).
-        const int G = p.compact;
-        int bid = (int)blockIdx.x;
-        int g = (p.nbands + G - 1) / G - 1;
-        for (; g > 0; --g) {
-            const int cnt = min(G, p.nbands - g * G) * (g + 1);
-            if (bid < cnt) break;
-            bid -= cnt;
-        }
-        by = g * G + bid / (g + 1);
-        bx = bid % (g + 1);
+        gpk_kmat_compact_decode((int)blockIdx.x, p.nbands, p.compact, by, bx);
         if (by >= p.nbands) return;
     }
     const int row0 = by * TM;
@@ -247,11 +229,7 @@ __global__ __launch_bounds__(256) void kdiff_band_kernel(KdiffArgs<T> p) {
     const T* __restrict__ Y = p.Y + b * p.sY;
     T* __restrict__ out = p.out + b * p.sO;
 
-    if (tid < TM * DC) {      // the band's X rows: TM * DC <= 256 elements, one per thread; d <= DC (launcher)
-        const int r = tid / DC, j = tid % DC;
-        const int row = row0 + r;
-        xs[tid] = (row < p.n && j < p.d) ? X[(int64_t)row * p.ldx + j] : T(0);
-    }
+    kmat_stage_band_x<T, DC>(p, X, tid, row0, xs);
     T stage[YL];
     auto fetch_y = [&](int col0) {      // consecutive lanes fetch consecutive elements of the (contiguous) Y tile
 #pragma unroll
@@ -320,10 +298,7 @@ __global__ __launch_bounds__(256) void kdiff_band_kernel(KdiffArgs<T> p) {
                     r2 += df * df;
                 }
                 T val = diff_terms<T, MODE, SH>(p, r2, xa - ya[v], xb - yb[v], MODE == MODE_DX ? ya[v] : xb, same);
-                if (has_diag && colb + v == row) {
-                    val += p.diag_add;
-                    if (p.diag_vec != nullptr) val += p.diag_vec[b * p.sDiag + row];
-                }
+                if (has_diag && colb + v == row) kmat_add_diag(p, b, row, val);
                 vals[v] = val;
             }
             T* o = out + (int64_t)row * p.ld + colb;
@@ -353,17 +328,8 @@ __global__ __launch_bounds__(256) void kdiff_band_kernel(KdiffArgs<T> p) {
 template <typename T, int MODE, bool SH>
 void launch_mode(const KdiffArgs<T>& a, bool band, dim3 grid, hipStream_t stream) {
 #define GPK_KDIFF(KERNEL, DCV) hipLaunchKernelGGL((KERNEL<T, MODE, SH, DCV>), grid, dim3(256), 0, stream, a)
-    if (band) {
-        if (a.d <= 1) GPK_KDIFF(kdiff_band_kernel, 1);
-        else if (a.d <= 2) GPK_KDIFF(kdiff_band_kernel, 2);
-        else if (a.d <= 4) GPK_KDIFF(kdiff_band_kernel, 4);
-        else GPK_KDIFF(kdiff_band_kernel, 8);
-    } else {
-        if (a.d <= 1) GPK_KDIFF(kdiff_kernel, 1);
-        else if (a.d <= 2) GPK_KDIFF(kdiff_kernel, 2);
-        else if (a.d <= 4) GPK_KDIFF(kdiff_kernel, 4);
-        else GPK_KDIFF(kdiff_kernel, 8);
-    }
+    if (band) GPK_KMAT_DC(a.d, GPK_KDIFF, kdiff_band_kernel);
+    else GPK_KMAT_DC(a.d, GPK_KDIFF, kdiff_kernel);
 #undef GPK_KDIFF
 }
 
@@ -406,11 +372,9 @@ int gpk_kmat_diff_launch(const int* kinds, const double* variances, const double
     a.n = (int)n; a.m = (int)m; a.d = d;
     a.dim_x = dim_x; a.dim_y = dim_y;
     a.nterms = nterms;
+    gpk_pack_terms(a.terms, kinds, variances, inv_ls, nterms, true);
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        const bool on = t < nterms, rq = on && kinds[t] == GPK_K_RQ;
-        a.terms[t].kind = on ? kinds[t] : GPK_K_CONST;
-        a.terms[t].variance = on ? (T)variances[t] : T(0);
-        a.terms[t].ils2 = on ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
+        const bool rq = t < nterms && kinds[t] == GPK_K_RQ;
         a.hshape[t] = rq ? (T)(0.5 / shapes[t]) : T(0);
         a.shape1[t] = rq ? (T)(shapes[t] + 1.0) : T(0);
         a.shape2[t] = rq ? (T)(shapes[t] + 2.0) : T(0);
@@ -419,25 +383,10 @@ int gpk_kmat_diff_launch(const int* kinds, const double* variances, const double
     a.diag_add = (T)diag_add;
     a.symmetric = symmetric; a.lower_only = lower_only; a.accumulate = accumulate;
     a.vec_ok = ((uintptr_t)out % 16 == 0) && (ld % VEC == 0) && (sO % VEC == 0);
-    a.ct = 1; a.nbands = (int)gy; a.compact = 0;
     const bool band = d <= 8 && g_kdiff_band;
-    dim3 grid((unsigned)gpk_cdiv(m, 64 * VEC), (unsigned)gy, (unsigned)batch);
-    if (band) {
-        const int64_t tiles_x = gpk_cdiv(m, 64 * VEC);
-        int ct = CT_MAX;
-        while (ct > 1 && gpk_cdiv(tiles_x, ct) * gy * batch / (lower_only ? 2 : 1) < 6144) ct >>= 1;
-        a.ct = ct;
-        grid = dim3((unsigned)gpk_cdiv(tiles_x, ct), (unsigned)gy, (unsigned)batch);
-        // lower triangle of a square matrix with several column chunks per row band: a 1-D grid of exactly the pairs needed (gpk_kmat.hip)
-        const int64_t chunk_cols = (int64_t)ct * 64 * VEC;
-        if (g_kdiff_compact && lower_only && symmetric && n == m && grid.x > 1 && chunk_cols % TM == 0) {
-            const int64_t G = chunk_cols / TM;
-            int64_t total = 0;
-            for (int64_t g = 0; g * G < gy; ++g) total += ((gy - g * G < G) ? gy - g * G : G) * (g + 1);
-            a.compact = (int)G;
-            grid = dim3((unsigned)total, 1u, (unsigned)batch);
-        }
-    }
+    const KmatPlan plan = gpk_kmat_plan(n, m, batch, VEC, lower_only, symmetric, band, g_kdiff_compact);
+    a.ct = plan.ct; a.nbands = plan.nbands; a.compact = plan.compact;
+    const dim3 grid(plan.gx, plan.gy, plan.gz);
     const int mode = dim_y < 0 ? MODE_DX : dim_x < 0 ? MODE_DY : MODE_DXY;
     if (shaped) {
         if (mode == MODE_DX) launch_mode<T, MODE_DX, true>(a, band, grid, stream);

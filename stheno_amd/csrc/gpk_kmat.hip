@@ -15,7 +15,7 @@
 // Y rows of a lane live in registers.  Squared distances are accumulated as
 // direct differences (no |a|^2 + |b|^2 - 2ab cancellation).
 #include "gpk_common.hpp"
-#include "gpk_kmat_math.hpp"   // KTermT, gpk_exp, gpk_sqrtk, gpk_log1p (shared with gpk_kdiff.hip)
+#include "gpk_kmat_tile.hpp"   // shared with gpk_kdiff.hip: tile helpers; brings gpk_kmat_plan.hpp (launch geometry) and gpk_kmat_math.hpp
 
 GPK_KNOB(int, g_kmat_compact, 1);   // tuning knob (gpk_tune(34, v)): 1-D compact grid for the lower triangle of a square matrix
 GPK_KNOB(int, g_kmat_band, 1);      // tuning knob (gpk_tune(12, v)): 1 = row-band kernel, 0 = the one-tile-per-workgroup kernel
@@ -28,8 +28,6 @@ void gpk_tune_kmat(int key, int64_t value) {
 
 namespace {
 
-constexpr int TM = 32;   // tile rows
-constexpr int RW = 8;    // rows per wave
 // input dimensions per staged chunk: template parameter DC in {1, 2, 4, 8} -- the smallest that holds d
 // (the distance loop runs over the whole chunk; with D = 1 or 3 a fixed chunk of 8 is mostly zero padding)
 
@@ -45,10 +43,7 @@ struct KmatArgs {
     KTermT<T> terms[GPK_MAX_TERMS];
     T diag_add;
     int symmetric, lower_only, accumulate, need_dot, vec_ok;
-    int ct;           // row-band kernel: column tiles per workgroup
-    int nbands;       // row-band kernel: number of row bands (TM rows each)
-    int compact;      // row-band kernel, lower triangle of one square matrix: a 1-D grid of exactly the (row band, column chunk) pairs on or
-                      // below the diagonal -- `compact` = row bands per column chunk; 0 = the plain 2-D grid
+    int ct, nbands, compact;      // row-band kernel: the launch plan (KmatPlan in gpk_kmat_plan.hpp)
     // shape parameters (GPK_K_RQ: alpha, and 1 / (2 alpha); GPK_K_DELTA: epsilon in `shape`).  Behind everything else: the programs that have none read the same
     // argument offsets as before and compile to the code they compiled to without these two arrays.
     T shape[GPK_MAX_TERMS];
@@ -163,10 +158,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
         for (int v = 0; v < VEC; ++v) {
             const int col = colb + v;
             T val = eval_terms<T, SH>(p, r2[r][v], dt[r][v]);
-            if (p.symmetric && col == row) {
-                val += p.diag_add;
-                if (p.diag_vec != nullptr) val += p.diag_vec[b * p.sDiag + row];
-            }
+            if (p.symmetric && col == row) kmat_add_diag(p, b, row, val);
             vals[v] = val;
         }
         T* o = out + (int64_t)row * p.ld + colb;
@@ -306,8 +298,6 @@ __device__ __forceinline__ T eval_prog(const KmatArgs<T>& p, T r2, T dot, const 
     return fma(fma(v0 * T(1.0 / 3.0), sd, v0), sd, v0) * gpk_exp_neg_t(-sd, etab);
 }
 
-constexpr int CT_MAX = 8;    // column tiles per workgroup (fewer when the grid would not fill the chip a few times over)
-
 template <typename T, int PROG, bool DOT, int DC>
 __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
@@ -326,18 +316,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int by = blockIdx.y, bx = blockIdx.x;
     if (p.compact) {
-        // 1-D grid over the (row band, column chunk) pairs on or below the diagonal: the bands of chunk-group g (G = p.compact
-        // consecutive row bands) have g + 1 chunks each.  Groups are laid out from the bottom of the matrix up (full chunks first).
-        const int G = p.compact;
-        int bid = (int)blockIdx.x;
-        int g = (p.nbands + G - 1) / G - 1;
-        for (; g > 0; --g) {
-            const int cnt = min(G, p.nbands - g * G) * (g + 1);
-            if (bid < cnt) break;
-            bid -= cnt;
-        }
-        by = g * G + bid / (g + 1);
-        bx = bid % (g + 1);
+        gpk_kmat_compact_decode((int)blockIdx.x, p.nbands, p.compact, by, bx);
         if (by >= p.nbands) return;
     }
     const int row0 = by * TM;
@@ -350,11 +329,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     const T* __restrict__ Y = p.Y + b * p.sY;
     T* __restrict__ out = p.out + b * p.sO;
 
-    if (tid < TM * DC) {      // the band's X rows: TM * DC <= 256 elements, one per thread; d <= DC (launcher)
-        const int r = tid / DC, j = tid % DC;
-        const int row = row0 + r;
-        xs[tid] = (row < p.n && j < p.d) ? X[(int64_t)row * p.ldx + j] : T(0);
-    }
+    kmat_stage_band_x<T, DC>(p, X, tid, row0, xs);
     // A column tile of Y is TN points x d values, contiguous in memory when ldy == d: consecutive lanes fetch
     // consecutive elements (two cache lines per wave-load); a lane fetching "its own" columns straight from global
     // memory touches 64 different lines per load instruction, and the L1 then sets the pace of the whole kernel
@@ -449,10 +424,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                 if (has_diag) {
 #pragma unroll
                     for (int v = 0; v < VEC; ++v)
-                        if (colb + v == row) {
-                            vals[v] += p.diag_add;
-                            if (p.diag_vec != nullptr) vals[v] += p.diag_vec[b * p.sDiag + row];
-                        }
+                        if (colb + v == row) kmat_add_diag(p, b, row, vals[v]);
                 }
             } else {
 #pragma unroll
@@ -465,10 +437,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         if (DOT) dt += xr[j] * ya[j][v];
                     }
                     T val = eval_prog<T, PROG>(p, r2, dt, etab);
-                    if (has_diag && colb + v == row) {
-                        val += p.diag_add;
-                        if (p.diag_vec != nullptr) val += p.diag_vec[b * p.sDiag + row];
-                    }
+                    if (has_diag && colb + v == row) kmat_add_diag(p, b, row, val);
                     vals[v] = val;
                 }
             }
@@ -541,13 +510,7 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     a.ldx = ldx; a.ldy = ldy; a.sX = sX; a.sY = sY; a.ld = ld; a.sO = sO; a.sDiag = sDiag;
     a.n = (int)n; a.m = (int)m; a.d = d;
     a.nterms = nterms;
-    a.need_dot = 0;
-    for (int t = 0; t < nterms; ++t) {
-        a.terms[t].kind = kinds[t];
-        a.terms[t].variance = (T)variances[t];
-        a.terms[t].ils2 = (T)(inv_ls[t] * inv_ls[t]);
-        if (kinds[t] == GPK_K_LINEAR) a.need_dot = 1;
-    }
+    a.need_dot = gpk_pack_terms(a.terms, kinds, variances, inv_ls, nterms, false);
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
         const bool rq = t < nterms && kinds[t] == GPK_K_RQ, delta = t < nterms && kinds[t] == GPK_K_DELTA;
         a.shape[t] = (rq || delta) ? (T)shapes[t] : T(0);
@@ -566,73 +529,36 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     // (round 2, with the library sqrt + exp: the one-tile kernel was 15 % faster for fp64 kernels with a square root -- 0.53 vs 0.62 ms at
     // N = 16384 -- and kept them; round 5: with the branch-free exp of round 3 and the rsq-based sqrt above, knob 51 decides)
     const bool band_ok = sizeof(T) == 4 || prog == PROG_EQ || prog == PROG_EQ_LINEAR || prog == PROG_RQ || g_kmat_band_f64_sqrt;
-    if (d <= 8 && g_kmat_band && band_ok) {
-        const int64_t tiles_x = gpk_cdiv(m, 64 * VEC);
-        int ct = CT_MAX;
-        while (ct > 1 && gpk_cdiv(tiles_x, ct) * gy * batch / (lower_only ? 2 : 1) < 6144) ct >>= 1;
-        a.ct = ct;
-        a.nbands = (int)gy;
-        a.compact = 0;
-        dim3 bgrid((unsigned)gpk_cdiv(tiles_x, ct), (unsigned)gy, (unsigned)batch);
-        // Lower triangle of a square matrix with several column chunks per row band: half of the 2-D grid would be workgroups
-        // that exit at once, and the dispatcher works through them in index order in front of the real ones (measured at
-        // N = 16384: the lower triangle took 0.46 ms against 0.52 ms for the FULL matrix).  A 1-D grid of exactly the pairs needed.
-        const int64_t chunk_cols = (int64_t)ct * 64 * VEC;
-        if (g_kmat_compact && lower_only && symmetric && n == m && bgrid.x > 1 && chunk_cols % TM == 0) {
-            const int64_t G = chunk_cols / TM;
-            int64_t total = 0;
-            for (int64_t g = 0; g * G < gy; ++g) total += ((gy - g * G < G) ? gy - g * G : G) * (g + 1);
-            a.compact = (int)G;
-            bgrid = dim3((unsigned)total, 1u, (unsigned)batch);
-        }
-#define GPK_BAND(PROGV, DOTV, DCV) hipLaunchKernelGGL((kmat_band_kernel<T, PROGV, DOTV, DCV>), bgrid, dim3(256), 0, stream, a)
-#define GPK_BAND_DC(PROGV, DOTV)                      \
-    do {                                              \
-        if (d <= 1) GPK_BAND(PROGV, DOTV, 1);         \
-        else if (d <= 2) GPK_BAND(PROGV, DOTV, 2);    \
-        else if (d <= 4) GPK_BAND(PROGV, DOTV, 4);    \
-        else GPK_BAND(PROGV, DOTV, 8);                \
-    } while (0)
+    const bool band = d <= 8 && g_kmat_band && band_ok;
+    const KmatPlan plan = gpk_kmat_plan(n, m, batch, VEC, lower_only, symmetric, band, g_kmat_compact);
+    a.ct = plan.ct; a.nbands = plan.nbands; a.compact = plan.compact;
+    const dim3 grid(plan.gx, plan.gy, plan.gz);
+    if (band) {
+#define GPK_BAND(PROGV, DOTV, DCV) hipLaunchKernelGGL((kmat_band_kernel<T, PROGV, DOTV, DCV>), grid, dim3(256), 0, stream, a)
         switch (prog) {
-            case PROG_EQ: GPK_BAND_DC(PROG_EQ, false); break;
-            case PROG_M12: GPK_BAND_DC(PROG_M12, false); break;
-            case PROG_M32: GPK_BAND_DC(PROG_M32, false); break;
-            case PROG_M52: GPK_BAND_DC(PROG_M52, false); break;
-            case PROG_EQ_LINEAR: GPK_BAND_DC(PROG_EQ_LINEAR, true); break;
-            case PROG_RQ: GPK_BAND_DC(PROG_RQ, false); break;
+            case PROG_EQ: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ, false); break;
+            case PROG_M12: GPK_KMAT_DC(d, GPK_BAND, PROG_M12, false); break;
+            case PROG_M32: GPK_KMAT_DC(d, GPK_BAND, PROG_M32, false); break;
+            case PROG_M52: GPK_KMAT_DC(d, GPK_BAND, PROG_M52, false); break;
+            case PROG_EQ_LINEAR: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ_LINEAR, true); break;
+            case PROG_RQ: GPK_KMAT_DC(d, GPK_BAND, PROG_RQ, false); break;
             default:
                 if (shaped) {
-                    if (a.need_dot) GPK_BAND_DC(PROG_GENERIC_RQ, true);
-                    else GPK_BAND_DC(PROG_GENERIC_RQ, false);
-                } else if (a.need_dot) GPK_BAND_DC(PROG_GENERIC, true);
-                else GPK_BAND_DC(PROG_GENERIC, false);
+                    if (a.need_dot) GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC_RQ, true);
+                    else GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC_RQ, false);
+                } else if (a.need_dot) GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC, true);
+                else GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC, false);
         }
-#undef GPK_BAND_DC
 #undef GPK_BAND
         GPK_CHECK_LAUNCH();
         return GPK_OK;
     }
-    dim3 grid((unsigned)gpk_cdiv(m, 64 * VEC), (unsigned)gy, (unsigned)batch);
-#define GPK_KMAT_LAUNCH(DCV)                                                                            \
-    do {                                                                                                \
-        if (shaped && a.need_dot)                                                                       \
-            hipLaunchKernelGGL((kmat_kernel<T, true, DCV, true>), grid, dim3(256), 0, stream, a);       \
-        else if (shaped)                                                                                \
-            hipLaunchKernelGGL((kmat_kernel<T, false, DCV, true>), grid, dim3(256), 0, stream, a);      \
-        else if (a.need_dot)                                                                            \
-            hipLaunchKernelGGL((kmat_kernel<T, true, DCV, false>), grid, dim3(256), 0, stream, a);      \
-        else                                                                                            \
-            hipLaunchKernelGGL((kmat_kernel<T, false, DCV, false>), grid, dim3(256), 0, stream, a);     \
-    } while (0)
-    if (d <= 1)
-        GPK_KMAT_LAUNCH(1);
-    else if (d <= 2)
-        GPK_KMAT_LAUNCH(2);
-    else if (d <= 4)
-        GPK_KMAT_LAUNCH(4);
-    else
-        GPK_KMAT_LAUNCH(8);
-#undef GPK_KMAT_LAUNCH
+#define GPK_ONE_TILE(DOTV, SHV, DCV) hipLaunchKernelGGL((kmat_kernel<T, DOTV, DCV, SHV>), grid, dim3(256), 0, stream, a)
+    if (shaped && a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, true);
+    else if (shaped) GPK_KMAT_DC(d, GPK_ONE_TILE, false, true);
+    else if (a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, false);
+    else GPK_KMAT_DC(d, GPK_ONE_TILE, false, false);
+#undef GPK_ONE_TILE
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
@@ -648,11 +574,7 @@ int gpk_kdiag_launch(const int* kinds, const double* variances, const double* in
     KdiagArgs<T> a;
     a.X = X; a.out = out; a.ldx = ldx; a.sX = sX; a.sO = sO;
     a.n = (int)n; a.d = d; a.nterms = nterms;
-    for (int t = 0; t < nterms; ++t) {
-        a.terms[t].kind = kinds[t];
-        a.terms[t].variance = (T)variances[t];
-        a.terms[t].ils2 = (T)(inv_ls[t] * inv_ls[t]);
-    }
+    gpk_pack_terms(a.terms, kinds, variances, inv_ls, nterms, false);
     dim3 grid((unsigned)gpk_cdiv(n, 256), (unsigned)batch);
     hipLaunchKernelGGL((kdiag_kernel<T>), grid, dim3(256), 0, stream, a);
     GPK_CHECK_LAUNCH();

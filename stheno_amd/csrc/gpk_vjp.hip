@@ -488,6 +488,17 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
     }
 }
 
+// The term table of either launch from the host arrays of the entry points, padded to GPK_MAX_TERMS with constant terms (`var`: dense variant only)
+template <typename T>
+void vjp_pack_terms(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int* kind, T* ils2, T* var, T* shape) {
+    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+        kind[t] = t < nterms ? kinds[t] : GPK_K_CONST;
+        ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
+        if (var != nullptr) var[t] = t < nterms ? (T)variances[t] : T(0);
+        shape[t] = (t < nterms && (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA)) ? (T)shapes[t] : T(1);
+    }
+}
+
 }  // namespace
 
 void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk) {
@@ -522,12 +533,7 @@ int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const d
     int64_t rt, nc, tpc;
     gpk_kmat_vjp_dense_grid_impl(n, m, &rt, &nc, &tpc);
     a.tiles_per_chunk = (int)tpc; a.nchunks = (int)nc; a.ctiles = (int)gpk_cdiv(m, DT);
-    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        a.kind[t] = t < nterms ? kinds[t] : GPK_K_CONST;
-        a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
-        a.var[t] = t < nterms ? (T)variances[t] : T(0);
-        a.shape[t] = (t < nterms && (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA)) ? (T)shapes[t] : T(1);
-    }
+    vjp_pack_terms<T>(kinds, variances, inv_ls, shapes, nterms, a.kind, a.ils2, a.var, a.shape);
     if (nc > 65535) return GPK_ERR_ARG(9);
     if (shaped)
         hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, true>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
@@ -572,11 +578,7 @@ int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, const double* sh
         if (c < C) s += g[c];
     }
     a.s = (T)s;
-    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        a.kind[t] = t < nterms ? kinds[t] : GPK_K_CONST;
-        a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
-        a.shape[t] = (t < nterms && (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA)) ? (T)shapes[t] : T(1);
-    }
+    vjp_pack_terms<T>(kinds, nullptr, inv_ls, shapes, nterms, a.kind, a.ils2, nullptr, a.shape);
     const int64_t nb = gpk_kmat_vjp_blocks_impl(n);
     if (shaped)
         hipLaunchKernelGGL((kmat_vjp_kernel<T, true>), dim3((unsigned)nb), dim3(256), 0, stream, a);

@@ -202,10 +202,9 @@ class HipBackend:
             raise RuntimeError(f"libgpk {what} failed with status {code}")
 
     # -- kernel matrices -----------------------------------------------------
-    @_on_operand_device
-    def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
-        """``out[b, i, j] (+)= k(x[b, i], y[b, j])``; ``y is None`` means the symmetric case
-        (then ``diag_add`` / ``diag_vec`` go on the diagonal)."""
+    def _kmat(self, entry, dims, terms, x, y, lower, diag_add, diag_vec, out, accumulate):
+        """One launch of ``gpk_kmat`` or ``gpk_kmat_diff`` (``entry``): the two take the same arguments, apart from ``dims`` -- what
+        ``gpk_kmat_diff`` has between the term table and the tensors."""
         symmetric = y is None
         x3, bshape = _as3(x)
         y3 = x3 if symmetric else _as3(y)[0]
@@ -224,37 +223,23 @@ class HipBackend:
         tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
                 _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
                 self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
-        code = self.lib.gpk_kmat(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, *tail)
-        self._st(code, "gpk_kmat")
+        code = getattr(self.lib, entry)(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, *dims, *tail)
+        self._st(code, entry)
         return out
+
+    @_on_operand_device
+    def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        """``out[b, i, j] (+)= k(x[b, i], y[b, j])``; ``y is None`` means the symmetric case
+        (then ``diag_add`` / ``diag_vec`` go on the diagonal)."""
+        return self._kmat("gpk_kmat", (), terms, x, y, lower, diag_add, diag_vec, out, accumulate)
 
     @_on_operand_device
     def kmat_diff(self, terms, x, y, dim_x, dim_y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
         """Derivative blocks of the kernel matrix (``gpk_kmat_diff``): ``out[b, i, j] (+)=`` the derivative of ``k(x[b, i], y[b, j])`` with
         respect to ``x[b, i, dim_x]`` and / or ``y[b, j, dim_y]`` (``None``: not differentiated in that argument; at least one is given).
         ``y is None``: the symmetric case, which needs ``dim_x == dim_y`` (``lower``, ``diag_add`` / ``diag_vec`` as for :meth:`kmat`)."""
-        symmetric = y is None
-        dx, dy = (-1 if v is None else int(v) for v in (dim_x, dim_y))
-        x3, bshape = _as3(x)
-        y3 = x3 if symmetric else _as3(y)[0]
-        self._check(x3, y3, diag_vec, out)
-        B, n, d = x3.shape
-        m = y3.shape[1]
-        if y3.shape[0] != B or y3.shape[2] != d:
-            raise ValueError("x and y must agree in batch size and input dimension")
-        if out is None:
-            out = _alloc(bshape, n, m, x.dtype, x.device)
-        o3, _ = _as3_out(out)
-        dv = None
-        if diag_vec is not None:
-            dv = diag_vec.reshape(B, n).contiguous()
-        kinds, var, ils, nt = terms.c_arrays()
-        tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
-                _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
-                self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
-        code = self.lib.gpk_kmat_diff(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, dx, dy, *tail)
-        self._st(code, "gpk_kmat_diff")
-        return out
+        dims = tuple(-1 if v is None else int(v) for v in (dim_x, dim_y))
+        return self._kmat("gpk_kmat_diff", dims, terms, x, y, lower, diag_add, diag_vec, out, accumulate)
 
     @_on_operand_device
     def kdiag(self, terms, x):
@@ -382,14 +367,13 @@ class HipBackend:
         self._st(code, "gpk_trtri_merge")
         return dsb
 
-    @_on_operand_device
-    def tri_solve_(self, l, dinv_sb, sb, b):
-        """``L^{-1} b``; ``b`` is (..., n, nrhs) with unit inner stride and is OVERWRITTEN (with the solution for up to 8 columns,
-        with intermediate values otherwise): use the return value."""
+    def _tri_solve(self, name, trsv, trsm, l, dinv_sb, sb, b):
+        """``tri_solve_`` / ``tri_solve_t_`` (``name``) through the library's sweep ``trsv`` for up to 8 columns and its blocked solve
+        ``trsm`` above: the two pairs of entries take the same arguments."""
         l3, _ = _as3(l)
         b3, _ = _as3(b)
         if b3.data_ptr() != b.data_ptr():
-            raise ValueError("tri_solve_ needs a right-hand side with unit inner stride")
+            raise ValueError(f"{name} needs a right-hand side with unit inner stride")
         self._check(l3, b3, dinv_sb)
         B, n, _ = l3.shape
         nrhs = b3.shape[2]
@@ -399,47 +383,31 @@ class HipBackend:
             return b
         if nrhs <= 8:
             tmp = torch.empty((B * sb * nrhs + 16,), dtype=b.dtype, device=b.device)     # (+ GPK_TRSV_CTRL_ELEMS: reserved)
-            code = self.lib.gpk_trsv_lower(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
+            code = getattr(self.lib, trsv)(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
                                            self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(tmp), B, self._stream())
-            self._st(code, "gpk_trsv_lower")
+            self._st(code, trsv)
             return b
         # many right-hand sides: the recursive blocked solve, out of place -- solved blocks go to a second buffer (no copy per
         # block), `b` is used up as workspace; the caller takes the return value (Chol.solve_)
         x = torch.empty(b.shape, dtype=b.dtype, device=b.device)
         x3, _ = _as3(x)
-        code = self.lib.gpk_trsm_lower_to(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
-                                          self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(x3), _ld(x3), _bs(x3), B, self._stream())
-        self._st(code, "gpk_trsm_lower_to")
+        code = getattr(self.lib, trsm)(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
+                                       self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(x3), _ld(x3), _bs(x3), B, self._stream())
+        self._st(code, trsm)
         return x
+
+    @_on_operand_device
+    def tri_solve_(self, l, dinv_sb, sb, b):
+        """``L^{-1} b``; ``b`` is (..., n, nrhs) with unit inner stride and is OVERWRITTEN (with the solution for up to 8 columns,
+        with intermediate values otherwise): use the return value."""
+        return self._tri_solve("tri_solve_", "gpk_trsv_lower", "gpk_trsm_lower_to", l, dinv_sb, sb, b)
 
     @_on_operand_device
     def tri_solve_t_(self, l, dinv_sb, sb, b):
         """``L^{-T} b`` with the TRANSPOSED factor (``gpk_trsv_lower_t`` for up to 8 columns, ``gpk_trsm_lower_t`` above), the mirror of
         :meth:`tri_solve_`: ``b`` (..., n, nrhs), unit inner stride, is OVERWRITTEN (with the solution for up to 8 columns, used up as
         workspace otherwise): use the return value."""
-        l3, _ = _as3(l)
-        b3, _ = _as3(b)
-        if b3.data_ptr() != b.data_ptr():
-            raise ValueError("tri_solve_t_ needs a right-hand side with unit inner stride")
-        self._check(l3, b3, dinv_sb)
-        B, n, _ = l3.shape
-        nrhs = b3.shape[2]
-        if b3.shape[0] != B or b3.shape[1] != n:
-            raise ValueError("right-hand side does not match the factor")
-        if n == 0 or nrhs == 0:
-            return b
-        if nrhs <= 8:
-            tmp = torch.empty((B * sb * nrhs + 16,), dtype=b.dtype, device=b.device)
-            code = self.lib.gpk_trsv_lower_t(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
-                                             self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(tmp), B, self._stream())
-            self._st(code, "gpk_trsv_lower_t")
-            return b
-        x = torch.empty(b.shape, dtype=b.dtype, device=b.device)
-        x3, _ = _as3(x)
-        code = self.lib.gpk_trsm_lower_t(_dtype_id(l3), self._ptr(l3), n, _ld(l3), _bs(l3), self._ptr(dinv_sb), sb,
-                                         self._ptr(b3), nrhs, _ld(b3), _bs(b3), self._ptr(x3), _ld(x3), _bs(x3), B, self._stream())
-        self._st(code, "gpk_trsm_lower_t")
-        return x
+        return self._tri_solve("tri_solve_t_", "gpk_trsv_lower_t", "gpk_trsm_lower_t", l, dinv_sb, sb, b)
 
     # -- products ------------------------------------------------------------
     @_on_operand_device
@@ -718,13 +686,9 @@ class _HostDelta:
 
         return torch.as_tensor(np.ascontiguousarray(a), dtype=like.dtype, device=like.device)
 
-    def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
-        rest, delta, _ = self._split(terms)
-        if not delta:
-            return self._inner.kmat(terms, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out, accumulate=accumulate)
-        res = self._inner.kmat(rest, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec)
-        for _, (_, var, scale), eps in delta:
-            res = res + self._t(var * self._kappa(x, x if y is None else y, scale, eps), res)
+    @staticmethod
+    def _deliver(res, out, accumulate):
+        """``res`` as the result of a call with ``out`` / ``accumulate``."""
         if out is None:
             return res
         if accumulate:
@@ -732,6 +696,15 @@ class _HostDelta:
         else:
             out.copy_(res)
         return out
+
+    def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        rest, delta, _ = self._split(terms)
+        if not delta:
+            return self._inner.kmat(terms, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out, accumulate=accumulate)
+        res = self._inner.kmat(rest, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec)
+        for _, (_, var, scale), eps in delta:
+            res = res + self._t(var * self._kappa(x, x if y is None else y, scale, eps), res)
+        return self._deliver(res, out, accumulate)
 
     def kmat_diff(self, terms, x, y, dim_x, dim_y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
         """``HipBackend.kmat_diff`` in NumPy (fp64, rounded to the inputs' dtype), from the closed forms in ``include/gpk.h``: the
@@ -796,14 +769,7 @@ class _HostDelta:
             res[..., idx, idx] += diag_add
             if diag_vec is not None:
                 res[..., idx, idx] += diag_vec.detach().cpu().numpy().reshape(res.shape[:-2] + (res.shape[-1],))
-        res = self._t(res, x)
-        if out is None:
-            return res
-        if accumulate:
-            out += res
-        else:
-            out.copy_(res)
-        return out
+        return self._deliver(self._t(res, x), out, accumulate)
 
     def kdiag(self, terms, x):
         rest, delta, _ = self._split(terms)

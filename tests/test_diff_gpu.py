@@ -4,7 +4,8 @@ longdouble reference of ``tests/diff_reference.py``, and ``f.diff(dim)`` end to 
 Shapes are the smallest at which the tiling can go wrong: tiles are 32 rows by 128 (fp64) / 256 (fp32) columns, so ``(33, 65)`` has a
 second row band and partial tiles, ``(97, 259)`` a second column tile in both dtypes (the band walk's double-buffered Y staging);
 ``d <= 8`` takes the row-band kernel, ``d = 9`` the chunked one-tile kernel (the switch the release library offers; the native
-self-test, ``gpk_selftest --diff``, forces each through the development knob as well).
+self-test, ``gpk_selftest --diff``, forces each through the development knob as well).  A workgroup walks more than one column tile,
+and the lower triangle goes onto the compact 1-D grid, only when the launch is large: the two cases at the end reach both with batches.
 
 Value bound: ``|got - ref| <= C eps absum`` element by element, ``absum`` as defined in ``tests/diff_reference.py``; ``C`` =
 ``VALUE_BOUND`` is twice the worst ratio measured with these cases on an MI355X (``profiles/README.md``, "Derivative kernel").  Inputs
@@ -209,6 +210,58 @@ def test_error_codes(hip_backend):
             hip_backend.kmat_diff(ops.KTerms(terms, shapes), x, x, 0, 0)
     with pytest.raises(RuntimeError, match="status -23$"):
         hip_backend.kmat_diff(eq, x, x, 0, None, lower=True)
+
+
+# ---------------------------------------------------------------------------------------------
+# launch plans with more than one column tile per workgroup: the launcher gives a workgroup CT > 1 tiles only once the grid holds 6144
+# workgroups without them, so these cases are batches of many small matrices whose entries repeat three different ones.  They are
+# compared bit for bit with the same three matrices launched as a batch of 3 (CT = 1, one tile per pass: the path of every case
+# above); tests/test_kmat_plan.py asserts that the launcher's arithmetic gives these shapes the plans named here.
+# ---------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def three(n, m, d):
+    """Three fp32-representable input pairs, never modified."""
+    xb, yb = (r32(v) for v in D.inputs(n, m, d, seed=2, batch=3))
+    xb.setflags(write=False)
+    yb.setflags(write=False)
+    return xb, yb
+
+
+def repeated(a, batch, dtype):
+    """A batch whose entry ``b`` is entry ``b % 3`` of ``a``."""
+    return dev(a, dtype)[torch.arange(batch, device="cuda") % 3].contiguous()
+
+
+@pytest.mark.parametrize("dtype,m", [("float64", 259), ("float32", 600)])
+def test_walk_of_several_column_tiles(hip_backend, dtype, m):
+    """``gy * batch = 4 * 1536 = 6144``: CT = 8, and the workgroup walks the 3 column tiles of its band, the last one ragged -- the
+    double-buffered Y staging with the next tile's fetch under this tile's arithmetic."""
+    n, d, a, b, batch = 97, 3, 2, 0, 1536
+    xb, yb = three(n, m, d)
+    kt = ops.KTerms(*D.TABLES["all8"])
+    small = hip_backend.kmat_diff(kt, dev(xb, dtype), dev(yb, dtype), a, b)
+    refs = [D.diff_matrices(*D.TABLES["all8"], xb[i], yb[i], a, b)["dxy"] for i in range(3)]
+    accept(f"kmat_diff all8 dxy batch=3 {n}x{m} d{d}", small, np.stack([r[0] for r in refs]), np.stack([r[1] for r in refs]), dtype)
+    got = hip_backend.kmat_diff(kt, repeated(xb, batch, dtype), repeated(yb, batch, dtype), a, b)
+    assert got.shape == (batch, n, m)
+    assert bool((got.reshape(batch // 3, 3, n, m) == small).all())
+
+
+@pytest.mark.parametrize("dtype,n", [("float64", 300), ("float32", 600)])
+def test_compact_grid_with_two_tiles_per_workgroup(hip_backend, dtype, n):
+    """Lower triangle of a batch of 640 symmetric blocks: CT = 8 and 4 leave fewer than 6144 workgroups, CT = 2 does not, and two column
+    chunks per row band put the launch on the compact 1-D grid (8 / 16 row bands per chunk).  Against the lower triangle of the full
+    matrices of a batch of 3."""
+    d, a, batch = 3, 2, 640
+    xb, _ = three(n, 1, d)
+    kt = ops.KTerms(*D.TABLES["all8"])
+    dv = (np.arange(3 * n).reshape(3, n) % 16) / 8.0
+    full = hip_backend.kmat_diff(kt, dev(xb, dtype), None, a, a, diag_add=0.25, diag_vec=dev(dv, dtype))
+    low = hip_backend.kmat_diff(kt, repeated(xb, batch, dtype), None, a, a, lower=True, diag_add=0.25, diag_vec=repeated(dv, batch, dtype))
+    assert low.shape == (batch, n, n)
+    upper = torch.ones((n, n), dtype=torch.bool, device="cuda").triu(1)
+    for r in range(3):
+        assert bool(((low[r::3] == full[r]) | upper).all()), r
 
 
 # ---------------------------------------------------------------------------------------------
