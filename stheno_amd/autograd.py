@@ -331,9 +331,9 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
         parameter)."""
         key = (i, id(imap))
         if key not in where:
-            where[key] = len(us)
+            where[key] = (len(us), imap)              # (the map is kept: its id cannot be recycled while the table lives)
             us.append(parts[i][1] if imap is None else imap(parts[i][1]))
-        return where[key]
+        return where[key][0]
 
     for i, (pi, _) in enumerate(parts):
         for j in range(i + 1):
@@ -341,12 +341,12 @@ def joint_logpdf(mok, x, noise_vec, r, eps):
             groups = _k._map_groups(kern) if isinstance(kern, _k.Kernel) else None
             if groups is None:
                 return None
-            for kg, imap in groups:
+            for kg, imap_x, imap_y in groups:            # block (i, j) = sum_g k_g(imap_x(x_i), imap_y(x_j))
                 rows = kg.tensor_table()
-                if rows is None:
+                if rows is None or (i == j and not _k._same_map(imap_x, imap_y)):
                     return None
                 kd, pr = _pack(rows)
-                layout.append((i, j, kd, len(pr), mapped(i, imap), mapped(j, imap)))
+                layout.append((i, j, kd, len(pr), mapped(i, imap_x), mapped(j, imap_y)))
                 params.extend(pr)
     if not torch.is_grad_enabled() or not (any(p.requires_grad for p in params) or any(u.requires_grad for u in us) or r.requires_grad
                                             or (noise_vec is not None and noise_vec.requires_grad)):
@@ -381,6 +381,8 @@ def kernel_requires_grad(kernel, _depth=0):
         return any(kernel_requires_grad(ks[p], _depth + 1) for p in kernel.pids)
     for val in vars(kernel).values():
         if torch.is_tensor(val) and val.requires_grad:
+            return True
+        if isinstance(val, _k.InputMap) and val.requires_grad:       # a learnable shift, the parameters behind a feature map
             return True
         if isinstance(val, _k.Kernel) and kernel_requires_grad(val, _depth + 1):
             return True

@@ -184,12 +184,15 @@ class Kernel:
         return num_elements(x)
 
     def input_scaled_view(self):
-        """``(k, imap)`` such that ``self(x, y) == k(imap(x), imap(y))`` with ``k`` a sum of primitives
-        (``k.terms()`` is not None) and ``imap`` a differentiable map of the inputs (:class:`InputMap`: the division by
-        per-dimension length scales of ``k.stretch(vector)``, the ``(sin, cos)`` embedding of ``k.periodic(p)``), or None for
-        "inputs as they are"; None when the kernel has no such form.  The differentiable paths run ``k`` on the mapped inputs and
-        leave the map to torch, which carries the gradient to its parameters (length scales, period) and to ``x``."""
-        return (self, None) if self.terms() is not None else None
+        """``(k, imap_x, imap_y)`` such that ``self(x, y) == k(imap_x(x), imap_y(y))`` with ``k`` a sum of primitives
+        (``k.terms()`` is not None) and each ``imap`` a differentiable map of the inputs (:class:`InputMap`: the division by
+        per-dimension length scales of ``k.stretch(vector)``, the ``(sin, cos)`` embedding of ``k.periodic(p)``, a shift, a selection of
+        dimensions, a feature map, a chain of those), or None for "inputs as they are"; None when the kernel has no such form.  A kernel
+        that sees both arguments through the same map -- every kernel of a process with itself -- carries that map twice
+        (``_same_map(imap_x, imap_y)``); the two differ for cross-kernels such as ``k.shift(c, 0)``, the covariance of ``f.shift(c)``
+        with ``f``.  The differentiable paths run ``k`` on the mapped inputs and leave the maps to torch, which carries the gradient to
+        their parameters (length scales, period, shift, the weights of a feature map) and to ``x``."""
+        return (self, None, None) if self.terms() is not None else None
 
     # -- evaluation ------------------------------------------------------------
     def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None, out=None, accumulate=False):
@@ -247,11 +250,45 @@ class Kernel:
 
     __rmul__ = __mul__
 
-    def stretch(self, scale):
-        """``k.stretch(l)``: ``k(x / l, y / l)``.  ``l``: a scalar, or one length scale per input dimension."""
+    def stretch(self, scale, scale_y=_UNSET):
+        """``k.stretch(l)``: ``k(x / l, y / l)``.  ``l``: a scalar, or one length scale per input dimension.
+        ``k.stretch(l_x, l_y)``: ``k(x / l_x, y / l_y)``, scalars only (the cross-kernel of ``f.stretch(l)`` with ``f`` is
+        ``k.stretch(l, 1)``, its kernel ``k.stretch(l, l)``).  The two-argument form always divides the INPUTS; the one-argument form
+        of a periodic kernel hands the stretch to the kernel behind the embedding, as it always did."""
+        if scale_y is not _UNSET:
+            if _is_vector_scale(scale) or _is_vector_scale(scale_y):
+                raise NotImplementedError("the two-argument stretch takes scalars: per-dimension length scales that differ between the "
+                                          "arguments are not implemented")
+            return _stretch_arguments(self, scale, scale_y)
         if _is_vector_scale(scale):
             return InputScaled(self, scale)
+        if self.terms() is None and _map_groups(self) is not None:
+            return _stretch_groups(self, _as_param(scale))
         return Stretched(self, _as_param(scale))
+
+    def shift(self, c, c_y=_UNSET):
+        """``k.shift(c)``: ``k(x - c, y - c)`` (a stationary kernel is its own shift: ``k`` itself comes back);
+        ``k.shift(c_x, c_y)``: ``k(x - c_x, y - c_y)``.  ``c``: a number, a 0-dim tensor or one entry per input dimension, kept as
+        given (a learnable lag); the number ``0`` leaves that argument as it is."""
+        if c_y is _UNSET:
+            if self.stationary:
+                return self
+            c_y = c
+        mx = None if _is_number(c, 0) else _ShiftMap(c)
+        return _behind(self, mx, mx if c_y is c else (None if _is_number(c_y, 0) else _ShiftMap(c_y)))
+
+    def select(self, dims, dims_y=_UNSET):
+        """``k.select(dims)``: ``k(x[:, dims], y[:, dims])``; ``k.select(dims_x, dims_y)``: one selection per argument, ``None`` leaves
+        that argument as it is.  ``dims``: an input dimension or a sequence of them."""
+        mx = None if dims is None else _SelectMap(dims)
+        return _behind(self, mx, mx if dims_y is _UNSET else (None if dims_y is None else _SelectMap(dims_y)))
+
+    def transform(self, fn, fn_y=_UNSET):
+        """``k.transform(fn)``: ``k(fn(x), fn(y))`` for a callable from ``(..., N, D)`` to ``(..., N, D')`` -- a warping, a feature
+        map, a small ``torch.nn`` network whose parameters are learnt through ``logpdf``; ``k.transform(fn_x, fn_y)``: one per argument,
+        ``None`` is the identity."""
+        mx = None if fn is None else _TransformMap(fn)
+        return _behind(self, mx, mx if fn_y is _UNSET else (None if fn_y is None else _TransformMap(fn_y)))
 
     def periodic(self, period):
         """``k.periodic(p)``: ``k`` on ``(sin(2 pi x / p), cos(2 pi x / p))`` (mlkernels' ``Periodic``).  ``p``: a positive scalar,
@@ -270,7 +307,13 @@ class Kernel:
 
     def __reversed__(self):
         # sums of (stretched / scaled) primitives are symmetric, the zero kernel included -- and so are they behind input maps
-        return self if (self.terms() is not None or _map_groups(self) is not None) else Reversed(self)
+        # (... unless a group sees its two arguments through different maps: then the maps change places, group by group)
+        if self.terms() is not None or _symmetric_groups(self) is not None:
+            return self
+        groups = _map_groups(self)
+        if groups is not None:
+            return _sum_of_groups([(kern, my, mx) for kern, mx, my in groups])
+        return Reversed(self)
 
     def __eq__(self, other):
         if isinstance(self, ZeroKernel) and isinstance(other, ZeroKernel):
@@ -410,7 +453,7 @@ class Scaled(Kernel):
 
     def input_scaled_view(self):
         v = self.k.input_scaled_view()
-        return None if v is None else (Scaled(v[0], self.v), v[1])
+        return None if v is None else (Scaled(v[0], self.v), v[1], v[2])
 
     def pairwise(self, x, y=None, **kw):
         if self.terms() is not None:
@@ -418,6 +461,12 @@ class Scaled(Kernel):
         view = self.input_scaled_view()
         if view is not None:                       # v * k0(x / l): still ONE fused launch, on the divided inputs
             return _Mapped(*view).pairwise(x, y, **kw)
+        if kw.get("out") is not None or kw.get("accumulate"):
+            # a caller's view (a block of a multi-process matrix, rows under a matrix): the product below would leave it in a new
+            # tensor -- a scaled sum behind different maps goes group by group into the view, the factor in each group's variances
+            groups = _map_groups(self)
+            if groups is not None:
+                return _sum_of_groups(groups).pairwise(x, y, **kw)
         da, dv = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
         out = _as_float(self.v) * self.k.pairwise(x, y, **kw)
         return _add_diag(out, da, dv) if y is None else out
@@ -455,6 +504,7 @@ class InputMap:
     fused launch, lower-triangle-only / in-place-factorisable like any other."""
 
     param = None          # the tensor (or host value) the map depends on
+    keeps_stationary = True      # k0(m(x), m(y)) of a stationary k0 is still a function of x - y (a feature map: not in general)
 
     def __call__(self, x):
         raise NotImplementedError
@@ -518,37 +568,193 @@ class _PeriodMap(InputMap):
         return torch.cat([torch.sin(a), torch.cos(a)], dim=-1)
 
 
+class _ShiftMap(InputMap):
+    """``x - c``: ``c`` a number, a 0-dim tensor, or one entry per input dimension (kept as given: a learnable lag)."""
+
+    def __init__(self, c):
+        if not torch.is_tensor(c) and np.ndim(c) > 0:
+            c = tuple(float(v) for v in np.asarray(c, dtype=np.float64).reshape(-1))
+        elif not torch.is_tensor(c):
+            c = float(c)
+        elif c.dim() > 1:
+            raise ValueError("a shift is a scalar or a vector (one entry per input dimension)")
+        self.param = c
+
+    def __call__(self, x):
+        c = self.param
+        c = c.to(dtype=x.dtype, device=x.device) if torch.is_tensor(c) else torch.as_tensor(c, dtype=x.dtype, device=x.device)
+        if c.numel() > 1 and c.numel() != x.shape[-1]:
+            raise ValueError(f"inputs have {x.shape[-1]} dimensions, the shift has {c.numel()} entries")
+        return x - c
+
+
+class _StretchMap(InputMap):
+    """``x / s`` with a scalar ``s``: a stretch that cannot be folded into the term table, because a shift or a feature map sits behind
+    it or because the two arguments are stretched differently."""
+
+    def __init__(self, s):
+        self.param = _as_param(s)
+
+    def __call__(self, x):
+        s = self.param
+        return x / (s.to(dtype=x.dtype, device=x.device) if torch.is_tensor(s) else s)
+
+
+class _SelectMap(InputMap):
+    """``x[..., dims]``: the kernel sees these input dimensions only."""
+
+    def __init__(self, dims):
+        dims = [dims] if isinstance(dims, (int, np.integer)) and not isinstance(dims, bool) else list(dims)
+        if not dims:
+            raise ValueError("select needs at least one input dimension")
+        self.param = tuple(_as_dim(d) for d in dims)
+
+    def __call__(self, x):
+        if max(self.param) >= x.shape[-1]:
+            raise ValueError(f"inputs have {x.shape[-1]} dimensions, the kernel selects dimension {max(self.param)}")
+        return x[..., list(self.param)]
+
+
+class _TransformMap(InputMap):
+    """``fn(x)`` for any callable from ``(..., N, D)`` to ``(..., N, D')`` -- a feature map, a warping, a small network.  Two transform
+    maps are the same only if they hold the same callable OBJECT, and nothing vouches for a cached comparison (``stamp()`` is None).
+
+    ``requires_grad``: ONE rule for every callable, ``nn.Module`` or not -- the probe.  ``fn`` runs on a detached copy of the first row
+    of an input it was given, and the map is learnable if that output requires a gradient: parameters of a module, tensors a
+    function or a module's ``forward`` closes over, are all seen this way.  Before the first evaluation nothing is known, and unknown
+    counts as learnable: the guards err towards refusing, never towards a value cut off from the graph."""
+
+    keeps_stationary = False
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise TypeError("transform takes a callable from (..., N, D) to (..., N, D')")
+        self.param = self.fn = fn
+        self._probe = None
+
+    def __call__(self, x):
+        p = self._probe
+        if p is None or p.shape[-1] != x.shape[-1] or p.dtype != x.dtype or p.device != x.device:
+            # (one row of its own, taken once per kind of input: the input itself is not kept alive)
+            self._probe = x.detach()[(0,) * (x.dim() - 2)][:1].clone()
+        out = self.fn(x)
+        if not (torch.is_tensor(out) and out.dim() == x.dim() and out.shape[:-1] == x.shape[:-1]):
+            raise ValueError(f"a transform maps inputs (..., N, D) to (..., N, D'); got {tuple(getattr(out, 'shape', ()))} for "
+                             f"{tuple(x.shape)}")
+        return out
+
+    @property
+    def requires_grad(self):
+        if self._probe is None or self._probe.shape[-2] == 0:
+            return True
+        with torch.enable_grad():
+            out = self.fn(self._probe)
+        return bool(torch.is_tensor(out) and out.requires_grad)
+
+    def stamp(self):
+        return None
+
+    def same(self, other):
+        return type(other) is type(self) and other.fn is self.fn
+
+
+class _ChainMap(InputMap):
+    """Maps applied one after the other, ``maps[0]`` first.  An operation applied LATER in the kernel algebra acts FIRST on the inputs
+    (mlkernels): ``k.shift(c).select(0)`` is ``k(x[:, [0]] - c, ...)``, the chain ``(select, shift)``.  Built by :func:`_chain`, which
+    flattens nested chains and hands a chain of one element back as that element."""
+
+    def __init__(self, maps):
+        self.maps = tuple(maps)
+        self.keeps_stationary = all(m.keeps_stationary for m in self.maps)
+
+    param = property(lambda self: tuple(m.param for m in self.maps))
+
+    def __call__(self, x):
+        for m in self.maps:
+            x = m(x)
+        return x
+
+    @property
+    def requires_grad(self):
+        return any(m.requires_grad for m in self.maps)
+
+    def stamp(self):
+        stamps = tuple(m.stamp() for m in self.maps)
+        return None if None in stamps else stamps
+
+    def same(self, other):
+        return (type(other) is type(self) and len(other.maps) == len(self.maps)
+                and all(a.same(b) for a, b in zip(self.maps, other.maps)))
+
+
+def _chain(first, then):
+    """The map ``x -> then(first(x))`` (either may be None: the inputs as they are)."""
+    maps = [e for m in (first, then) if m is not None for e in (m.maps if isinstance(m, _ChainMap) else (m,))]
+    if not maps:
+        return None
+    return maps[0] if len(maps) == 1 else _ChainMap(maps)
+
+
+#: maps a scalar stretch applied in front of them may be folded THROUGH, into the term table behind them (today's behaviour of
+#: ``InputScaled.stretch`` / ``Periodic.stretch``, where mlkernels hands the stretch to the kernel behind the map)
+_STRETCH_FOLDS_THROUGH = (_ScaleMap, _PeriodMap, _SelectMap, _StretchMap)
+
+
+def _folds_stretch(imap):
+    return imap is None or all(isinstance(m, _STRETCH_FOLDS_THROUGH) for m in (imap.maps if isinstance(imap, _ChainMap) else (imap,)))
+
+
 class _Mapped(Kernel):
-    """``k0(imap(x), imap(y))`` for a sum of primitives ``k0`` (or anything whose ``pairwise`` takes mapped inputs)."""
+    """``k0(imap_x(x), imap_y(y))`` for a sum of primitives ``k0`` (or anything whose ``pairwise`` takes mapped inputs).  One map: both
+    arguments see it.  With two DIFFERENT maps the kernel is a cross-kernel: ``k(x)`` is the full block ``k0(imap_x(x), imap_y(x))``,
+    not symmetric -- ``lower`` and the diagonal additions are refused, as the one-sided blocks of ``gpk_kmat_diff`` refuse them."""
 
-    def __init__(self, k, imap):
-        self.k, self.imap = k, imap
-        self.stationary = k.stationary
+    def __init__(self, k, imap, imap_y=_UNSET):
+        self.k, self.imap_x, self.imap_y = k, imap, (imap if imap_y is _UNSET else imap_y)
+        self.stationary = bool(k.stationary and self.symmetric and (imap is None or imap.keeps_stationary))
 
-    def _mapped(self, x):
+    @property
+    def symmetric(self):
+        return _same_map(self.imap_x, self.imap_y)
+
+    def _mapped(self, x, imap):
         x = uprank(x)
         if isinstance(x, MultiInput):
             raise ValueError(f"{type(self).__name__} is a single-output kernel; it cannot take multi-process inputs")
         # (values only: the differentiable log-density / bound take the kernel apart through `input_scaled_view`
         # and map the inputs themselves; everything that is not covered there refuses loudly at its own entry)
-        return x.detach() if self.imap is None else self.imap.values(x)
+        return x.detach() if imap is None else imap.values(x)
 
     def input_scaled_view(self):
-        return (self.k, self.imap)
+        return (self.k, self.imap_x, self.imap_y)
 
     def num_outputs(self, x):
         return self.k.num_outputs(x)
 
     def pairwise(self, x, y=None, **kw):
-        return self.k.pairwise(self._mapped(x), None if y is None else self._mapped(y), **kw)
+        if self.symmetric:
+            return self.k.pairwise(self._mapped(x, self.imap_x), None if y is None else self._mapped(y, self.imap_x), **kw)
+        if y is None:
+            if kw.get("lower") or kw.get("diag_add") or kw.get("diag_vec") is not None:
+                raise ValueError("a kernel behind two different input maps is not symmetric: k(x) is the full block, without `lower` "
+                                 "and without additions to the diagonal")
+            kw = {key: val for key, val in kw.items() if key not in ("lower", "diag_add", "diag_vec")}
+            y = x
+        return self.k.pairwise(self._mapped(x, self.imap_x), self._mapped(y, self.imap_y), **kw)
 
     def elwise(self, x, y=None, **kw):
         if y is not None and y is not x:
             raise NotImplementedError("elwise is implemented for identical inputs")
-        return self.k.elwise(self._mapped(x), **kw)
+        if not self.symmetric:
+            raise NotImplementedError("elwise is implemented for identical inputs behind the same map in both arguments")
+        return self.k.elwise(self._mapped(x, self.imap_x), **kw)
 
     def __reversed__(self):
-        return self                      # k(m(x), m(y)) of a symmetric k is symmetric
+        # k(m(x), m(y)) of a symmetric k is symmetric; behind two maps the maps change places
+        return self if self.symmetric else _Mapped(self.k, self.imap_y, self.imap_x)
+
+    def __repr__(self):
+        return f"({self.k!r} behind {type(self.imap_x).__name__}, {type(self.imap_y).__name__})"
 
 
 class InputScaled(_Mapped):
@@ -569,10 +775,12 @@ class InputScaled(_Mapped):
         if not bool((scales > 0).all()):
             raise ValueError("length scales must be positive")
         self.k, self.scales = k, scales
-        self.imap = _ScaleMap(scales)
+        self.imap_x = self.imap_y = _ScaleMap(scales)
         self.stationary = k.stationary
 
-    def stretch(self, scale):
+    def stretch(self, scale, scale_y=_UNSET):
+        if scale_y is not _UNSET:
+            return Kernel.stretch(self, scale, scale_y)
         if _is_vector_scale(scale):
             return InputScaled(self.k, self.scales * (scale if torch.is_tensor(scale) else torch.as_tensor(scale)).to(self.scales))
         return InputScaled(self.k, self.scales * _as_float(scale))
@@ -600,10 +808,12 @@ class Periodic(_Mapped):
         if not ok:
             raise ValueError("periods must be positive")
         self.k, self.period = k, period
-        self.imap = _PeriodMap(period)
+        self.imap_x = self.imap_y = _PeriodMap(period)
         self.stationary = k.stationary
 
-    def stretch(self, scale):
+    def stretch(self, scale, scale_y=_UNSET):
+        if scale_y is not _UNSET:
+            return Kernel.stretch(self, scale, scale_y)
         return Periodic(self.k.stretch(scale), self.period)      # (mlkernels: the stretch goes to the kernel behind the map)
 
     def __repr__(self):
@@ -645,8 +855,9 @@ def _same_map(a, b):
 
 
 def _map_groups(k):
-    """A kernel as groups of terms that see the same inputs: ``[(k_g, imap_g)]`` with ``k(x, y) = sum_g k_g(imap_g(x), imap_g(y))``,
-    every ``k_g`` a sum of primitives; None when the kernel has no such form.  One group: ``input_scaled_view()``."""
+    """A kernel as groups of terms that see the same inputs: ``[(k_g, imap_x, imap_y)]`` with ``k(x, y) = sum_g k_g(imap_x(x),
+    imap_y(y))``, every ``k_g`` a sum of primitives; None when the kernel has no such form.  One group: ``input_scaled_view()``.  Two
+    summands share a group only when they agree on BOTH maps."""
     v = k.input_scaled_view()
     if v is not None:
         return [v]
@@ -655,18 +866,27 @@ def _map_groups(k):
         if ga is None or gb is None:
             return None
         out = list(ga)
-        for kern, m in gb:
-            for i, (k2, m2) in enumerate(out):
-                if _same_map(m, m2):
-                    out[i] = (Sum(k2, kern), m2)
+        for kern, mx, my in gb:
+            for i, (k2, mx2, my2) in enumerate(out):
+                if _same_map(mx, mx2) and _same_map(my, my2):
+                    out[i] = (Sum(k2, kern), mx2, my2)
                     break
             else:
-                out.append((kern, m))
+                out.append((kern, mx, my))
         return out
     if isinstance(k, Scaled):
         g = _map_groups(k.k)
-        return None if g is None else [(Scaled(kern, k.v), m) for kern, m in g]
+        return None if g is None else [(Scaled(kern, k.v), mx, my) for kern, mx, my in g]
     return None
+
+
+def _symmetric_groups(k):
+    """``_map_groups(k)`` if every group sees both arguments through the same map (a kernel matrix ``k(x)`` is then symmetric: built
+    lower-only, factorised in place), else None."""
+    groups = _map_groups(k)
+    if groups is None or not all(_same_map(mx, my) for _, mx, my in groups):
+        return None
+    return groups
 
 
 class Sum(Kernel):
@@ -689,7 +909,7 @@ class Sum(Kernel):
         # -- and again whenever one of them has been written in place since (the answer of `torch.equal` must not outlive
         # the values it compared; tensors without a version counter are compared every time)
         va, vb = self.a.input_scaled_view(), self.b.input_scaled_view()
-        stamp = tuple(_scale_stamp(v[1]) for v in (va, vb) if v is not None)
+        stamp = tuple(_scale_stamp(m) for v in (va, vb) if v is not None for m in v[1:])
         if self._view is _UNSET or None in stamp or stamp != self._view_stamp:
             self._view = self._input_scaled_view()
             self._view_stamp = stamp
@@ -699,7 +919,8 @@ class Sum(Kernel):
         va, vb = self.a.input_scaled_view(), self.b.input_scaled_view()
         if va is None or vb is None:
             return None
-        return (Sum(va[0], vb[0]), va[1]) if _same_map(va[1], vb[1]) else None      # different maps (length-scale vectors, periods): no common one
+        # different maps (length-scale vectors, periods, shifts, ...) in either argument: no common one
+        return (Sum(va[0], vb[0]), va[1], va[2]) if (_same_map(va[1], vb[1]) and _same_map(va[2], vb[2])) else None
 
     def pairwise(self, x, y=None, **kw):
         if self.terms() is not None:
@@ -716,8 +937,8 @@ class Sum(Kernel):
             first = not kw.pop("accumulate", False)
             xr = uprank(x)
             yr = None if y is None else uprank(y)
-            for kern, m in groups:
-                g = _Mapped(kern, m)
+            for group in groups:
+                g = _Mapped(*group)
                 out = g.pairwise(xr, yr, out=out, accumulate=not first, diag_add=da if first else 0.0, diag_vec=dv if first else None, **kw)
                 first = False
             return out
@@ -761,6 +982,95 @@ class Reversed(Kernel):
 
 
 # ---------------------------------------------------------------------------
+# input maps in the kernel algebra: shift, select, transform, the two-argument stretch (mlkernels' semantics)
+# ---------------------------------------------------------------------------
+class PosteriorOperationError(NotImplementedError):
+    """A posterior mean / kernel was asked for an operation it has no form for.  ``GP`` catches exactly this when it registers a derived
+    process in a posterior conditioned earlier, and ``post(p)`` there refuses with the reason."""
+
+
+class PosteriorInputMapError(PosteriorOperationError):
+    """A posterior mean / kernel was asked to shift, stretch, select or transform its inputs: map the prior process, condition then,
+    and look the mapped process up under the posterior."""
+
+
+def _is_number(v, value):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v == value
+
+
+def _sum_of_groups(groups):
+    """The kernel ``sum_g k_g(imap_x(x), imap_y(y))`` of groups as ``_map_groups`` lists them."""
+    out = None
+    for kern, mx, my in groups:
+        g = kern if (mx is None and my is None) else _Mapped(kern, mx, my)
+        out = g if out is None else out + g
+    return out
+
+
+def _behind(k, mx, my):
+    """``k(mx(x), my(y))`` as a kernel (a map that is None: that argument as it is).  The new maps act FIRST on the inputs, whatever
+    maps ``k`` sits behind already come after them.  Refuses, loudly, what has no form as groups of primitives behind maps."""
+    if mx is None and my is None or isinstance(k, ZeroKernel):
+        return k
+    groups = _map_groups(k)
+    if groups is not None:
+        both = mx is my
+        out = []
+        for kern, gx, gy in groups:
+            cx = _chain(mx, gx)
+            out.append((kern, cx, cx if (both and gx is gy) else _chain(my, gy)))
+        return _sum_of_groups(out)
+    if isinstance(k, Sum):
+        return _behind(k.a, mx, my) + _behind(k.b, mx, my)
+    if isinstance(k, Scaled):
+        return Scaled(_behind(k.k, mx, my), k.v)
+    if isinstance(k, Reversed):
+        return reversed(_behind(k.k, my, mx))
+    if isinstance(k, (PosteriorKernel, SubspaceKernel)):
+        raise PosteriorInputMapError("input maps (shift / stretch / select / transform) of posterior kernels are not implemented: map the "
+                                     "prior process, condition then, and look the mapped process up under the posterior")
+    raise NotImplementedError(f"input maps (shift / select / transform / the two-argument stretch) are not implemented for "
+                              f"{type(k).__name__}: it is no sum of primitive kernels behind input maps")
+
+
+def _stretch_arguments(k, sx, sy):
+    """``k(x / sx, y / sy)`` for scalars: the inputs themselves are divided, whatever maps ``k`` sits behind.  The same stretch in both
+    arguments is folded into a group's term table where that is the same function (no map, a selection, per-dimension scales, another
+    stretch -- NOT the periodic embedding); everything else becomes a stretch map at the head of each argument's chain."""
+    same = sx is sy or (not torch.is_tensor(sx) and not torch.is_tensor(sy) and float(sx) == float(sy))
+    groups = _map_groups(k) if same and not _is_number(sx, 1) else None
+    if groups is None:
+        return _behind(k, *(None if _is_number(s, 1) else _StretchMap(s) for s in (sx, sy)))
+
+    def divides_inputs(imap):
+        return _folds_stretch(imap) and not any(isinstance(m, _PeriodMap) for m in (getattr(imap, "maps", None) or (imap,)))
+
+    out, m = [], _StretchMap(sx)
+    for kern, gx, gy in groups:
+        if divides_inputs(gx) and divides_inputs(gy):
+            out.append((kern.stretch(_as_param(sx)), gx, gy))
+        else:
+            cx = _chain(m, gx)
+            out.append((kern, cx, cx if gx is gy else _chain(m, gy)))
+    return _sum_of_groups(out)
+
+
+def _stretch_groups(k, s):
+    """``k.stretch(s)`` with a scalar ``s`` for a kernel that is groups of primitives behind maps: the stretch is folded into the
+    group's term table where it commutes with the maps (a selection, per-dimension scales, the periodic embedding), and becomes a map
+    of its own, applied first, in front of a shift or a feature map (``k.shift(c).stretch(s)`` is ``k(x / s - c, ...)``)."""
+    out = []
+    for kern, gx, gy in _map_groups(k):
+        if _folds_stretch(gx) and _folds_stretch(gy):
+            out.append((kern.stretch(s), gx, gy))
+        else:
+            m = _StretchMap(s)
+            cx = _chain(m, gx)
+            out.append((kern, cx, cx if gx is gy else _chain(m, gy)))
+    return _sum_of_groups(out)
+
+
+# ---------------------------------------------------------------------------
 # derivatives (mlkernels' DerivativeKernel behind GP.diff: stheno/model/measure.py:343-360)
 # ---------------------------------------------------------------------------
 #: kinds the fused derivative launch knows, with the value of ``-2 kappa'(0)``: what ``d^2 k / dx_a dy_a`` is at coincident points per unit
@@ -768,7 +1078,7 @@ class Reversed(Kernel):
 _DIFF_AT_ZERO = {"eq": 1.0, "rq": 1.0, "matern32": 3.0, "matern52": 5.0 / 3.0, "linear": 1.0, "const": 0.0}
 
 
-class PosteriorDerivativeError(NotImplementedError):
+class PosteriorDerivativeError(PosteriorOperationError):
     """A posterior mean / kernel was asked for its derivative: differentiate the prior process, then look the derivative up under the
     posterior (``post(f.diff())``)."""
 
@@ -792,11 +1102,14 @@ def _diff_kernel(k, a, b):
         return DiffKernel(k.k, k.dim_x if a is None else a, k.dim_y if b is None else b)
     view = k.input_scaled_view()
     if view is not None:
-        kern, imap = view
+        kern, imap, imap_y = view
         if isinstance(imap, _PeriodMap):
             raise NotImplementedError("derivatives of kernels behind a periodic map are not implemented")
-        if imap is not None and not isinstance(imap, _ScaleMap):
-            raise NotImplementedError(f"derivatives behind the input map {type(imap).__name__} are not implemented")
+        for m in (imap, imap_y):
+            if m is not None and not isinstance(m, _ScaleMap):
+                raise NotImplementedError(f"derivatives behind the input map {type(m).__name__} are not implemented")
+        if not _same_map(imap, imap_y):
+            raise NotImplementedError("derivatives behind two different input maps are not implemented")
         bad = sorted({kind for kind, _, _ in kern.terms() if kind not in _DIFF_AT_ZERO})
         if bad:
             raise NotImplementedError(f"kernels of the kind {', '.join(bad)} are not differentiable (Matern12 has a kink at distance 0, "
@@ -834,7 +1147,7 @@ class DiffKernel(Kernel):
 
     def _parts(self, x):
         """``(kern, imap, fa, fb)``: the sum of primitives behind the map and the chain-rule factors of the two slots."""
-        kern, imap = self.k.input_scaled_view()
+        kern, imap, _ = self.k.input_scaled_view()          # (one map for both arguments: _diff_kernel admits nothing else)
         fa = fb = 1.0
         if imap is not None:
             scales = imap.param.detach().to(dtype=torch.float64, device="cpu")
@@ -904,12 +1217,17 @@ class DiffKernel(Kernel):
 # Cartesian products of processes (stheno/mo/kernel.py, stheno/mo/mean.py, measure.py:404-423)
 # ---------------------------------------------------------------------------
 def _eval_into(k, x, y, view, lower=False):
-    """Write ``k(x, y)`` (``y is None``: symmetric) into the matrix view ``view``: a sum of
-    primitives -- or a derivative of one (``DiffKernel``) -- goes straight into the block (one fused launch, no temporary)."""
+    """Write ``k(x, y)`` (``y is None``: symmetric) into the matrix view ``view``: a sum of primitives, a derivative of one
+    (``DiffKernel``), or groups of primitives behind input maps go straight into the block (one fused launch per group, no temporary)."""
     if isinstance(k, ZeroKernel):
         view.zero_()
     elif (k.terms() is not None or isinstance(k, DiffKernel)) and not isinstance(y, MultiInput):
         k.pairwise(x, y, lower=lower, out=view)
+    elif isinstance(k, Kernel) and _map_groups(k) is not None and not isinstance(x, MultiInput) and not isinstance(y, MultiInput):
+        # (`lower` only where the block is symmetric: a cross-kernel behind two maps writes its full block)
+        got = k.pairwise(x, y, out=view, **({"lower": True} if lower else {}))
+        if got.data_ptr() != view.data_ptr():          # (a kernel that handed back a tensor of its own: the copy it always paid)
+            view.copy_(got)
     else:
         view.copy_(k.pairwise(x, y))
 
@@ -1046,6 +1364,25 @@ class Mean:
         """``dm / dx[dim]`` as a mean (the mean of ``f.diff(dim)``, ``measure.py:357``)."""
         raise NotImplementedError(f"derivatives are not implemented for {type(self).__name__}")
 
+    # -- input maps: m(imap(x)), the mean of f.shift(c) / f.stretch(s) / f.select(dims) / f.transform(fn) -------------------------
+    def shift(self, c):
+        return self if _is_number(c, 0) else self._behind(_ShiftMap(c))
+
+    def stretch(self, s):
+        if _is_vector_scale(s):
+            return self._behind(_ScaleMap(s if torch.is_tensor(s) else torch.as_tensor(s)))
+        return self if _is_number(s, 1) else self._behind(_StretchMap(s))
+
+    def select(self, dims):
+        return self._behind(_SelectMap(dims))
+
+    def transform(self, fn):
+        return self._behind(_TransformMap(fn))
+
+    def _behind(self, imap):
+        """``x -> self(imap(x))`` as a mean; constants are their own, sums and scalings distribute."""
+        return MappedMean(self, imap)
+
 
 class ZeroMean(Mean):
     def __call__(self, x, cache=None):
@@ -1055,6 +1392,9 @@ class ZeroMean(Mean):
     def diff(self, dim=0):
         return ZeroMean()
 
+    def _behind(self, imap):
+        return self
+
     def __repr__(self):
         return "0"
 
@@ -1063,6 +1403,9 @@ class OneMean(Mean):
     def __call__(self, x, cache=None):
         x = uprank(x)
         return torch.ones(x.shape[:-1] + (1,), dtype=x.dtype, device=x.device)
+
+    def _behind(self, imap):
+        return self
 
     def diff(self, dim=0):
         return ZeroMean()
@@ -1114,6 +1457,10 @@ class DiffMean(Mean):
     def diff(self, dim=0):
         raise NotImplementedError("second derivatives (f.diff().diff()) are not implemented")
 
+    def _behind(self, imap):
+        raise NotImplementedError("input maps (shift / stretch / select / transform) of a derivative mean are not implemented: map the "
+                                  "process first, differentiate then")
+
     def __repr__(self):
         return f"d({self.dim}) {self.m!r}"
 
@@ -1127,6 +1474,9 @@ class ScaledMean(Mean):
 
     def diff(self, dim=0):
         return ScaledMean(self.m.diff(dim), self.v)
+
+    def _behind(self, imap):
+        return ScaledMean(self.m._behind(imap), self.v)
 
     def __repr__(self):
         return f"{self.v} * {self.m!r}"
@@ -1142,8 +1492,34 @@ class SumMean(Mean):
     def diff(self, dim=0):
         return self.a.diff(dim) + self.b.diff(dim)
 
+    def _behind(self, imap):
+        return self.a._behind(imap) + self.b._behind(imap)
+
     def __repr__(self):
         return f"{self.a!r} + {self.b!r}"
+
+
+class MappedMean(Mean):
+    """``m(imap(x))``: a mean behind a map of its inputs (:class:`InputMap`).  The map is a torch expression: a learnable shift or the
+    parameters of a feature map get their gradient through the mean as through the kernel.  A map applied later acts first."""
+
+    def __init__(self, m, imap):
+        self.m, self.imap = m, imap
+
+    def __call__(self, x, cache=None):
+        x = uprank(x)
+        if isinstance(x, MultiInput):
+            raise ValueError("a mean behind an input map is the mean of one process; it cannot take multi-process inputs")
+        return _call_mean(self.m, self.imap(x), None)
+
+    def _behind(self, imap):
+        return MappedMean(self.m, _chain(imap, self.imap))
+
+    def diff(self, dim=0):
+        raise NotImplementedError(f"derivatives behind the input map {type(self.imap).__name__} are not implemented")
+
+    def __repr__(self):
+        return f"({self.m!r} behind {type(self.imap).__name__})"
 
 
 def _wrap_mean(m):
@@ -1165,6 +1541,9 @@ class MultiOutputMean(Mean):
 
         self._measure = weakref.ref(measure)
         self.pids = tuple(id(p) for p in ps)
+
+    def _behind(self, imap):
+        raise NotImplementedError("input maps of the mean of a product process are not implemented: map the component processes")
 
     def __call__(self, x, cache=None):
         means = self._measure().means
@@ -1342,6 +1721,10 @@ class PosteriorMean(Mean):
         raise PosteriorDerivativeError("derivatives of posterior means are not implemented: differentiate the prior process and look its "
                                        "derivative up under the posterior (`post(f.diff())`)")
 
+    def _behind(self, imap):
+        raise PosteriorInputMapError("input maps (shift / stretch / select / transform) of posterior means are not implemented: map the "
+                                     "prior process, condition then, and look the mapped process up under the posterior")
+
     def _residual(self):
         if self._r is None:
             y = uprank(self.y)
@@ -1438,8 +1821,8 @@ def _learnable_marginals(pm, pk, x, cache):
     noise_vec = K_z.differentiable_noise()
     if noise_vec is NotImplemented or (noise_vec is not None and noise_vec.dim() != 1):
         return None
-    groups = _map_groups(k)              # terms behind the same input map: one group is the plain case
-    if groups is None or not all(kern.tensor_terms() for kern, _ in groups):
+    groups = _symmetric_groups(k)        # terms behind the same input map: one group is the plain case
+    if groups is None or not all(kern.tensor_terms() for kern, _, _ in groups):
         return None
     from . import autograd as _ag
 
@@ -1454,7 +1837,7 @@ def _learnable_marginals(pm, pk, x, cache):
                  or (noise_vec is not None and noise_vec.requires_grad) or (r is not None and r.requires_grad))
     if not learnable:
         return None
-    mapped = [(kern, z if imap is None else imap(z), x if imap is None else imap(x)) for kern, imap in groups]
+    mapped = [(kern, z if imap is None else imap(z), x if imap is None else imap(x)) for kern, imap, _ in groups]
     for _, zin, xin in mapped:
         if zin.requires_grad or xin.requires_grad:
             _ag.check_input_dims(xin)

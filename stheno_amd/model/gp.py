@@ -51,7 +51,8 @@ class GP(RandomProcess):
         # and the Cholesky factor it owns -- dies with its last user handle, not with the prior GP.
         self._measure0 = None
         self._backrefs = weakref.WeakSet()
-        self._refused_by = weakref.WeakSet()      # posteriors conditioned before this (derivative) process existed: see `diff`
+        self._refused_by = weakref.WeakSet()      # posteriors conditioned before this (derived) process existed: see `_derived`
+        self._refusal = None                      # ... and what they refused with
         self._parents = ()      # processes this one is derived from (kept alive: rules refer to their ids)
         if len(args) == 0:
             return
@@ -143,15 +144,41 @@ class GP(RandomProcess):
         conditioned EARLIER: a posterior mean / kernel has no derivative (``PosteriorDerivativeError``, nothing else is caught), so
         such a measure is remembered on the new process and ``post(df)`` there refuses with that reason.  Differentiate first,
         condition then."""
+        return self._derived(lambda measure, res: measure.diff(res, self, dim))
+
+    def _derived(self, register):
+        """A new process derived from ``self`` by an operation on its mean and kernel (a derivative, a map of the inputs),
+        registered by ``register(measure, new process)`` in every measure that knows ``self``.  A posterior conditioned EARLIER
+        cannot take it (``PosteriorOperationError``, nothing else is caught): the refusal is remembered on the new process and the
+        lookup ``post(new process)`` raises it with its reason."""
         res = GP()
         res._parents = (self,)
-        self.measure.diff(res, self, dim)
+        register(self.measure, res)
         for measure in list(self._backrefs):
             try:
-                measure.diff(res, self, dim)
-            except _k.PosteriorDerivativeError:
+                register(measure, res)
+            except _k.PosteriorOperationError as err:
                 res._refused_by.add(measure)
+                res._refusal = err
         return res
+
+    def shift(self, c):
+        """``f.shift(c)``: the process ``x -> f(x - c)`` (``gp.py:190``), jointly Gaussian with ``f``; ``c`` may be a learnable tensor
+        (a lag between two sensors, learnt from the joint log-density)."""
+        return self._derived(lambda measure, res: measure.shift(res, self, c))
+
+    def stretch(self, s):
+        """``f.stretch(s)``: the process ``x -> f(x / s)`` (``gp.py:197``), ``s`` a scalar (a vector is refused before anything is registered)."""
+        return self._derived(lambda measure, res: measure.stretch(res, self, s))
+
+    def select(self, *dims):
+        """``f.select(0, 2)``: the process ``x -> f(x[:, [0, 2]])`` (``gp.py:204``)."""
+        dims = tuple(dims[0]) if len(dims) == 1 and isinstance(dims[0], (list, tuple)) else dims
+        return self._derived(lambda measure, res: measure.select(res, self, dims))
+
+    def transform(self, fn):
+        """``f.transform(fn)``: the process ``x -> f(fn(x))`` (``gp.py:211``)."""
+        return self._derived(lambda measure, res: measure.transform(res, self, fn))
 
     @property
     def stationary(self):

@@ -116,6 +116,10 @@ class Measure:
         if isinstance(p, FDD):
             return self(p.p)(p.x, p.noise)
         if self in p._refused_by:
+            if isinstance(p._refusal, _k.PosteriorInputMapError):
+                raise _k.PosteriorInputMapError(
+                    "this posterior was conditioned before the mapped process was created and cannot take it (" + str(p._refusal)
+                    + "): call `f.shift(...)` / `.stretch` / `.select` / `.transform` first, condition then")
             raise _k.PosteriorDerivativeError(
                 "this posterior was conditioned before the derivative process was created and cannot take it (a posterior mean / "
                 "kernel has no derivative): call `f.diff()` first, condition then, and look the derivative up as `post(df)`")
@@ -155,6 +159,29 @@ class Measure:
         wself, pid = weakref.ref(self), id(p)
         return self._update(p_diff, self.means[p].diff(dim), self.kernels[p].diff(dim),
                             lambda j: wself().kernels[pid, j].diff(dim, None))
+
+    def _input_mapped(self, p_new, p, mean, kernel, left):
+        """Register ``p_new`` as ``p`` behind a map of its inputs (``measure.py:271-341``): mean and kernel mapped, the cross-kernel
+        with any other process mapped in its first argument only."""
+        wself, pid = weakref.ref(self), id(p)
+        return self._update(p_new, mean(self.means[p]), kernel(self.kernels[p]), lambda j: left(wself().kernels[pid, j]))
+
+    def shift(self, p_shifted, p, c):
+        return self._input_mapped(p_shifted, p, lambda m: m.shift(c), lambda k: k.shift(c), lambda k: k.shift(c, 0))
+
+    def stretch(self, p_stretched, p, s):
+        if _k._is_vector_scale(s):
+            raise NotImplementedError("f.stretch with one length scale per input dimension is not implemented (the cross-kernel with "
+                                      "other processes would be a two-argument stretch by a vector): stretch the kernel, "
+                                      "`GP(k.stretch([l0, l1]))`")
+        return self._input_mapped(p_stretched, p, lambda m: m.stretch(s), lambda k: k.stretch(s, s), lambda k: k.stretch(s, 1))
+
+    def select(self, p_selected, p, dims):
+        dims = list(dims)
+        return self._input_mapped(p_selected, p, lambda m: m.select(dims), lambda k: k.select(dims), lambda k: k.select(dims, None))
+
+    def transform(self, p_transformed, p, fn):
+        return self._input_mapped(p_transformed, p, lambda m: m.transform(fn), lambda k: k.transform(fn), lambda k: k.transform(fn, None))
 
     def cross(self, p_cross, *ps):
         """Register ``p_cross`` as the Cartesian product of ``ps`` (``measure.py:404-423``): its

@@ -227,9 +227,9 @@ class AbstractPseudoObservations(AbstractObservations):
         view = k.input_scaled_view() if hasattr(k, "input_scaled_view") else None
         if view is None or isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
             return autograd.kernel_requires_grad(k) or self.y.requires_grad
-        kern, imap = view
+        kern, imap, _ = view
         return (autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, self.y - measure.means[p_x](x))
-                or (imap is not None and imap.requires_grad))
+                or any(m is not None and m.requires_grad for m in view[1:]))
 
     def _differentiable(self, measure):
         from .. import autograd
@@ -242,11 +242,17 @@ class AbstractPseudoObservations(AbstractObservations):
             return None
         k = measure.kernels[p_z]
         view = k.input_scaled_view()
-        if view is None:
+        if view is None or not _k._same_map(view[1], view[2]):
             return None
-        kern, imap = view                         # k(a, b) = kern(imap(a), imap(b))
+        kern, imap, _ = view                      # k(a, b) = kern(imap(a), imap(b))
         y_bar = self.y - measure.means[p_x](x)
-        if not (autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, y_bar) or (imap is not None and imap.requires_grad)):
+        need = autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, y_bar) or (imap is not None and imap.requires_grad)
+        if not need and p_x is not p_z:
+            # data on a process mapped from the inducing points' one (`g = f.shift(tau)`, `f.transform(net)`): a learnable map sits in
+            # the data's kernel and in the cross-kernel only -- outside this path, and refused below rather than detached
+            need = any(m is not None and m.requires_grad for other in (measure.kernels[p_x], measure.kernels[p_z, p_x])
+                       for g in (_k._map_groups(other) or []) for m in g[1:])
+        if not need:
             return None
         if not (measure.kernels[p_x] is k and measure.kernels[p_z, p_x] is k and isinstance(noise_z, Zero)
                 and x.dim() == 2 and z.dim() == 2):

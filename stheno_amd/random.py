@@ -260,13 +260,14 @@ class Normal(RandomVector):
             # k(x) = sum_g k_g(m_g(x)) with every k_g a sum of primitives (m_g: the division by per-dimension length scales, the periodic
             # embedding, or none): the fused path runs k_g on the mapped inputs; torch differentiates the maps (d/dl, d/dperiod, d/dx).
             # One group is the plain case; several go group by group through the unbatched log-density only.
-            from .kernels import _map_groups
+            # (a kernel matrix k(x) is symmetric: every group sees both arguments through the same map)
+            from .kernels import _symmetric_groups
 
-            groups = _map_groups(var.kernel) if torch.is_tensor(var.x) else None
+            groups = _symmetric_groups(var.kernel) if torch.is_tensor(var.x) else None
             if groups is not None and len(groups) > 1 and r.dim() != 2:
                 groups = None
-            if noise_vec is not NotImplemented and groups is not None and all(kern.tensor_terms() is not None for kern, _ in groups):
-                mapped = [(kern, var.x if imap is None else imap(var.x)) for kern, imap in groups]
+            if noise_vec is not NotImplemented and groups is not None and all(kern.tensor_terms() is not None for kern, _, _ in groups):
+                mapped = [(kern, var.x if imap is None else imap(var.x)) for kern, imap, _ in groups]
                 if _ag.groups_need_grad(mapped, noise_vec, r, noise_mat):
                     for _, xin in mapped:
                         if xin.requires_grad:
