@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void sum_lower_kernel(const T* __restrict__ pa
     const int64_t c = c0 + (int64_t)threadIdx.x * VEC;
     for (int i = 0; i < 16; ++i) {
         const int64_t r = r0 + i;
-        if (r >= n || c > r) continue;        // (whole vectors up to the one holding the diagonal: a few entries above it are written too -- with the sums of what the products wrote there or left there, never read as part of a lower triangle)
+        if (r >= n || c > r) continue;        // (whole vectors are LOADED up to the one holding the diagonal, so a few entries above it are read and added up; only col <= row is ever stored -- nothing above the diagonal of `out` is written)
         if ((vec_ok & 1) && c + VEC <= n) {
             vec_t acc = *reinterpret_cast<const vec_t*>(parts + r * ldp + c);
             for (int s = 1; s < S; ++s) {

@@ -600,7 +600,8 @@ class HipBackend:
     @_on_operand_device
     def sum_lower(self, parts, out):
         """``out[i, j] = sum_s parts[s, i, j]`` for ``j <= i`` (``gpk_sum_lower``): the partial products of a split-K symmetric update,
-        of which only the lower tiles were written, added up in a fixed order.  Entries above the diagonal of ``out`` are unspecified."""
+        of which only the lower tiles were written, added up in a fixed order.  Entries above the diagonal of ``out`` are not written: they
+        keep what they held."""
         if parts.dim() != 3 or out.dim() != 2 or parts.shape[1] != parts.shape[2] or tuple(out.shape) != tuple(parts.shape[1:]):
             raise ValueError("sum_lower takes (S, n, n) partial products and an (n, n) output")
         if parts.stride(-1) != 1 or out.stride(-1) != 1:
