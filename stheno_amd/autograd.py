@@ -28,7 +28,7 @@ import torch
 from . import ops
 from .matrix import LOG_2_PI, Chol, config
 
-__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals"]
+__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals", "sparse_posterior_marginals"]
 
 
 # Hyper-parameters travel through the autograd functions as one flat list of scalar tensors: the variances, then the scales and --
@@ -673,6 +673,206 @@ class _PosteriorMarginals(torch.autograd.Function):
         grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[1]) else None
         inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
         return (grad_r, grad_noise, None, None, *inputs, *grads)
+
+
+# ---------------------------------------------------------------------------------------------
+# Posterior marginals of a PSEUDO-POINT posterior (VFE / FITC / DTC; observations.py:255-336), f | PseudoObs(f(z), f(x, noise), y)
+# evaluated at test inputs xs, differentiable w.r.t. the kernel parameters, the noise, r = y - m(x), z, x and xs.
+#
+# D = diag(d) the effective noise (VFE / DTC: the noise; FITC: noise_i + k(x_i, x_i) - k_i^T K_z^{-1} k_i, k_i = k(z, x_i)),
+# Sigma = K_z + K_zx D^{-1} K_xz, a = Sigma^{-1} K_zx D^{-1} r, K_s = k(z, xs).  Outputs: mu_j = K_s[:, j]^T a (the mean minus m(xs))
+# and s_j = K_s[:, j]^T (K_z^{-1} - Sigma^{-1}) K_s[:, j] (k(xs_j, xs_j) minus the marginal variance).  With the cotangents gm of mu
+# and gs of s, P = K_z^{-1} K_s, Q = Sigma^{-1} K_s, e = Q gm, G_v = Q diag(gs) Q^T, G_m = -1/2 (e a^T + a e^T), G = G_v + G_m:
+#     dL/dK_s  = a gm^T + 2 (P - Q) diag(gs)                              (M x N*)
+#     dL/dK_z  = -P diag(gs) P^T + G                                       (M x M)
+#     dL/dK_zx = 2 G K_zx D^{-1} + e (D^{-1} r)^T                          (M x N: ONE MFMA GEMM, 2 M^2 N flops)
+#     dL/dd_i  = -[ k_i^T G k_i + (e^T k_i) r_i ] / d_i^2,       dL/dr_i = (e^T k_i) / d_i
+#     FITC, g_d = dL/dd:  dL/dk(x_i, x_i) += g_d_i,  dL/dK_zx -= 2 K_z^{-1} K_zx diag(g_d),  dL/dK_z += K_z^{-1} K_zx diag(g_d) K_xz K_z^{-1}
+# Each kernel-matrix cotangent is reduced by gpk_kmat_vjp_dense on its own pair of inputs -- (z, xs), (z, x), (z, z) -- the rank-one
+# parts in its w / b operands, the diagonal scalings in its colscale; k_i^T G k_i comes out of its column sums.  The jitter is a
+# constant: the plain path holds the mean's Sigma as L_z (A + eps I) L_z^T = Sigma + eps K_z and the variance's as Sigma + eps I
+# (`AbstractPseudoObservations.A`); Q is taken with the latter, e and a with the former, whose K_z share counts (1 + eps) times.
+# A loss of the mean only (gs = 0) has G = G_m of rank two: no M x N* solve, and (VFE / DTC) no GEMM either -- the cotangent of K_zx is
+# e ((r - K_xz a) / d)^T - a (K_xz e / d)^T, two rank-one passes.  Nothing of size M x N lives between forward and backward: K_zx (and
+# FITC's V, for d) is evaluated again in the backward.
+# ---------------------------------------------------------------------------------------------
+class _SparsePosteriorMarginals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, noise_vec, run, fitc, layout, *tensors):
+        """``run()`` -> ``(chol_z, chol_a, chol_post, w, vz, va, mu, s)``: the plain HIP path of the pseudo-point posterior
+        (``kernels._sparse_posterior_parts``) -- the factors of ``K_z``, of ``A + eps I`` (the mean's) and of ``A + eps L_z^{-1} L_z^{-T}``
+        (the variance's), ``w = L_z^{-1} (mu_z - m(z))`` (M, 1), ``vz = L_z^{-1} K_s``, ``va = L_post^{-1} vz`` (M, N*) and the outputs;
+        what a mean-only / variance-only call does not need is None.  ``layout`` / ``tensors``: ONE group, its inputs ``x`` (N, D), ``z``
+        (M, D) and ``xs`` (N*, D) as the fused kernels see them, then its parameters; ``r`` (N, 1), ``noise_vec`` (N,)."""
+        chol_z, chol_a, chol_post, w, vz, va, mu, s = run()
+        (ctx.group,) = _split_groups(layout, tensors, 3)
+        ctx.parts = (chol_z, chol_a, chol_post, w, vz, va)
+        ctx.r, ctx.noise, ctx.fitc = r.detach(), noise_vec.detach(), fitc
+        ctx.set_materialize_grads(False)
+        ref = mu if mu is not None else s
+        return (torch.zeros_like(ref) if mu is None else mu), (torch.zeros_like(ref) if s is None else s)
+
+    @staticmethod
+    def backward(ctx, g_mu, g_s):
+        be = ops.get_backend()
+        chol_z, chol_a, chol_post, w, vz, va = ctx.parts
+        grp, fitc = ctx.group, ctx.fitc
+        (x, z, xs), terms, kinds, nt = grp.inputs, grp.terms, grp.kinds, len(grp.kinds)
+        x, z, xs = x.detach(), z.detach(), xs.detach()
+        n, m, ns = x.shape[0], z.shape[0], xs.shape[0]
+        dt, dev = x.dtype, x.device
+        gm = g_mu.to(dt).contiguous() if (g_mu is not None and w is not None) else None
+        gs = g_s.to(dt).contiguous() if (g_s is not None and va is not None) else None
+        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
+            gs = None
+        need_r, need_noise, need_x, need_z, need_xs = (ctx.needs_input_grad[i] for i in (0, 1, 5, 6, 7))
+        if gm is None and gs is None:
+            return (None,) * (8 + len(grp.meta))
+        if need_x or need_z or need_xs:
+            check_input_dims(x)
+        eps = float(config.epsilon)
+        # (an ascent over xs alone -- an acquisition function on a fitted surrogate -- ends behind the k(z, xs) block: nothing of size N)
+        model = need_r or need_noise or need_x or need_z or any(ctx.needs_input_grad[8:])
+
+        def zeros(rows, cols):          # an all-zero operand read through a zero row stride (no rows x cols buffer)
+            return torch.zeros((1, cols), dtype=dt, device=dev).expand(rows, cols)
+
+        def outer(u, v):
+            return u[:, None] * v[None, :]
+
+        r = ctx.r[:, 0]
+        a = e = None
+        if gm is not None:
+            a = chol_z.solve_t(w)[:, 0]                                            # Sigma^{-1} K_zx D^{-1} r
+            t = chol_a.solve_t(chol_a.solve(be.gemv(vz, gm[:, None])))             # (A + eps I)^{-1} L_z^{-1} K_s gm
+            e = chol_z.solve_t(t)[:, 0]                                            # Sigma^{-1} K_s gm
+        pq = g_v = g_kz = None
+        if gs is not None:
+            # P = K_z^{-1} K_s and Q = Sigma^{-1} K_s: the M x N* back-substitutions (on private copies: the solves use them up)
+            pm = chol_z.solve_t_(be.copy(vz))
+            qm = chol_z.solve_t_(chol_post.solve_t_(be.copy(va)))
+            if model:
+                sc = be.scale_cols_(be.copy(qm), gs)
+                g_v = be.symmetrize_(be.gemm(sc, qm, a_kmajor=True, b_kmajor=True, lower_only=True))       # Q diag(gs) Q^T
+                sc.copy_(pm)
+                be.scale_cols_(sc, gs)
+                g_kz = be.symmetrize_(be.gemm(sc, pm, a_kmajor=True, b_kmajor=True, alpha=-1.0, lower_only=True))
+                del sc
+            pq = pm.sub_(qm)
+            del pm, qm
+        # through k(z, xs): cotangent a gm^T + 2 (P - Q) diag(gs)
+        cs = 2.0 * gs if gs is not None else None
+        if model:
+            S, _, gz = be.kmat_vjp_dense(terms, z, xs, pq if pq is not None else zeros(m, ns), colscale=cs, w=a, b=gm, want_gradx=need_z)
+        gxs = None
+        if need_xs:
+            if pq is not None:
+                be.scale_cols_(pq, cs)
+                g_t = pq.t().contiguous()                                          # (N*, M): 2 diag(gs) (P - Q)^T, explicit
+            else:
+                g_t = zeros(ns, m)
+            _, _, gxs = be.kmat_vjp_dense(terms, xs, z, g_t, w=gm, b=a, want_gradx=True)
+            del g_t
+        del pq
+        if not model:
+            return (None,) * 7 + (gxs,) + (None,) * len(grp.meta)
+        # the effective noise: FITC's takes V = L_z^{-1} K_zx once more
+        kzx = be.kmat(terms, z, x)
+        d, rr = ctx.noise, None
+        if fitc:
+            rr = chol_z.solve(kzx)
+            _, q = be.colreduce(rr, want_ss=True)
+            d = d + be.kdiag(terms, x) - q
+        ek = be.colreduce(kzx, e, want_dot=True, want_ss=False)[0] if gm is not None else None      # K_xz e
+        # through k(z, x): cotangent 2 G K_zx D^{-1} + e (D^{-1} r)^T
+        if gs is None and not fitc:
+            # G = G_m, of rank two: e ((r - K_xz a) / d)^T - a (K_xz e / d)^T, two rank-one passes and no M x N cotangent
+            ak = be.colreduce(kzx, a, want_dot=True, want_ss=False)[0]
+            del kzx
+            g_k, cs_k = None, None
+            ranks = [(e, (r - ak) / d), (a, -ek / d)]
+            g_d = -ek * (r - ak) / (d * d)
+            gz_k = None
+            for wv, bv in ranks:
+                s_k, _, gz_p = be.kmat_vjp_dense(terms, z, x, zeros(m, n), w=wv, b=bv, want_gradx=need_z)
+                S = S + s_k
+                if need_z:
+                    gz_k = gz_p if gz_k is None else gz_k + gz_p
+        else:
+            g_sig = g_v if g_v is not None else torch.zeros((m, m), dtype=dt, device=dev)
+            if gm is not None:
+                g_sig = g_sig - 0.5 * (outer(e, a) + outer(a, e))
+            g_k = be.gemm(g_sig, kzx, a_kmajor=True, b_kmajor=False, alpha=2.0)    # M x N, the one big GEMM
+            del kzx
+            cs_k = 1.0 / d
+            ranks = [(e, r / d)] if gm is not None else [(None, None)]
+            s_k, colsum, gz_k = be.kmat_vjp_dense(terms, z, x, g_k, colscale=cs_k, w=ranks[0][0], b=ranks[0][1], want_colsum=True,
+                                                  want_gradx=need_z and not fitc)
+            g_d = -(colsum * d + (ek * r if gm is not None else 0.0)) / (2.0 * d * d)
+            if fitc:
+                # the effective noise depends on K_zx and K_z through q_i = k_i^T K_z^{-1} k_i: the cotangent of K_zx gets
+                # -2 K_z^{-1} K_zx diag(g_d) and that of K_z  K_z^{-1} K_zx diag(g_d) K_xz K_z^{-1}
+                rr = chol_z.solve_t_(rr)                                           # K_z^{-1} K_zx   (M x N)
+                g_k.addcmul_(rr, (-2.0 * g_d * d)[None, :])
+                s_k, _, gz_k = be.kmat_vjp_dense(terms, z, x, g_k, colscale=cs_k, w=ranks[0][0], b=ranks[0][1], want_gradx=need_z)
+                sc = be.scale_cols_(be.copy(rr), g_d)
+                rgr = be.symmetrize_(be.gemm(sc, rr, a_kmajor=True, b_kmajor=True, lower_only=True))
+                g_kz = rgr if g_kz is None else g_kz + rgr
+                del sc, rr
+            S = S + s_k
+        gx = None
+        if need_x:
+            # d/dx through K_zx: the same reduction with the roles of the arguments swapped, on the explicit N x M transpose of the
+            # cotangent's full-rank part (one extra N x M buffer, backward only)
+            if g_k is not None:
+                be.scale_cols_(g_k, cs_k)
+                g_t = g_k.t().contiguous()
+            else:
+                g_t = zeros(n, m)
+            del g_k
+            for i, (wv, bv) in enumerate(ranks):
+                _, _, gx_p = be.kmat_vjp_dense(terms, x, z, g_t if i == 0 else zeros(n, m), w=bv, b=wv, want_gradx=True)
+                gx = gx_p if gx is None else gx + gx_p
+            del g_t
+        else:
+            del g_k
+        # through K_z: -P diag(gs) P^T + G  (the mean's share of G sits behind Sigma + eps K_z)
+        if g_kz is None:
+            g_kz = torch.zeros((m, m), dtype=dt, device=dev)
+        if g_v is not None:
+            g_kz = g_kz + g_v
+        if gm is not None:
+            g_kz = g_kz - (0.5 * (1.0 + eps)) * (outer(e, a) + outer(a, e))
+        s_kz, _, gz_kz = be.kmat_vjp_dense(terms, z, z, g_kz, want_gradx=need_z)
+        S = S + s_kz
+        variances, scales, _ = grp.values
+        gr = _param_grads(kinds, grp.values, S, [(S.device, S.dtype)] * len(grp.meta))
+        if fitc:
+            # through k(x_i, x_i) in the effective noise: stationary terms are their variance there, whatever their shape
+            for t in range(nt):
+                if kinds[t] == "linear":
+                    xx = ((x * x).sum(-1) * g_d).sum() / scales[t] ** 2
+                    gr[t], gr[nt + t] = gr[t] + xx, gr[nt + t] - 2.0 * variances[t] / scales[t] * xx
+                    if need_x:
+                        gx = gx + (2.0 * variances[t] / scales[t] ** 2) * g_d[:, None] * x
+                else:
+                    gr[t] = gr[t] + g_d.sum()
+        grads = [None if g_ is None else g_.to(device=dv, dtype=dty) for g_, (dv, dty) in zip(gr, grp.meta)]
+        grad_z = None
+        if need_z:
+            grad_z = gz + 2.0 * gz_kz + (gz_k if gz_k is not None else 0.0)
+        grad_r = (ek / d)[:, None] if (need_r and ek is not None) else None
+        grad_noise = g_d if need_noise else None
+        return (grad_r, grad_noise, None, None, None, gx, grad_z, gxs, *grads)
+
+
+def sparse_posterior_marginals(kernel, x, z, xs, r, noise_vec, method, run):
+    """Differentiable ``(mu, s)`` of ``_SparsePosteriorMarginals``: ``kernel`` a sum of primitives evaluated on ``x`` / ``z`` / ``xs``
+    (already behind its input map, so torch carries the map's parameter)."""
+    if method not in ("vfe", "fitc", "dtc"):
+        raise ValueError(f'Invalid approximation method "{method}".')
+    layout, params = _pack_groups([kernel])
+    return _SparsePosteriorMarginals.apply(r, noise_vec, run, method == "fitc", layout, x, z, xs, *params)
 
 
 def kdiag_terms(tensor_terms, x):

@@ -953,6 +953,10 @@ class Sum(Kernel):
         view = self.input_scaled_view()
         if view is not None:
             return _Mapped(*view).elwise(x, y, **kw)
+        if y is None and _sparse_pair(self) is not None:                 # a pseudo-point posterior under learnable quantities
+            got = _learnable_sparse_marginals(None, self, uprank(x), kw.get("cache"))
+            if got is not None:
+                return got[1]
         return self.a.elwise(x, y, **kw) + self.b.elwise(x, y, **kw)
 
     def __repr__(self):
@@ -1631,6 +1635,7 @@ class PosteriorKernel(Kernel):
         self.k_ij, self.k_zi, self.k_zj, self.z, self.K_z = k_ij, k_zi, k_zj, z, K_z
         self.own_cross = own_cross       # see _whiten
         self.exact = exact               # exact conditioning on observations of the process itself (see _learnable_marginals)
+        self.sparse = None               # weak (obs, measure) of a pseudo-point conditioning (see _learnable_sparse_marginals)
 
     def num_outputs(self, x):
         return self.k_ij.num_outputs(x)
@@ -1681,6 +1686,7 @@ class SubspaceKernel(Kernel):
 
     def __init__(self, k_zi, k_zj, z, A):
         self.k_zi, self.k_zj, self.z, self.A = k_zi, k_zj, z, A
+        self.sparse = None               # see PosteriorKernel
 
     def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None):
         x = uprank(x)
@@ -1713,6 +1719,7 @@ class PosteriorMean(Mean):
         self.m_i, self.m_z, self.k_zi, self.z, self.K_z, self.y = m_i, m_z, k_zi, z, K_z, y
         self.own_cross = own_cross       # see _whiten
         self.exact = exact               # see PosteriorKernel
+        self.sparse = None               # see PosteriorKernel
         self._w = None
         self._r = None
         self._r_detached = False         # the residual was formed under torch.no_grad() (cut off from a learnable mean / y)
@@ -1754,7 +1761,7 @@ class PosteriorMean(Mean):
 
     def __call__(self, x, cache=None):
         x = uprank(x)
-        got = _learnable_marginals(self, None, x, cache)
+        got = _learnable_marginals(self, None, x, cache) if self.sparse is None else _learnable_sparse_marginals(self, None, x, cache)
         if got is not None:
             return got[0]
         rhs = None
@@ -1801,7 +1808,7 @@ def _learnable_marginals(pm, pk, x, cache):
     """Posterior mean / marginal variances of an EXACT posterior of one process under learnable quantities, through
     ``autograd._PosteriorMarginals``: ``(mean column or None, marginal-variance column or None)`` for the posterior mean ``pm`` and /
     or the posterior kernel ``pk`` at the test inputs ``x``.  None when nothing learnable is behind them, when grad is off, or when the
-    call is outside that path (pseudo-point posteriors, several processes, chained conditioning, batched inputs, a kernel that is no
+    call is outside that path (pseudo-point posteriors: ``_learnable_sparse_marginals``; several processes, chained conditioning, batched inputs, a kernel that is no
     sum of primitives behind input maps, dense noise): the plain path then runs exactly as before."""
     if not torch.is_grad_enabled():
         return None
@@ -1857,6 +1864,106 @@ def _learnable_marginals(pm, pk, x, cache):
     return mean, vd
 
 
+def _sparse_pair(kernel):
+    """The link (weak references to ``(obs, measure)``) behind ``PosteriorKernel + SubspaceKernel`` of one pseudo-point conditioning
+    (``AbstractPseudoObservations.posterior_kernel``), else None."""
+    if isinstance(kernel, Sum) and isinstance(kernel.a, PosteriorKernel) and isinstance(kernel.b, SubspaceKernel):
+        link = getattr(kernel.a, "sparse", None)
+        if link is not None and getattr(kernel.b, "sparse", None) is link:
+            return link
+    return None
+
+
+def _sparse_posterior_parts(pm, pk, sk, k, z, x, cache, chol_a):
+    """The plain HIP path of the pseudo-point posterior marginals, unchanged (``PosteriorMean.__call__``, ``PosteriorKernel.elwise`` +
+    ``SubspaceKernel.elwise``): returns ``(chol_z, chol_a, chol_post, w, vz, va, mu, s)`` as ``autograd._SparsePosteriorMarginals``
+    takes them -- ``mu = vz^T w``, ``s = |vz_j|^2 - |va_j|^2``; what a mean-only (``pk`` None) or variance-only (``pm`` None) call does
+    not need is None."""
+    be = ops.get_backend()
+    K_z = (pm if pm is not None else pk).K_z
+    vz = _whiten(cache, K_z, k, z, x)
+    w = mu = va = s = chol_post = None
+    if pm is not None:
+        w = pm._whitened_residual()
+        mu = be.colreduce(vz, w, want_dot=True, want_ss=False)[0]
+    if pk is not None:
+        va = _whiten(cache, sk.A, k, z, x)
+        s = be.colreduce(vz, want_ss=True)[1] - be.colreduce(va, want_ss=True)[1]
+        chol_post = sk.A.chol().chols[1]
+    return K_z.chol(), chol_a, chol_post, w, vz, va, mu, s
+
+
+def _learnable_sparse_marginals(pm, kernel, x, cache):
+    """Posterior mean / marginal variances of a PSEUDO-POINT posterior (VFE / FITC / DTC) under learnable quantities, through
+    ``autograd._SparsePosteriorMarginals``: ``(mean column or None, marginal-variance column or None)`` for the posterior mean ``pm``
+    and / or the posterior kernel ``kernel`` (``PosteriorKernel + SubspaceKernel``) at the test inputs ``x``.  None when nothing
+    learnable is behind them, when grad is off, or when the call is outside the case the bound admits
+    (``AbstractPseudoObservations._differentiable``: noise-free inducing points of the observed process itself, one kernel that is a sum
+    of primitives behind one input map, diagonal noise, unbatched) at the inducing process: the plain path then runs as before."""
+    if not torch.is_grad_enabled():
+        return None
+    link = pm.sparse if pm is not None else _sparse_pair(kernel)
+    if link is None or (pm is not None and kernel is not None and _sparse_pair(kernel) is not link):
+        return None
+    obs, measure = link[0](), link[1]()
+    if obs is None or measure is None:
+        return None
+    from .matrix import Diagonal, Zero
+
+    p_x, xo, noise_x = obs.fdd.p, obs.fdd._xr, obs.fdd.noise
+    p_z, z, noise_z = obs.u.p, obs.u._xr, obs.u.noise
+    if isinstance(xo, MultiInput) or isinstance(z, MultiInput) or not isinstance(noise_x, Diagonal) or not isinstance(noise_z, Zero):
+        return None
+    k = measure.kernels[p_z]
+    view = k.input_scaled_view() if isinstance(k, Kernel) else None
+    if view is None or not _same_map(view[1], view[2]):
+        return None
+    if not (measure.kernels[p_x] is k and measure.kernels[p_z, p_x] is k):
+        return None
+    if not all(torch.is_tensor(t) and t.dim() == 2 and t.shape[-1] == z.shape[-1] and t.dtype == z.dtype and t.device == z.device
+               for t in (x, xo, z)):
+        return None
+    pk = sk = None
+    if kernel is not None:
+        pk, sk = kernel.a, kernel.b
+        if not (pk.k_ij is k and pk.k_zi is k and pk.k_zj is k and sk.k_zi is k and sk.k_zj is k and pk.z is z and sk.z is z):
+            return None
+    if pm is not None and not (pm.k_zi is k and pm.z is z and pm.m_i is measure.means[p_z] and (pk is None or pk.K_z is pm.K_z)):
+        return None
+    parts = obs._parts.get(measure)
+    if parts is None or parts["K_z"] is not (pm if pm is not None else pk).K_z or noise_x.diag().dim() != 1:
+        return None
+    kern, imap, _ = view                          # k(a, b) = kern(imap(a), imap(b))
+    if not kern.tensor_terms():
+        return None
+    from . import autograd as _ag
+
+    noise_vec = noise_x.diag()
+    learnable = _ag.kernel_requires_grad(k) or any(t.requires_grad for t in (x, xo, z, noise_vec, obs.y))
+    if not learnable and isinstance(measure.means[p_x], ZeroMean):
+        return None                               # (nothing learnable, and no mean that could hide a parameter: not even the residual)
+    r = obs.y - measure.means[p_x](xo)
+    if r.dim() != 2 or r.shape[-1] != 1 or not (learnable or r.requires_grad):
+        return None
+    xm, zm, xsm = (t if imap is None else imap(t) for t in (xo, z, x))
+    if xm.requires_grad or zm.requires_grad or xsm.requires_grad:
+        _ag.check_input_dims(xsm)
+    xd = x.detach()                  # (the plain path sees values only)
+    cache = {} if cache is None else cache        # (K_s is evaluated once for the two whitenings)
+
+    def run():
+        return _sparse_posterior_parts(pm, pk, sk, k, z, xd, cache, parts["chol_A"])
+
+    mu, s = _ag.sparse_posterior_marginals(kern, xm, zm, xsm, r, noise_vec, obs.method, run)
+    mean = pm.m_i(x) + mu[..., None] if pm is not None else None
+    vd = None
+    if pk is not None:
+        # the value of k(x, x) from the fused launch (the plain path's bits), its gradient from the same sum written in torch
+        kt = _ag.kdiag_terms(kern.tensor_terms(), xsm)
+        vd = (k.elwise(xd) + (kt - kt.detach())[..., None]) - s[..., None]
+    return mean, vd
+
+
 # ---------------------------------------------------------------------------
 # mean_var / mean_var_diag  (fdd.py:68-74)
 # ---------------------------------------------------------------------------
@@ -1891,6 +1998,10 @@ def mean_var_diag(mean, kernel, x):
     with deferred_checks():          # (see mean_var)
         if isinstance(mean, PosteriorMean) and isinstance(kernel, PosteriorKernel):
             got = _learnable_marginals(mean, kernel, x, cache)       # (under learnable quantities: ONE autograd node for both)
+            if got is not None:
+                return got
+        if isinstance(mean, PosteriorMean) and mean.sparse is not None and _sparse_pair(kernel) is mean.sparse:
+            got = _learnable_sparse_marginals(mean, kernel, x, cache)
             if got is not None:
                 return got
         m = _call_mean(mean, x, cache)

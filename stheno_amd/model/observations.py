@@ -200,6 +200,7 @@ class AbstractPseudoObservations(AbstractObservations):
             u = combine(*u)
         self.u = u
         self._K_z, self._elbo, self._mu, self._A, self._parts = (weakref.WeakKeyDictionary() for _ in range(5))
+        self._links = weakref.WeakKeyDictionary()
 
     def K_z(self, measure):
         if measure not in self._K_z:
@@ -318,16 +319,29 @@ class AbstractPseudoObservations(AbstractObservations):
 
     def posterior_kernel(self, measure, p_i, p_j):
         z = self.u._xr
-        return _k.PosteriorKernel(
+        pk = _k.PosteriorKernel(
             measure.kernels[p_i, p_j], measure.kernels[self.u.p, p_i], measure.kernels[self.u.p, p_j], z,
             self.K_z(measure),
-        ) + _k.SubspaceKernel(measure.kernels[self.u.p, p_i], measure.kernels[self.u.p, p_j], z, self.A(measure))
+        )
+        sk = _k.SubspaceKernel(measure.kernels[self.u.p, p_i], measure.kernels[self.u.p, p_j], z, self.A(measure))
+        pk.sparse = sk.sparse = self._link(measure)      # (the marginals' differentiable path: kernels._learnable_sparse_marginals)
+        return pk + sk
 
     def posterior_mean(self, measure, p):
-        return _k.PosteriorMean(
+        pm = _k.PosteriorMean(
             measure.means[p], measure.means[self.u.p], measure.kernels[self.u.p, p], self.u._xr,
             self.K_z(measure), self.mu(measure),
         )
+        pm.sparse = self._link(measure)
+        return pm
+
+    def _link(self, measure):
+        """``(self, measure)`` as weak references, ONE object per measure: the posterior mean and the two posterior kernels of one
+        conditioning find each other by its identity (weak: the posterior measure's rules keep both alive, and no cycle keeps the
+        factors alive behind them)."""
+        if measure not in self._links:
+            self._links[measure] = (weakref.ref(self), weakref.ref(measure))
+        return self._links[measure]
 
     def _compute(self, measure, reduce=None):
         """``observations.py:279-336``.  Heavy steps: ``K_zx`` (kmat), ``chol(K_z)`` (potrf),
