@@ -60,7 +60,7 @@ extern "C" {
 #define GPK_DIAG_BLOCK 128 /* order of the diagonal blocks whose inverses gpk_potrf leaves in `dinv` */
 
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
- * 105: gpk_kmat_diff. */
+ * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -419,6 +419,45 @@ int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, con
                        const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream);
+
+/* VJP of a derivative block: `g` (n x m, ldg, unit inner stride) is the explicit cotangent of the block gpk_kmat_diff writes for the
+ * same (dim_x, dim_y) -- gradients of a posterior through the covariance of a process with its derivative and of two derivatives.
+ * The block is never formed.  Grid, partial rows and their summation as for gpk_kmat_vjp_dense (rowtiles x nchunks workgroups from
+ * gpk_kmat_vjp_dense_grid, rows of NS * GPK_MAX_TERMS + 1 elements, NS = 3 exactly when a term is GPK_K_RQ, the trace slot 0);
+ * deterministic (no atomics), `g` is read once and nothing outside its n x m view; any d (input dimensions in chunks of 8).
+ *   A block element is sum_t v_t beta_t.  Stationary term, c = inv_ls^2, q = c |x - y|^2, D_a = x[a] - y[a], kappa', kappa'' as above:
+ *     d/dx_a         beta = 2 c kappa' D_a                                   c dbeta/dc = 2 c D_a (kappa' + q kappa'')
+ *     d/dy_b         the same with -D_b
+ *     d^2/dx_a dy_b  beta = -4 c^2 kappa'' D_a D_b - 2 c kappa' [a == b]
+ *                    c dbeta/dc = -4 c^2 D_a D_b (2 kappa'' + q kappa''') - 2 c [a == b] (kappa' + q kappa'')
+ *     GPK_K_EQ        q kappa''' = -q kappa / 8
+ *     GPK_K_RQ        q kappa''' = -(alpha + 1)(alpha + 2) / (8 alpha^2) q (1 + u)^(-alpha - 3)
+ *     GPK_K_MATERN52  q kappa''' = -(25/24) s e^(-s)
+ *     GPK_K_MATERN32  q kappa''' = -(9/8) (1 + s) / s e^(-s),  so  2 kappa'' + q kappa''' = (9/8) (3 - s) / s e^(-s)
+ *   GPK_K_LINEAR: beta = c y[a] | c x[b] | c [a == b] and c dbeta/dc = beta;  GPK_K_CONST: 0.
+ *     row[NS t]     = S1_t = sum g beta_t                    d/d variance_t = S1_t
+ *     row[NS t + 1] = S2_t = sum g c dbeta_t/dc              d/d scale_t = -2 v_t S2_t / l_t
+ *     row[NS t + 2] = S3_t = sum g dbeta_t/dalpha_t          d/d alpha_t = v_t S3_t      (GPK_K_RQ only; 0 for every other kind)
+ *   RQ's shape derivative, P_k = (1 + u)^(-alpha - k):  dP_k/dalpha = P_k ((alpha + k) u / (alpha (1 + u)) - log1p(u)),
+ *   kappa' = -P_1 / 2, kappa'' = (alpha + 1) / (4 alpha) P_2; every exponent stays <= 0.  Matern32's 1 / s is taken as 0 where s is not
+ *   positive, as in gpk_kmat_diff: coincident points add exactly 0 to its sums in both dtypes.
+ *   gradx (nullable): [nchunks][n][d], the gradient with respect to the row input, summed over chunks by the caller; the two one-sided
+ *   modes and d <= 8 only:
+ *     d/dx_a:  dbeta/dx_e = 4 c^2 kappa'' D_a D_e + 2 c kappa' [e == a];     d/dy_b: -(4 c^2 kappa'' D_b D_e + 2 c kappa' [e == b]);
+ *     GPK_K_LINEAR: 0 for d/dx_a, c [e == b] for d/dy_b.  (The mixed block's input gradient needs kappa''' alone, which Matern32 does
+ *     not have at coincident points: not provided.)
+ *   Numerics: element by element within 1.2 eps (the sums) / 3.5 eps (gradx) of the sum of the absolute values of everything added
+ *   up for an output, in both dtypes (measured on an MI355X against an 80-bit reference: tests/diff_vjp_reference.py,
+ *   tests/test_diff_vjp_gpu.py, profiles/README.md "Derivative-block gradient kernel, element by element").
+ *   Every argument is checked before an empty problem (n or m <= 0) returns 0.  Returns -k for argument k:
+ *     -6  nterms outside 0 .. GPK_MAX_TERMS;      -2  GPK_K_MATERN12, GPK_K_DELTA or an unknown kind;
+ *     `shapes` as for gpk_kmat_diff: -1 for a GPK_K_RQ term with shapes == NULL, -5 for an alpha <= 0;
+ *     -15 d < 0;      -7  dim_x outside [-1, d), or dim_x and dim_y both -1;      -8  dim_y outside [-1, d);
+ *     -10 / -13  n / m too large (more than 2^31 - 1, or more than 65535 column chunks);
+ *     -19 gradx != NULL in the mixed mode or with d > 8. */
+int gpk_kmat_diff_vjp(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                      int dim_x, int dim_y, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
+                      const void* g, int64_t ldg, void* partial, void* gradx, void* stream);
 
 /* Measurement hooks (bench.py's live roofline figure).  Between gpk_prof_start and
  * gpk_prof_stop every MFMA GEMM launch of this process is bracketed by HIP events on its

@@ -119,6 +119,11 @@ SIGNATURES = {
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr,
          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr],
     ),
+    "gpk_kmat_diff_vjp": (
+        _c_int,
+        [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_int, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int,
+         _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr],
+    ),
     "gpk_gemm_colss_rows": (_c_i64, [_c_i64]),
     "gpk_gemm_colscale": (
         _c_int,

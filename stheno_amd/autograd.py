@@ -19,6 +19,13 @@ k_g(u_g(x), u_g(y))`` with ``k_g`` a sum of primitives and ``u_g`` a differentia
 per-dimension length scales, the periodic embedding), formed in torch by the caller.  The cotangent of ``K`` is the same for every group;
 the reductions against it run once per group, on that group's term table and mapped inputs, and each group's input gradient goes back to
 torch, which carries it through the map to its parameter and to ``x``.  One group is the plain case: the same launches as ever.
+
+The posterior marginals (``post(xs).mean`` / ``.var_diag`` / ``.marginals()`` / ``.marginal_credible_bounds()``) have three functions
+further down: ``_PosteriorMarginals`` (an exact posterior of one process predicted from its own observations), ``_BlockPosteriorMarginals``
+(one exact conditioning step ACROSS processes: a component of a sum, several observed processes, derivatives -- the blocks are sums of
+groups ``s D^(a, b) k_g(u_g(x), u_g(y))``, ``kernels._block_groups``, and a derivative group's cotangent is reduced by
+``gpk_kmat_diff_vjp``) and ``_SparsePosteriorMarginals`` (pseudo-point posteriors).  Each runs the plain path as its forward, so the
+values are that path's bits, and derives everything else from the stored factors.
 """
 import collections
 import math
@@ -28,7 +35,7 @@ import torch
 from . import ops
 from .matrix import LOG_2_PI, Chol, config
 
-__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals", "sparse_posterior_marginals"]
+__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals", "block_posterior_marginals", "sparse_posterior_marginals"]
 
 
 # Hyper-parameters travel through the autograd functions as one flat list of scalar tensors: the variances, then the scales and --
@@ -673,6 +680,132 @@ class _PosteriorMarginals(torch.autograd.Function):
         grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[1]) else None
         inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
         return (grad_r, grad_noise, None, None, *inputs, *grads)
+
+
+# ---------------------------------------------------------------------------------------------
+# Posterior marginals ACROSS processes: one exact conditioning step on one or several observation sets, any one process p of the
+# measure predicted at xs -- a component of a sum, another observed process, a derivative (`post(f.diff())`), or values predicted from
+# observed slopes.  K is the block matrix of the observed processes (MultiOutputKernel), C = K(x_obs, xs) the stacked cross-covariances
+# with p; every block is a sum of groups s D^(a, b) k_g(u_g(x), u_g(y)) (kernels._block_groups), (a, b) the derivative slots of a
+# DiffKernel, both None for a plain group.  Forward: the plain path, as it is.  Backward, from the stored factor and V = L^{-1} C, with
+# B = L^{-T} V, alpha = K^{-1} r, beta = B gm (the same algebra as above):
+#     dL/dC = alpha gm^T + 2 B diag(gs)                                   (N x N*, explicit)
+#     dL/dK = -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T)         (N x N, explicit and symmetric; its diagonal: d/dnoise)
+#     dL/dr = beta
+# -- one gpk_trsm_lower_t and one N x N x N* GEMM (the rank-one and rank-two parts are GEMMs of contraction length 1 and 2) -- and then
+# one reduction per group and block over the block's view of either cotangent: gpk_kmat_vjp_dense for a plain group, gpk_kmat_diff_vjp
+# for a derivative group; off-diagonal blocks of dL/dK count twice.  A mapped input that requires a gradient (the test inputs, a
+# learnable period, ...) gets it from the pass where it is the row input and from one more pass over the transposed view, with the
+# derivative slots exchanged, where it is the column input.  The one-sided derivative blocks have an input gradient (d <= 8), the mixed
+# block has none: the caller refuses that before anything is launched.
+# ---------------------------------------------------------------------------------------------
+class _BlockPosteriorMarginals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, noise_vec, run, sizes, layout, nu, *tensors):
+        """``run()`` -> ``(chol, w, v, mu, s)`` as for ``_PosteriorMarginals``; ``sizes``: the rows of each observation set; ``layout``
+        = ``[(which, i, j, kinds, number of parameters, ua, ub, a, b)]``, one entry per group: ``which`` = ``"K"`` for block ``(i, j)``
+        of the lower block triangle of the observed covariance, ``"C"`` for the rows of set ``i`` of the cross-covariance; ``ua`` /
+        ``ub`` the positions of the group's row / column inputs among the ``nu`` mapped inputs that lead ``tensors``, ``(a, b)`` its
+        derivative slots; behind the inputs the groups' parameters (``_pack``; the group's factor is in the variances)."""
+        chol, w, v, mu, s = run()
+        params = tensors[nu:]
+        ctx.chol, ctx.w, ctx.v, ctx.sizes, ctx.layout, ctx.us = chol, w, v, sizes, layout, tensors[:nu]
+        ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
+        ctx.param_meta = [(p.device, p.dtype) for p in params]
+        ctx.values = [float(p) for p in params]
+        ctx.set_materialize_grads(False)
+        if mu is None:
+            mu = torch.zeros_like(s)
+        return mu, s
+
+    @staticmethod
+    def backward(ctx, g_mu, g_s):
+        be = ops.get_backend()
+        chol, v, us = ctx.chol, ctx.v, ctx.us
+        nu = len(us)
+        nothing = (None,) * (6 + nu + len(ctx.values))
+        dt, dev = us[0].dtype, us[0].device
+        gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
+        gs = g_s.to(dt).contiguous() if g_s is not None else None
+        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
+            gs = None
+        if gm is None and gs is None:
+            return nothing
+        need_u = [ctx.needs_input_grad[6 + a] for a in range(nu)]
+        transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
+        alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
+        bm = beta = None
+        if gs is not None:
+            bm = chol.solve_t_(v.plain() if transposed else be.copy(v))      # B = L^{-T} V (a private copy: the solve uses it up)
+            if gm is not None:
+                beta = be.gemv(bm, gm[:, None])[:, 0]
+        else:
+            vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[:, None])[:, 0]
+            beta = chol.solve_t(vg[:, None])[:, 0]
+        n = sum(ctx.sizes)
+        ns = gm.shape[0] if gm is not None else gs.shape[0]
+        # the two cotangents, explicit
+        if bm is not None:
+            cbar = be.copy(bm)
+            be.scale_cols_(cbar, 2.0 * gs)
+            bs = be.copy(bm)
+            be.scale_cols_(bs, gs)
+            kbar = be.gemm(bs, bm, a_kmajor=True, b_kmajor=True, alpha=-1.0)
+            del bs, bm
+        else:
+            cbar = torch.zeros((n, ns), dtype=dt, device=dev)
+            kbar = torch.zeros((n, n), dtype=dt, device=dev)
+        if gm is not None:
+            be.gemm(alpha[:, None].contiguous(), gm[:, None].contiguous(), a_kmajor=True, b_kmajor=True, alpha=1.0, beta=1.0, out=cbar)
+            be.gemm(torch.stack([beta, alpha], dim=1), torch.stack([alpha, beta], dim=1), a_kmajor=True, b_kmajor=True, alpha=-0.5,
+                    beta=1.0, out=kbar)
+        offs = [0]
+        for rows in ctx.sizes:
+            offs.append(offs[-1] + rows)
+        cbar_t = None
+        grads, grad_us, pos = [None] * len(ctx.values), [None] * nu, 0
+
+        def add(a, gx):
+            grad_us[a] = gx if grad_us[a] is None else grad_us[a] + gx
+
+        def reduce(terms, x, y, a, b, g, want_gx):
+            if a is None and b is None:
+                S, _, gx = be.kmat_vjp_dense(terms, x, y, g, want_gradx=want_gx)
+                return S, gx
+            return be.kmat_diff_vjp(terms, x, y, a, b, g, want_gradx=want_gx)
+
+        for (which, i, j, kinds, npar, ua, ub, a, b) in ctx.layout:
+            terms, values = _unpack(kinds, ctx.values[pos: pos + npar])
+            if which == "K":
+                g = kbar[offs[i]: offs[i + 1], offs[j]: offs[j + 1]]
+                wgt = 1.0 if i == j else 2.0
+            else:
+                g = cbar[offs[i]: offs[i + 1], :]
+                wgt = 1.0
+            S, gx = reduce(terms, us[ua], us[ub], a, b, g, need_u[ua])
+            grads[pos: pos + npar] = _param_grads(kinds, values, S, ctx.param_meta[pos: pos + npar], wgt)
+            pos += npar
+            symmetric = which == "K" and i == j and ua == ub and a == b
+            if need_u[ua]:
+                add(ua, (2.0 if symmetric else wgt) * gx)
+            if need_u[ub] and not symmetric:
+                # the input is the column one: the transposed view (dL/dK is symmetric, explicitly), the derivative slots exchanged
+                if which == "K":
+                    gt = kbar[offs[j]: offs[j + 1], offs[i]: offs[i + 1]]
+                else:
+                    if cbar_t is None:
+                        cbar_t = cbar.t().contiguous()
+                    gt = cbar_t[:, offs[i]: offs[i + 1]]
+                _, gx = reduce(terms, us[ub], us[ua], b, a, gt, True)
+                add(ub, wgt * gx)
+        grad_r = beta[:, None] if (beta is not None and ctx.has_r and ctx.needs_input_grad[0]) else None
+        grad_noise = torch.diagonal(kbar).clone() if (ctx.has_noise and ctx.needs_input_grad[1]) else None
+        return (grad_r, grad_noise, None, None, None, None, *grad_us, *grads)
+
+
+def block_posterior_marginals(r, noise_vec, run, sizes, layout, us, params):
+    """Differentiable ``(mu, s)`` of ``_BlockPosteriorMarginals`` (``kernels._learnable_block_marginals`` builds the arguments)."""
+    return _BlockPosteriorMarginals.apply(r, noise_vec, run, sizes, layout, len(us), *us, *params)
 
 
 # ---------------------------------------------------------------------------------------------

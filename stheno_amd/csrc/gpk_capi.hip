@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 105; }
+int gpk_version(void) { return 106; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -273,6 +273,13 @@ int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, con
     D1(dtype, gpk_kmat_vjp_dense_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, (const T*)y, m,
                                            ldy, d, (const T*)g, ldg, (const T*)colscale, (const T*)w,
                                            (const T*)b, (T*)partial, (T*)colsum, (T*)gradx, (hipStream_t)stream));
+}
+
+int gpk_kmat_diff_vjp(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                      int dim_x, int dim_y, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
+                      const void* g, int64_t ldg, void* partial, void* gradx, void* stream) {
+    D1(dtype, gpk_kmat_diff_vjp_launch<T>(kinds, variances, inv_ls, shapes, nterms, dim_x, dim_y, (const T*)x, n, ldx, (const T*)y, m,
+                                          ldy, d, (const T*)g, ldg, (T*)partial, (T*)gradx, (hipStream_t)stream));
 }
 
 }  // extern "C"

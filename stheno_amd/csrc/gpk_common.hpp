@@ -299,6 +299,12 @@ int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const d
                               const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
                               const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
                               T* colsum, T* gradx, hipStream_t stream);
+// VJP of a derivative block (gpk_kmat_diff_vjp in gpk.h; gpk_vjp.hip): the grid and partial rows of gpk_kmat_vjp_dense_launch; status
+// codes are that entry's argument positions
+template <typename T>
+int gpk_kmat_diff_vjp_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                             int dim_x, int dim_y, const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                             const T* G, int64_t ldg, T* partial, T* gradx, hipStream_t stream);
 template <typename T>
 int gpk_trtri_launch(const T* L, int64_t n, int64_t ld, const T* dinv_sb, int sb, T* W, int64_t ldw, T* tmp,
                      hipStream_t stream);

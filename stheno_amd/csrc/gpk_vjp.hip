@@ -551,6 +551,363 @@ template int gpk_kmat_vjp_dense_launch<float>(const int*, const double*, const d
                                               const float*, const float*, const float*, float*, float*, float*,
                                               hipStream_t);
 
+// ---------------------------------------------------------------------------------------------
+// VJP of a DERIVATIVE block (gpk_kmat_diff_vjp in gpk.h): the explicit cotangent g (n x m) of the block gpk_kmat_diff writes for the
+// same (dim_x, dim_y) -- never formed here -- reduced to the per-term sums of the block's derivatives with respect to the variances,
+// the scales and RQ's alpha, and (one-sided modes, d <= 8) to the gradient with respect to the row input.  The walk of
+// kmat_vjp_dense_kernel: a workgroup owns a 64-row tile and a chunk of 64-column tiles, 4 x 4 elements per thread, the input
+// dimensions staged in chunks of 8; the selected coordinates x[a], x[b] / y[a], y[b] are fetched beside the chunks.  With
+// q = c r^2, D_a = x[a] - y[a], a block element is sum_t v_t beta_t:
+//   d/dx_a:          beta = 2 c kappa' D_a                      c dbeta/dc = 2 c D_a (kappa' + q kappa'')
+//   d/dy_b:          the same with -D_b
+//   d2/dx_a dy_b:    beta = -4 c^2 kappa'' D_a D_b - 2 c kappa' [a == b]
+//                    c dbeta/dc = -4 c^2 D_a D_b (2 kappa'' + q kappa''') - 2 c [a == b] (kappa' + q kappa'')
+// and d beta / d alpha the same expressions on d kappa' / d alpha, d kappa'' / d alpha (RQ).  Linear: beta = c y[a] | c x[b] | c [a == b]
+// and c dbeta/dc = beta; Const: nothing.  The mode, "some term is RQ" and "gradx is wanted" are template parameters: a one-sided launch
+// without gradx never evaluates kappa'', a table without RQ never the logarithm.  gradx is summed in LDS by each row's owner thread, not
+// in 32 more registers per thread: with eight terms x three sums in fp64 those spilled 200 to 340 bytes per lane to scratch memory in
+// every fp64 gradx instantiation; this way one of them (RQ table, d/dy) is left with 32 bytes, the others with none.  The term table
+// is walked term by term, as in kmat_vjp_dense_kernel: with the elements outermost the unrolled body of the RQ instantiations is past
+// the compiler's size limit, the loop over this thread's rows stays rolled and its register arrays are indexed dynamically.
+namespace {
+
+enum { DMODE_DX = 0, DMODE_DY = 1, DMODE_DXY = 2 };
+
+template <typename T>
+struct VjpDiffArgs {
+    const T *X, *Y, *G;
+    T *partial, *gradx;
+    int64_t ldx, ldy, ldg;
+    int n, m, d, nterms, tiles_per_chunk, ctiles, nchunks;
+    int dim_x, dim_y;
+    int kind[GPK_MAX_TERMS];
+    T ils2[GPK_MAX_TERMS], var[GPK_MAX_TERMS];
+    T shape[GPK_MAX_TERMS];    // (SH only) RQ's alpha
+};
+
+// The profile of a stationary kind at q: k1 = kappa', k2 = kappa'', qk2 = q kappa'', m3 = 2 kappa'' + q kappa''' and (RQ) the
+// derivatives of kappa' and kappa'' with respect to alpha.
+//   eq         kappa''' = -kappa / 8
+//   matern52   q kappa''' = -(25/24) s e^(-s)
+//   matern32   q kappa'' = (3/4) s e^(-s),  2 kappa'' + q kappa''' = (9/8) (3 - s) / s e^(-s);  1 / s is taken as 0 where s is not
+//              positive, as the forward kernel does (whatever multiplies it tends to 0 with the distance)
+//   rq         P_k = (1 + u)^(-alpha - k) from exp(-(alpha + 1) log1p(u)) and 1 / (1 + u): every exponent <= 0;
+//              q kappa''' = -kappa'' q (alpha + 2) / (2 alpha (1 + u)),  dP_k / dalpha = P_k ((alpha + k) u / (alpha (1 + u)) - log1p(u))
+template <typename T, bool SH>
+__device__ __forceinline__ void diff_profile(int kind, T q, T al, T& k1, T& k2, T& qk2, T& m3, T& k1a, T& k2a) {
+    k1a = k2a = T(0);
+    if (kind == GPK_K_EQ) {
+        const T e = vexp<T>(T(-0.5) * q);
+        k1 = T(-0.5) * e;
+        k2 = T(0.25) * e;
+        qk2 = q * k2;
+        m3 = e * (T(0.5) - T(0.125) * q);
+    } else if (kind == GPK_K_MATERN32) {
+        const T s = vsqrt<T>(T(3) * q), e = vexp<T>(-s);
+        const T is = s > T(0) ? T(1) / s : T(0);
+        k1 = T(-1.5) * e;
+        k2 = T(2.25) * e * is;
+        qk2 = T(0.75) * s * e;
+        m3 = T(1.125) * (T(3) - s) * e * is;
+    } else if (kind == GPK_K_MATERN52) {
+        const T s = vsqrt<T>(T(5) * q), e = vexp<T>(-s);
+        k1 = T(-5.0 / 6.0) * (T(1) + s) * e;
+        k2 = T(25.0 / 12.0) * e;
+        qk2 = T(5.0 / 12.0) * s * s * e;
+        m3 = e * (T(25.0 / 6.0) - T(25.0 / 24.0) * s);
+    } else if (SH && kind == GPK_K_RQ) {
+        const T h = T(0.5) / al, u = q * h;
+        const T lg = vlog1p<T>(u), ri = T(1) / (T(1) + u);
+        const T p1 = vexp<T>(-(al + T(1)) * lg), p2 = p1 * ri;
+        const T w = T(2) * h * u * ri;                 // u / (alpha (1 + u))
+        k1 = T(-0.5) * p1;
+        k2 = (al + T(1)) * T(0.5) * h * p2;            // (alpha + 1) / (4 alpha) P_2
+        qk2 = q * k2;
+        m3 = k2 * (T(2) - q * ri * (al + T(2)) * h);
+        k1a = T(-0.5) * p1 * ((al + T(1)) * w - lg);
+        k2a = (al + T(1)) * T(0.5) * h * p2 * ((al + T(2)) * w - lg) - h * h * p2;
+    } else {
+        k1 = k2 = qk2 = m3 = T(0);
+    }
+}
+
+template <typename T, int MODE, bool SH, bool GX>
+__global__ __launch_bounds__(256) void kmat_diff_vjp_kernel(VjpDiffArgs<T> p) {
+    constexpr int NS = SH ? 3 : 2;      // sums per term
+    __shared__ T xi[DT * VDC], yj[DT * VDC];
+    __shared__ T red[4 * NS * GPK_MAX_TERMS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ty = tid >> 4, tx = tid & 15;     // 16 x 16 threads, 4 x 4 elements each
+    const int rt = blockIdx.x, chunk = blockIdx.y;
+    const int i0 = rt * DT;
+    const bool same = p.dim_x == p.dim_y;
+    const int sel = MODE == DMODE_DY ? p.dim_y : p.dim_x;      // (GX: the one-sided modes) the differentiated dimension
+
+    T s1[GPK_MAX_TERMS], s2[GPK_MAX_TERMS], s3[SH ? GPK_MAX_TERMS : 1];
+#pragma unroll
+    for (int t = 0; t < GPK_MAX_TERMS; ++t) s1[t] = s2[t] = T(0);
+    if (SH) {
+#pragma unroll
+        for (int t = 0; t < GPK_MAX_TERMS; ++t) s3[SH ? t : 0] = T(0);
+    }
+    // (GX) d/dX of the tile's rows over this workgroup's chunk.  Row r belongs to the thread tx == 0 of its row group alone (it zeroes,
+    // adds to and writes out its own 4 x VDC entries: no barrier), so no thread carries 32 more accumulators through the term table.
+    __shared__ T gxs[GX ? DT * VDC : 1];
+    if (GX && tx == 0) {
+#pragma unroll
+        for (int k = 0; k < 4 * VDC; ++k) gxs[GX ? ty * 4 * VDC + k : 0] = T(0);
+    }
+    T xa[4], xb[4];      // x[row][dim_x], x[row][dim_y] of this thread's rows
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int i = i0 + ty * 4 + u;
+        xa[u] = (MODE != DMODE_DY && i < p.n) ? p.X[(int64_t)i * p.ldx + p.dim_x] : T(0);
+        xb[u] = (MODE != DMODE_DX && i < p.n) ? p.X[(int64_t)i * p.ldx + p.dim_y] : T(0);
+    }
+
+    const int ct_end = min((chunk + 1) * p.tiles_per_chunk, p.ctiles);
+    for (int ct = chunk * p.tiles_per_chunk; ct < ct_end; ++ct) {
+        const int j0 = ct * DT;
+        T ya[4], yb[4];      // y[col][dim_x], y[col][dim_y] of this thread's columns
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int j = j0 + tx * 4 + v;
+            ya[v] = (MODE != DMODE_DY && j < p.m) ? p.Y[(int64_t)j * p.ldy + p.dim_x] : T(0);
+            yb[v] = (MODE != DMODE_DX && j < p.m) ? p.Y[(int64_t)j * p.ldy + p.dim_y] : T(0);
+        }
+        T r2[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) r2[a][b] = T(0);
+        for (int dc = 0; dc < p.d; dc += VDC) {
+            __syncthreads();
+            for (int idx = tid; idx < DT * VDC; idx += 256) {
+                const int r = idx / VDC, c = idx % VDC;
+                xi[idx] = (i0 + r < p.n && dc + c < p.d) ? p.X[(int64_t)(i0 + r) * p.ldx + dc + c] : T(0);
+                yj[idx] = (j0 + r < p.m && dc + c < p.d) ? p.Y[(int64_t)(j0 + r) * p.ldy + dc + c] : T(0);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < VDC; ++c) {
+                T a[4], b[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    a[q] = xi[(ty * 4 + q) * VDC + c];
+                    b[q] = yj[(tx * 4 + q) * VDC + c];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const T df = a[u] - b[v];
+                        r2[u][v] += df * df;
+                    }
+            }
+        }
+        // the cotangent of this thread's 4 x 4 elements (nothing outside the n x m view is read)
+        T Ge[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + ty * 4 + u;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int j = j0 + tx * 4 + v;
+                Ge[u][v] = (i < p.n && j < p.m) ? p.G[(int64_t)i * p.ldg + j] : T(0);
+            }
+        }
+        // term by term (the kind is uniform: one branch per term and tile); (GX) d block / dx_e = cD (x_e - y_e) + cS [e == sel],
+        // cD and cS summed over the terms
+        T cD[GX ? 4 : 1][GX ? 4 : 1], cS[GX ? 4 : 1][GX ? 4 : 1];
+        if (GX) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) cD[GX ? u : 0][GX ? v : 0] = cS[GX ? u : 0][GX ? v : 0] = T(0);
+        }
+#pragma unroll
+        for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+            if (t < p.nterms) {
+                const int kind = p.kind[t];
+                const T c = p.ils2[t], var = p.var[t];
+                const T al = SH ? p.shape[t] : T(1);
+                if (kind == GPK_K_LINEAR) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            const T be = MODE == DMODE_DX ? c * ya[v] : MODE == DMODE_DY ? c * xb[u] : (same ? c : T(0));
+                            s1[t] += Ge[u][v] * be;
+                            s2[t] += Ge[u][v] * be;
+                            if (GX && MODE == DMODE_DY) cS[GX ? u : 0][GX ? v : 0] += var * c;
+                        }
+                } else if (kind != GPK_K_CONST) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            T k1, k2, qk2, m3, k1a, k2a;
+                            diff_profile<T, SH>(kind, r2[u][v] * c, al, k1, k2, qk2, m3, k1a, k2a);
+                            T be, bc, ba;
+                            if (MODE == DMODE_DXY) {
+                                const T f = T(-4) * c * c * ((xa[u] - ya[v]) * (xb[u] - yb[v]));
+                                const T h = same ? T(-2) * c : T(0);
+                                be = f * k2 + h * k1;
+                                bc = f * m3 + h * (k1 + qk2);
+                                ba = f * k2a + h * k1a;
+                            } else {
+                                const T sd = MODE == DMODE_DX ? xa[u] - ya[v] : yb[v] - xb[u];      // D_a, or -D_b
+                                const T f = T(2) * c * sd;
+                                be = f * k1;
+                                bc = f * (k1 + qk2);
+                                ba = f * k1a;
+                                if (GX) {
+                                    cD[GX ? u : 0][GX ? v : 0] += var * (T(2) * c) * f * k2;
+                                    cS[GX ? u : 0][GX ? v : 0] += (MODE == DMODE_DX ? T(2) : T(-2)) * var * c * k1;
+                                }
+                            }
+                            s1[t] += Ge[u][v] * be;
+                            s2[t] += Ge[u][v] * bc;
+                            if (SH) s3[SH ? t : 0] += Ge[u][v] * ba;
+                        }
+                }
+            }
+        }
+        // d/dx_i[e] += (sum_j Ge cD) x_i[e] - sum_j Ge cD y_j[e] + [e == sel] sum_j Ge cS   (xi / yj still hold the only d-chunk): this
+        // row's share of the tile over the 16 tx lanes of the row group, then into the owner's entries
+        if (GX) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                T sumD = T(0), sumS = T(0);
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    cD[GX ? u : 0][GX ? v : 0] *= Ge[u][v];
+                    sumD += cD[GX ? u : 0][GX ? v : 0];
+                    sumS += cS[GX ? u : 0][GX ? v : 0] * Ge[u][v];
+                }
+#pragma unroll
+                for (int c = 0; c < VDC; ++c) {
+                    T a = sumD * xi[(ty * 4 + u) * VDC + c] + (c == sel ? sumS : T(0));
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) a -= cD[GX ? u : 0][GX ? v : 0] * yj[(tx * 4 + v) * VDC + c];
+#pragma unroll
+                    for (int o = 8; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+                    if (tx == 0) gxs[GX ? (ty * 4 + u) * VDC + c : 0] += a;
+                }
+            }
+        }
+    }
+
+    // per-term sums of the whole workgroup
+    T* out = p.partial + ((int64_t)rt * p.nchunks + chunk) * (NS * GPK_MAX_TERMS + 1);
+#pragma unroll
+    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            s1[t] += __shfl_xor(s1[t], o, 64);
+            s2[t] += __shfl_xor(s2[t], o, 64);
+            if (SH) s3[SH ? t : 0] += __shfl_xor(s3[SH ? t : 0], o, 64);
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+            red[(wave * GPK_MAX_TERMS + t) * NS] = s1[t];
+            red[(wave * GPK_MAX_TERMS + t) * NS + 1] = s2[t];
+            if (SH) red[(wave * GPK_MAX_TERMS + t) * NS + 2] = s3[SH ? t : 0];
+        }
+    }
+    __syncthreads();
+    if (tid < NS * GPK_MAX_TERMS) {
+        out[tid] = red[tid] + red[NS * GPK_MAX_TERMS + tid] + red[2 * NS * GPK_MAX_TERMS + tid] + red[3 * NS * GPK_MAX_TERMS + tid];
+    } else if (tid == NS * GPK_MAX_TERMS) {
+        out[tid] = T(0);      // the trace slot
+    }
+    // d/dX: one partial per column chunk, written by the rows' owners
+    if (GX && tx == 0) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = i0 + ty * 4 + u;
+            for (int c = 0; c < p.d; ++c)
+                if (i < p.n) p.gradx[((int64_t)chunk * p.n + i) * p.d + c] = gxs[GX ? (ty * 4 + u) * VDC + c : 0];
+        }
+    }
+}
+
+template <typename T, int MODE, bool SH>
+void diff_vjp_launch_mode(const VjpDiffArgs<T>& a, dim3 grid, hipStream_t stream) {
+    if constexpr (MODE != DMODE_DXY) {
+        if (a.gradx != nullptr) {
+            hipLaunchKernelGGL((kmat_diff_vjp_kernel<T, MODE, SH, true>), grid, dim3(256), 0, stream, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((kmat_diff_vjp_kernel<T, MODE, SH, false>), grid, dim3(256), 0, stream, a);
+}
+
+}  // namespace
+
+// Status codes: the argument positions of gpk_kmat_diff_vjp (include/gpk.h); every argument is checked before an empty problem returns GPK_OK.
+template <typename T>
+int gpk_kmat_diff_vjp_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                             int dim_x, int dim_y, const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
+                             const T* G, int64_t ldg, T* partial, T* gradx, hipStream_t stream) {
+    if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(6);
+    bool shaped = false;
+    for (int t = 0; t < nterms; ++t) {
+        const int k = kinds[t];
+        if (k != GPK_K_EQ && k != GPK_K_MATERN32 && k != GPK_K_MATERN52 && k != GPK_K_LINEAR && k != GPK_K_CONST && k != GPK_K_RQ)
+            return GPK_ERR_ARG(2);      // Matern12 and Delta have no derivative; unknown kinds
+        if (k == GPK_K_RQ) {
+            shaped = true;
+            if (shapes == nullptr) return GPK_ERR_ARG(1);       // (`shapes` as for gpk_kmat_diff: -1 without the array, -5 for alpha <= 0)
+            if (!(shapes[t] > 0)) return GPK_ERR_ARG(5);
+        }
+    }
+    if (d < 0) return GPK_ERR_ARG(15);
+    if (dim_x < -1 || dim_x >= d || (dim_x < 0 && dim_y < 0)) return GPK_ERR_ARG(7);
+    if (dim_y < -1 || dim_y >= d) return GPK_ERR_ARG(8);
+    if (n > INT32_MAX) return GPK_ERR_ARG(10);
+    if (m > INT32_MAX) return GPK_ERR_ARG(13);
+    const int mode = dim_y < 0 ? DMODE_DX : dim_x < 0 ? DMODE_DY : DMODE_DXY;
+    if (gradx != nullptr && (mode == DMODE_DXY || d > VDC)) return GPK_ERR_ARG(19);     // d/dX: the one-sided modes, d <= 8
+    int64_t rt, nc, tpc;
+    gpk_kmat_vjp_dense_grid_impl(n, m, &rt, &nc, &tpc);
+    if (nc > 65535) return GPK_ERR_ARG(13);
+    if (n <= 0 || m <= 0) return GPK_OK;
+    VjpDiffArgs<T> a;
+    a.X = X; a.Y = Y; a.G = G; a.partial = partial; a.gradx = gradx;
+    a.ldx = ldx; a.ldy = ldy; a.ldg = ldg;
+    a.n = (int)n; a.m = (int)m; a.d = d; a.nterms = nterms;
+    a.dim_x = dim_x; a.dim_y = dim_y;
+    a.tiles_per_chunk = (int)tpc; a.nchunks = (int)nc; a.ctiles = (int)gpk_cdiv(m, DT);
+    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+        a.kind[t] = t < nterms ? kinds[t] : GPK_K_CONST;
+        a.ils2[t] = t < nterms ? (T)(inv_ls[t] * inv_ls[t]) : T(0);
+        a.var[t] = t < nterms ? (T)variances[t] : T(0);
+        a.shape[t] = (t < nterms && kinds[t] == GPK_K_RQ) ? (T)shapes[t] : T(1);
+    }
+    const dim3 grid((unsigned)rt, (unsigned)nc);
+    if (shaped) {
+        if (mode == DMODE_DX) diff_vjp_launch_mode<T, DMODE_DX, true>(a, grid, stream);
+        else if (mode == DMODE_DY) diff_vjp_launch_mode<T, DMODE_DY, true>(a, grid, stream);
+        else diff_vjp_launch_mode<T, DMODE_DXY, true>(a, grid, stream);
+    } else {
+        if (mode == DMODE_DX) diff_vjp_launch_mode<T, DMODE_DX, false>(a, grid, stream);
+        else if (mode == DMODE_DY) diff_vjp_launch_mode<T, DMODE_DY, false>(a, grid, stream);
+        else diff_vjp_launch_mode<T, DMODE_DXY, false>(a, grid, stream);
+    }
+    GPK_CHECK_LAUNCH();
+    return GPK_OK;
+}
+template int gpk_kmat_diff_vjp_launch<double>(const int*, const double*, const double*, const double*, int, int, int, const double*,
+                                              int64_t, int64_t, const double*, int64_t, int64_t, int, const double*, int64_t, double*,
+                                              double*, hipStream_t);
+template int gpk_kmat_diff_vjp_launch<float>(const int*, const double*, const double*, const double*, int, int, int, const float*,
+                                             int64_t, int64_t, const float*, int64_t, int64_t, int, const float*, int64_t, float*, float*,
+                                             hipStream_t);
+
 int64_t gpk_kmat_vjp_blocks_impl(int64_t n) {
     const int64_t nt = gpk_cdiv(n > 0 ? n : 1, VT);
     return nt * (nt + 1) / 2;

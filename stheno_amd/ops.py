@@ -588,6 +588,32 @@ class HipBackend:
         return (tot[: ns * nt].reshape(nt, ns), colsum.sum(0) if want_colsum else None,
                 gradx.sum(0) if want_gradx else None)
 
+    @_on_operand_device
+    def kmat_diff_vjp(self, terms, x, y, dim_x, dim_y, g, want_gradx=False):
+        """Sums over the explicit cotangent ``g`` (n, m) of the derivative block ``kmat_diff(terms, x, y, dim_x, dim_y)``, which is never
+        formed (``gpk_kmat_diff_vjp``): returns ``(S, gradx)`` with ``S[t] = (sum g beta_t, sum g c dbeta_t/dc[, sum g dbeta_t/dalpha_t])``
+        in the conventions of ``kmat_vjp_dense`` -- a block element is ``sum_t v_t beta_t`` -- and ``gradx[i] = sum_j g_ij d block_ij /
+        dx_i`` (``None`` unless asked for; the one-sided blocks and at most 8 input dimensions)."""
+        self._check(x, y, g)
+        n, d = x.shape
+        m = y.shape[0]
+        if g.shape != (n, m) or g.stride(1) != 1:
+            raise ValueError("cotangent must be an (n, m) matrix with unit inner stride")
+        dims = tuple(-1 if v is None else int(v) for v in (dim_x, dim_y))
+        rt, nc = ctypes.c_int64(), ctypes.c_int64()
+        self._st(self.lib.gpk_kmat_vjp_dense_grid(n, m, ctypes.byref(rt), ctypes.byref(nc)), "gpk_kmat_vjp_dense_grid")
+        rt, nc = rt.value, nc.value
+        ns = 2 if terms.shapes is None else 3
+        partial = torch.zeros((rt * nc, ns * _native.MAX_TERMS + 1), dtype=x.dtype, device=x.device)
+        gradx = torch.zeros((nc, n, d), dtype=x.dtype, device=x.device) if want_gradx else None
+        kinds, var, ils, nt = terms.c_arrays()
+        x, y = x.contiguous(), y.contiguous()
+        code = self.lib.gpk_kmat_diff_vjp(_dtype_id(x), kinds, var, ils, terms.c_shapes(), nt, *dims, self._ptr(x), n, x.stride(0),
+                                          self._ptr(y), m, y.stride(0), d, self._ptr(g), g.stride(0), self._ptr(partial),
+                                          self._ptr(gradx), self._stream())
+        self._st(code, "gpk_kmat_diff_vjp")
+        return partial.sum(0)[: ns * nt].reshape(nt, ns), gradx.sum(0) if want_gradx else None
+
     # -- in-place odds and ends ------------------------------------------------
     @_on_operand_device
     def tril_(self, a):
@@ -771,6 +797,93 @@ class _HostDelta:
             if diag_vec is not None:
                 res[..., idx, idx] += diag_vec.detach().cpu().numpy().reshape(res.shape[:-2] + (res.shape[-1],))
         return self._deliver(self._t(res, x), out, accumulate)
+
+    def kmat_diff_vjp(self, terms, x, y, dim_x, dim_y, g, want_gradx=False):
+        """``HipBackend.kmat_diff_vjp`` in NumPy (fp64), from the closed forms in ``include/gpk.h`` (gpk_kmat_diff_vjp)."""
+        import numpy as np
+
+        if dim_x is None and dim_y is None:
+            raise ValueError("a derivative block differentiates at least one argument")
+        a = x.detach().cpu().numpy().astype(np.float64)
+        b = y.detach().cpu().numpy().astype(np.float64)
+        G = g.detach().cpu().numpy().astype(np.float64)
+        n, d = a.shape
+        for dim in (dim_x, dim_y):
+            if dim is not None and not 0 <= dim < d:
+                raise ValueError(f"dimension {dim} outside the {d} input dimensions")
+        mixed = dim_x is not None and dim_y is not None
+        if want_gradx and (mixed or d > 8):
+            raise RuntimeError("libgpk gpk_kmat_diff_vjp failed with status -19")
+        df = a[:, None, :] - b[None, :, :]
+        r2 = (df ** 2).sum(-1)
+        da = df[..., dim_x] if dim_x is not None else None
+        db = df[..., dim_y] if dim_y is not None else None
+        sd = None if mixed else (da if dim_y is None else -db)      # D_a, or -D_b
+        same = mixed and dim_x == dim_y
+        sel = dim_x if dim_y is None else dim_y
+        shapes = terms.shapes or [None] * len(terms)
+        S = np.zeros((len(terms), 2 if terms.shapes is None else 3))
+        cD, cS = np.zeros_like(r2), np.zeros_like(r2)
+        for t, ((kind, v, scale), al) in enumerate(zip(terms.terms, shapes)):
+            c = (1.0 / scale) ** 2
+            if kind == "const":
+                continue
+            if kind == "linear":
+                if dim_y is None:
+                    be = c * b[None, :, dim_x]
+                elif dim_x is None:
+                    be = c * a[:, None, dim_y]
+                else:
+                    be = c * float(same)
+                S[t, 0] = S[t, 1] = (G * be).sum()
+                if dim_x is None:
+                    cS += v * c
+                continue
+            q = c * r2
+            k1a = k2a = 0.0
+            if kind == "eq":
+                e = np.exp(-0.5 * q)
+                k1, k2, qk2, m3 = -0.5 * e, 0.25 * e, 0.25 * q * e, e * (0.5 - 0.125 * q)
+            elif kind == "matern32":
+                s = np.sqrt(3.0 * q)
+                e = np.exp(-s)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    inv = np.where(s > 0, 1.0 / np.where(s > 0, s, 1.0), 0.0)
+                k1, k2, qk2, m3 = -1.5 * e, 2.25 * e * inv, 0.75 * s * e, 1.125 * (3.0 - s) * e * inv
+            elif kind == "matern52":
+                s = np.sqrt(5.0 * q)
+                e = np.exp(-s)
+                k1, k2, qk2, m3 = -(5.0 / 6.0) * (1.0 + s) * e, (25.0 / 12.0) * e, (5.0 / 12.0) * s * s * e, e * (25.0 / 6.0 - 25.0 / 24.0 * s)
+            elif kind == "rq":
+                u = q / (2.0 * al)
+                lg, ri = np.log1p(u), 1.0 / (1.0 + u)
+                p1 = np.exp(-(al + 1.0) * lg)
+                p2 = p1 * ri
+                w = u * ri / al
+                r2c = (al + 1.0) / (4.0 * al)
+                k1, k2 = -0.5 * p1, r2c * p2
+                qk2 = q * k2
+                m3 = k2 * (2.0 - q * ri * (al + 2.0) / (2.0 * al))
+                k1a = -0.5 * p1 * ((al + 1.0) * w - lg)
+                k2a = r2c * p2 * ((al + 2.0) * w - lg) - p2 / (4.0 * al * al)
+            else:
+                raise NotImplementedError(f"a {kind!r} term has no derivative")
+            if mixed:
+                f, h = -4.0 * c * c * da * db, (-2.0 * c if same else 0.0)
+                be, bc, ba = f * k2 + h * k1, f * m3 + h * (k1 + qk2), f * k2a + h * k1a
+            else:
+                f = 2.0 * c * sd
+                be, bc, ba = f * k1, f * (k1 + qk2), f * k1a
+                cD += v * 2.0 * c * f * k2
+                cS += (2.0 if dim_y is None else -2.0) * v * c * k1
+            S[t, 0], S[t, 1] = (G * be).sum(), (G * bc).sum()
+            if kind == "rq":
+                S[t, 2] = (G * ba).sum()
+        gradx = None
+        if want_gradx:
+            gradx = ((G * cD)[:, :, None] * df).sum(1)
+            gradx[:, sel] += (G * cS).sum(1)
+        return self._t(S, x), (self._t(gradx, x) if want_gradx else None)
 
     def kdiag(self, terms, x):
         rest, delta, _ = self._split(terms)
