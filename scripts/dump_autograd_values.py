@@ -1,5 +1,5 @@
 """Every output and every gradient of the differentiable paths on the test-only host backends, as raw fp64 in one ``.npz``: what a
-host-side change of ``kernels.py`` / ``autograd.py`` must leave equal BIT FOR BIT.
+host-side change of ``kernels.py`` / ``learnable.py`` / ``autograd.py`` must leave equal BIT FOR BIT.
 
     python scripts/dump_autograd_values.py OUT.npz            # dump
     python scripts/dump_autograd_values.py A.npz B.npz        # compare two dumps (exit status 1 when an entry differs)

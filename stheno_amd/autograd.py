@@ -14,7 +14,7 @@ Gradients w.r.t. the inputs ``x`` (learnt input warps, latent inputs, per-dimens
 ``G`` is formed in the buffer of ``K^{-1}`` (a rank-C GEMM update) and ``gpk_kmat_vjp_dense`` reduces it
 against ``dK_ij/dx_i``; both arguments of ``k(x, x)`` move with ``x``, hence the factor two.
 
-A kernel enters every function here as GROUPS of terms that see the same inputs (``kernels._map_groups``): ``k(x, y) = sum_g
+A kernel enters every function here as GROUPS of terms that see the same inputs (``Kernel`` objects taken apart by ``kernels._map_groups``): ``k(x, y) = sum_g
 k_g(u_g(x), u_g(y))`` with ``k_g`` a sum of primitives and ``u_g`` a differentiable map of the inputs (none, the division by
 per-dimension length scales, the periodic embedding), formed in torch by the caller.  The cotangent of ``K`` is the same for every group;
 the reductions against it run once per group, on that group's term table and mapped inputs, and each group's input gradient goes back to
@@ -23,11 +23,16 @@ torch, which carries it through the map to its parameter and to ``x``.  One grou
 The posterior marginals (``post(xs).mean`` / ``.var_diag`` / ``.marginals()`` / ``.marginal_credible_bounds()``) have three functions
 further down: ``_PosteriorMarginals`` (an exact posterior of one process predicted from its own observations), ``_BlockPosteriorMarginals``
 (one exact conditioning step ACROSS processes: a component of a sum, several observed processes, derivatives -- the blocks are sums of
-groups ``s D^(a, b) k_g(u_g(x), u_g(y))``, ``kernels._block_groups``, and a derivative group's cotangent is reduced by
+groups ``s D^(a, b) k_g(u_g(x), u_g(y))``, ``learnable._block_groups``, and a derivative group's cotangent is reduced by
 ``gpk_kmat_diff_vjp``) and ``_SparsePosteriorMarginals`` (pseudo-point posteriors).  Each runs the plain path as its forward, so the
 values are that path's bits, and derives everything else from the stored factors.
+
+This module holds the maths on ``libgpk`` launches and the packing of a kernel into a function's arguments; it imports nothing from
+``kernels``.  Whether a call is in a covered case (groups, mapped inputs, dimension checks, dispatch, plain path or refusal) is decided in
+``stheno_amd/learnable.py``, which calls the thin ``apply`` wrappers here.
 """
 import collections
+import itertools
 import math
 
 import torch
@@ -137,6 +142,69 @@ def _inverse_parts(be, chol, w):
     kinv = be.gemm(W, W, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True)    # N^3/3 flops
     cols = [be.colreduce(W, w[:, c], want_dot=True, want_ss=False)[0] for c in range(w.shape[1])]
     return W, kinv, (cols[0][:, None] if len(cols) == 1 else torch.stack(cols, dim=1))
+
+
+def _zeros(rows, cols, like):
+    """An all-zero (rows, cols) operand read through a zero row stride (no rows x cols buffer), dtype and device of ``like``."""
+    return torch.zeros((1, cols), dtype=like.dtype, device=like.device).expand(rows, cols)
+
+
+def _offsets(sizes):
+    """The first row of each observation set in the block matrix, and the total behind them."""
+    return [0, *itertools.accumulate(sizes)]
+
+
+#: one group of one block in the layout of ``_JointLogpdf`` / ``_BlockPosteriorMarginals``: ``which`` = ``"K"`` for block ``(i, j)`` of the
+#: lower block triangle of the observed covariance, ``"C"`` for the rows of set ``i`` of the cross-covariance; its ``kinds`` and number of
+#: parameters (``_pack``); ``ua`` / ``ub``: its row / column inputs among the mapped inputs; ``(a, b)``: its derivative slots, or None
+Block = collections.namedtuple("Block", "which i j kinds npar ua ub a b")
+
+
+def _walk_blocks(be, layout, sizes, values, meta, us, need_u, kbar, cbar=None):
+    """One reduction per group and block over the block's view of its cotangent -- ``kbar`` (N, N, explicit and symmetric) for the
+    ``"K"`` entries of ``layout``, ``cbar`` (N, N*) for the ``"C"`` ones: ``gpk_kmat_vjp_dense`` for a plain group, ``gpk_kmat_diff_vjp``
+    for a derivative group; off-diagonal blocks of ``kbar`` count twice.  A mapped input that requires a gradient gets it from the pass
+    where it is the row input and from one more pass over the transposed view, with the derivative slots exchanged, where it is the
+    column input; a group that is symmetric in a diagonal block moves both arguments at once, hence twice its one reduction.  Returns
+    ``(gradients of the mapped inputs, gradients of the flat parameters)``."""
+    offs = _offsets(sizes)
+    cbar_t = None
+    grads, grad_us, pos = [None] * len(values), [None] * len(us), 0
+
+    def add(a, gx):
+        grad_us[a] = gx if grad_us[a] is None else grad_us[a] + gx
+
+    def reduce(terms, x, y, a, b, g, want_gx):
+        if a is None and b is None:
+            S, _, gx = be.kmat_vjp_dense(terms, x, y, g, want_gradx=want_gx)
+            return S, gx
+        return be.kmat_diff_vjp(terms, x, y, a, b, g, want_gradx=want_gx)
+
+    for (which, i, j, kinds, npar, ua, ub, a, b) in layout:
+        terms, vals = _unpack(kinds, values[pos: pos + npar])
+        if which == "K":
+            g = kbar[offs[i]: offs[i + 1], offs[j]: offs[j + 1]]
+            wgt = 1.0 if i == j else 2.0
+        else:
+            g = cbar[offs[i]: offs[i + 1], :]
+            wgt = 1.0
+        S, gx = reduce(terms, us[ua], us[ub], a, b, g, need_u[ua])
+        grads[pos: pos + npar] = _param_grads(kinds, vals, S, meta[pos: pos + npar], wgt)
+        pos += npar
+        symmetric = which == "K" and i == j and ua == ub and a == b
+        if need_u[ua]:
+            add(ua, (2.0 if symmetric else wgt) * gx)
+        if need_u[ub] and not symmetric:
+            # the input is the column one: the transposed view (the cotangent of K is symmetric, explicitly), the derivative slots exchanged
+            if which == "K":
+                gt = kbar[offs[j]: offs[j + 1], offs[i]: offs[i + 1]]
+            else:
+                if cbar_t is None:
+                    cbar_t = cbar.t().contiguous()
+                gt = cbar_t[:, offs[i]: offs[i + 1]]
+            _, gx = reduce(terms, us[ub], us[ua], b, a, gt, True)
+            add(ub, wgt * gx)
+    return grad_us, grads
 
 
 class _GPLogpdf(torch.autograd.Function):
@@ -261,12 +329,11 @@ class _JointLogpdf(torch.autograd.Function):
     ``kernels[p_i, p_j](x_i, x_j)``, every block a sum of groups of primitives behind input maps.  Forward = the plain HIP path (blocks
     written into one buffer, factorised in place).  Backward: the explicit cotangent ``G = 1/2 (alpha diag(g) alpha^T - sum(g) K^{-1})``
     once, then one ``gpk_kmat_vjp_dense`` pass per group of every block of the lower block triangle over the block's view of ``G``
-    (off-diagonal blocks count twice: ``G`` and the block matrix are symmetric).  ``layout`` = [(i, j, kinds, number of parameters, a,
-    b)], ``a`` / ``b`` the positions of the group's row / column inputs among the ``nu`` mapped inputs that lead ``tensors``; behind
+    (off-diagonal blocks count twice: ``G`` and the block matrix are symmetric: ``_walk_blocks``).  ``layout`` = one ``Block`` per group,
+    all of them ``"K"`` and without derivative slots; the ``nu`` mapped inputs lead ``tensors``; behind
     them the variances, scales (and shape parameters, for a group that has any: ``_pack``) of group after group: autograd carries them
     back to the user's leaves through whatever kernel algebra produced them.  A mapped input that requires a gradient (a learnable
-    period, learnable per-dimension scales) gets it from the same pass where it is the row input, and from one more pass over the
-    transposed view ``G[j-block, i-block]`` where it is the column input of an off-diagonal block; either way twice the reduction."""
+    period, learnable per-dimension scales) gets twice its reduction, as the row input or, mirrored, as the column input."""
 
     @staticmethod
     def forward(ctx, r, noise_vec, build, sizes, layout, nu, *tensors):
@@ -296,113 +363,15 @@ class _JointLogpdf(torch.autograd.Function):
         g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
         _, kinv, alpha = _inverse_parts(be, chol, w)
         G = _cotangent(be, kinv, alpha, g)
-        offs = [0]
-        for rows in ctx.sizes:
-            offs.append(offs[-1] + rows)
-        grads, grad_us, pos = [None] * len(ctx.values), [None] * nu, 0
-
-        def add(a, gx):
-            grad_us[a] = 2.0 * gx if grad_us[a] is None else grad_us[a] + 2.0 * gx
-
-        for (i, j, kinds, npar, a, b) in ctx.layout:
-            terms, values = _unpack(kinds, ctx.values[pos: pos + npar])
-            gb = G[offs[i]: offs[i + 1], offs[j]: offs[j + 1]]
-            S, _, gx = be.kmat_vjp_dense(terms, us[a], us[b], gb, want_gradx=need_u[a])
-            grads[pos: pos + npar] = _param_grads(kinds, values, S, ctx.param_meta[pos: pos + npar], 1.0 if i == j else 2.0)
-            if need_u[a]:
-                add(a, gx)
-            if i != j and need_u[b]:                             # (the block's mirror image: G is symmetric, explicitly)
-                _, _, gx = be.kmat_vjp_dense(terms, us[b], us[a], G[offs[j]: offs[j + 1], offs[i]: offs[i + 1]], want_gradx=True)
-                add(b, gx)
-            pos += npar
+        grad_us, grads = _walk_blocks(be, ctx.layout, ctx.sizes, ctx.values, ctx.param_meta, us, need_u, G)
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype)) if ctx.needs_input_grad[0] else None
         grad_noise = torch.diagonal(G).clone() if ctx.has_noise else None
         return (grad_r, grad_noise, None, None, None, None, *grad_us, *grads)
 
 
-def joint_logpdf(mok, x, noise_vec, r, eps):
-    """Differentiable joint log-density under ``MultiOutputKernel`` ``mok`` at the multi-input ``x``; None when a block of the
-    lower block triangle is not a sum of primitives behind input maps with scalar hyper-parameters (the caller then refuses)."""
-    from . import kernels as _k
-
-    kernels = mok.kernels
-    parts = [(pid, xi) for pid, xi in mok._split(x)]
-    if any((not torch.is_tensor(xi)) or xi.dim() != 2 or kernels[pid].num_outputs(xi) != xi.shape[0] for pid, xi in parts):
-        return None                                   # batched inputs / nested product processes: not covered
-    if any(xi.requires_grad for _, xi in parts):
-        return None                                   # d/dx through the block matrix: not covered (the caller refuses)
-    layout, params, us, where = [], [], [], {}
-
-    def mapped(i, imap):
-        """Position of ``imap(x_i)`` among the mapped inputs (formed once per part and map, in torch: the graph reaches the map's
-        parameter)."""
-        key = (i, id(imap))
-        if key not in where:
-            where[key] = (len(us), imap)              # (the map is kept: its id cannot be recycled while the table lives)
-            us.append(parts[i][1] if imap is None else imap(parts[i][1]))
-        return where[key][0]
-
-    for i, (pi, _) in enumerate(parts):
-        for j in range(i + 1):
-            kern = kernels[pi] if i == j else kernels[pi, parts[j][0]]
-            groups = _k._map_groups(kern) if isinstance(kern, _k.Kernel) else None
-            if groups is None:
-                return None
-            for kg, imap_x, imap_y in groups:            # block (i, j) = sum_g k_g(imap_x(x_i), imap_y(x_j))
-                rows = kg.tensor_table()
-                if rows is None or (i == j and not _k._same_map(imap_x, imap_y)):
-                    return None
-                kd, pr = _pack(rows)
-                layout.append((i, j, kd, len(pr), mapped(i, imap_x), mapped(j, imap_y)))
-                params.extend(pr)
-    if not torch.is_grad_enabled() or not (any(p.requires_grad for p in params) or any(u.requires_grad for u in us) or r.requires_grad
-                                            or (noise_vec is not None and noise_vec.requires_grad)):
-        return None
-    for u in us:
-        if u.requires_grad:
-            check_input_dims(u)
-
-    def build():
-        return mok.pairwise(x, None, lower=True, diag_add=eps, diag_vec=noise_vec)
-
-    return _JointLogpdf.apply(r, noise_vec, build, tuple(xi.shape[0] for _, xi in parts), tuple(layout), len(us), *us, *params)
-
-
-def table_requires_grad(rows):
-    """Does a term table in its tensor view (``Kernel.tensor_table()``) carry a gradient -- on a variance, a scale or a shape parameter?"""
-    return torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for row in rows for p in row[1:])
-
-
-def kernel_requires_grad(kernel, _depth=0):
-    """Does any hyper-parameter reachable from ``kernel`` carry a gradient?  (Used to refuse -- loudly --
-    the cases the differentiable paths do not cover, instead of returning a value cut off from the graph.)"""
-    from . import kernels as _k
-
-    if _depth > 16:
-        return False
-    rows = kernel.tensor_table() if isinstance(kernel, _k.Kernel) else None
-    if rows is not None:
-        return table_requires_grad(rows)
-    if isinstance(kernel, _k.MultiOutputKernel):
-        ks = kernel.kernels
-        return any(kernel_requires_grad(ks[p], _depth + 1) for p in kernel.pids)
-    for val in vars(kernel).values():
-        if torch.is_tensor(val) and val.requires_grad:
-            return True
-        if isinstance(val, _k.InputMap) and val.requires_grad:       # a learnable shift, the parameters behind a feature map
-            return True
-        if isinstance(val, _k.Kernel) and kernel_requires_grad(val, _depth + 1):
-            return True
-    return False
-
-
-def groups_need_grad(groups, *others):
-    """Does anything behind a kernel given as groups ``[(k_g, u_g)]`` require a gradient: a group's term table or mapped inputs, or one
-    of the ``others`` (noise, residual, inducing inputs; ``None`` entries are skipped)?"""
-    if not torch.is_grad_enabled():
-        return False
-    return (any(table_requires_grad(kern.tensor_table()) or (torch.is_tensor(u) and u.requires_grad) for kern, u in groups)
-            or any(t is not None and t.requires_grad for t in others))
+def joint_logpdf(r, noise_vec, build, sizes, layout, us, params):
+    """Differentiable log-density of ``_JointLogpdf`` (``learnable.logpdf`` builds the arguments)."""
+    return _JointLogpdf.apply(r, noise_vec, build, sizes, layout, len(us), *us, *params)
 
 
 def gp_logpdf(groups, noise_vec, r, noise_mat=None):
@@ -413,6 +382,23 @@ def gp_logpdf(groups, noise_vec, r, noise_mat=None):
         (x,) = [u for _, u in groups]
         return _GPLogpdfBatched.apply(r, noise_vec, layout, x, *params)
     return _GPLogpdf.apply(r, noise_vec, noise_mat, layout, *[u for _, u in groups], *params)
+
+
+def _diag_share(grp, x, g_kd, gr, gx, need_x):
+    """The share of ``k(x_j, x_j)`` (cotangent ``g_kd`` (N,): the trace term of VFE, FITC's effective noise) in the parameter gradients
+    ``gr`` (``_param_grads``' list, updated in place) and in the gradient ``gx`` of the inputs ``x`` (returned; only with ``need_x``):
+    a stationary term is its variance there, whatever its scale and shape; a linear term is ``v |x_j|^2 / l^2`` and moves with ``x_j``."""
+    kinds, nt = grp.kinds, len(grp.kinds)
+    variances, scales, _ = grp.values
+    for t in range(nt):
+        if kinds[t] == "linear":
+            xx = ((x * x).sum(-1) * g_kd).sum() / scales[t] ** 2
+            gr[t], gr[nt + t] = gr[t] + xx, gr[nt + t] - 2.0 * variances[t] / scales[t] * xx
+            if need_x:
+                gx = gx + (2.0 * variances[t] / scales[t] ** 2) * g_kd[:, None] * x
+        else:
+            gr[t] = gr[t] + g_kd.sum()
+    return gx
 
 
 # ---------------------------------------------------------------------------------------------
@@ -475,7 +461,7 @@ class _SparseELBO(torch.autograd.Function):
         be = ops.get_backend()
         sv, grp = ctx.saved, ctx.group
         r, d, s, v, q, corr, tau = sv["r"], sv["d"], sv["s"], sv["v"], sv["q"], sv["corr"], sv["tau"]
-        (x, z), terms, kinds, nt = grp.inputs, grp.terms, grp.kinds, len(grp.kinds)
+        (x, z), terms, kinds = grp.inputs, grp.terms, grp.kinds
         m = z.shape[0]
         eye = torch.eye(m, dtype=x.dtype, device=x.device)
         w_a = sv["chol_a"].inverse_lower()                                     # L_A^{-1}
@@ -525,21 +511,12 @@ class _SparseELBO(torch.autograd.Function):
         S = s_k + s_kz
         # through k(x_j, x_j) (VFE: trace term; FITC: the effective noise): stationary terms are constant there
         g_kd = g_d if fitc else -0.5 * tau / d
-        variances, scales, _ = grp.values
         go = grad_out.to(x.dtype)
         # through the kernel matrices: the sums' own formulas, left where they were computed -- the diagonal's share is added term by
-        # term BEFORE the output cotangent multiplies (the order the sums have always been taken in); shape parameters get none: every
-        # stationary kind is 1 on the diagonal, whatever its shape
+        # term BEFORE the output cotangent multiplies (the order the sums have always been taken in)
         gr = _param_grads(kinds, grp.values, S, [(S.device, S.dtype)] * len(grp.meta))
         if tau or fitc:
-            for t in range(nt):
-                if kinds[t] == "linear":
-                    xx = ((x * x).sum(-1) * g_kd).sum() / scales[t] ** 2
-                    gr[t], gr[nt + t] = gr[t] + xx, gr[nt + t] - 2.0 * variances[t] / scales[t] * xx
-                    if need_x:      # k(x_j, x_j) = v |x_j|^2 / l^2 moves with x_j (stationary terms are constant there)
-                        gx_k = gx_k + (2.0 * variances[t] / scales[t] ** 2) * g_kd[:, None] * x
-                else:
-                    gr[t] = gr[t] + g_kd.sum()
+            gx_k = _diag_share(grp, x, g_kd, gr, gx_k, need_x)
         grads = [None if g_ is None else (g_ * go).to(device=dev, dtype=dt) for g_, (dev, dt) in zip(gr, grp.meta)]
         grad_z = (gz_k + 2.0 * gz_kz) * go if need_z else None
         grad_x = gx_k * go if need_x else None
@@ -575,10 +552,39 @@ def sparse_elbo(kernel, x, z, noise_vec, r, method):
 # (gpk_kmat_vjp_dense, x 2, as in the log-density).  The one new operation is the back-substitution with the transposed factor,
 # gpk_trsm_lower_t / gpk_trsv_lower_t: N^2 N* flops for B against N^3/3 for an explicit inverse.
 # ---------------------------------------------------------------------------------------------
+def _posterior_cotangents(be, ctx, g_mu, g_s, dt, dims=()):
+    """What the backward of the exact posterior marginals starts from, one process or several: ``(gm, gs, alpha, bm, beta)`` -- the
+    cotangents of ``mu`` and ``s`` (None for an output that has none; ``gs`` also for a loss of the mean only), ``alpha = K^{-1} r``,
+    ``bm = B = L^{-T} V`` (only with ``gs``: the N x N* back-substitution) and ``beta = B gm`` (without ``gs``: one single-column
+    back-substitution) -- or None when neither output has a cotangent.  ``dims``: the inputs whose gradient is wanted (``check_input_dims``
+    behind that answer, in front of the first launch)."""
+    chol, v = ctx.chol, ctx.v
+    gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
+    gs = g_s.to(dt).contiguous() if g_s is not None else None
+    if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
+        gs = None
+    if gm is None and gs is None:
+        return None
+    for u in dims:
+        check_input_dims(u)
+    transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
+    alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
+    bm = beta = None
+    if gs is not None:
+        # B = L^{-T} V: the N x N* back-substitution (its right-hand side is a private copy: the solve uses it up)
+        bm = chol.solve_t_(v.plain() if transposed else be.copy(v))
+        if gm is not None:
+            beta = be.gemv(bm, gm[:, None])[:, 0]
+    else:
+        vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[:, None])[:, 0]
+        beta = chol.solve_t(vg[:, None])[:, 0]
+    return gm, gs, alpha, bm, beta
+
+
 class _PosteriorMarginals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, noise_vec, run, layout, *tensors):
-        """``run()`` -> ``(chol, w, v, mu, s)``: the plain HIP path of the posterior (``kernels._posterior_parts``: the factor a
+        """``run()`` -> ``(chol, w, v, mu, s)``: the plain HIP path of the posterior (``learnable._posterior_parts``: the factor a
         preceding log-density left, or the one whose factorisation carried the cross-covariance as rows under the matrix); ``v`` is
         ``L^{-1} k(x, xs)`` (N, N*) or its transpose as a ``WhitenedT``.  ``layout`` = one ``(kinds, number of parameters)`` per group of
         terms; ``tensors`` = per group ``x`` / ``xs`` as its fused kernels see them (behind the group's input map), then the groups'
@@ -595,45 +601,24 @@ class _PosteriorMarginals(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_mu, g_s):
         be = ops.get_backend()
-        chol, v, groups = ctx.chol, ctx.v, ctx.groups
+        groups = ctx.groups
         ng = len(groups)
         x0, xs0 = groups[0].inputs
         n, ns = x0.shape[0], xs0.shape[0]
         dt, dev = x0.dtype, x0.device
-        gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
-        gs = g_s.to(dt).contiguous() if g_s is not None else None
-        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
-            gs = None
         need_x = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
         need_xs = [ctx.needs_input_grad[5 + 2 * i] for i in range(ng)]
-        npar = sum(len(grp.meta) for grp in groups)
-        if gm is None and gs is None:
-            return (None,) * (4 + 2 * ng + npar)
-        for grp, nx, nxs in zip(groups, need_x, need_xs):
-            if nx or nxs:
-                check_input_dims(grp.inputs[0])
-        transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
-        alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
-        bm = beta = None
-        if gs is not None:
-            # B = L^{-T} V: the N x N* back-substitution (its right-hand side is a private copy: the solve uses it up)
-            bm = chol.solve_t_(v.plain() if transposed else be.copy(v))
-            if gm is not None:
-                beta = be.gemv(bm, gm[:, None])[:, 0]
-        elif gm is not None:
-            vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[:, None])[:, 0]
-            beta = chol.solve_t(vg[:, None])[:, 0]
-
-        def zeros(rows, cols):          # an all-zero operand read through a zero row stride (no rows x cols buffer)
-            return torch.zeros((1, cols), dtype=dt, device=dev).expand(rows, cols)
-
+        pre = _posterior_cotangents(be, ctx, g_mu, g_s, dt, [grp.inputs[0] for grp, nx, nxs in zip(groups, need_x, need_xs) if nx or nxs])
+        if pre is None:
+            return (None,) * (4 + 2 * ng + sum(len(grp.meta) for grp in groups))
+        gm, gs, alpha, bm, beta = pre
         # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs), the same for every group
         cs = 2.0 * gs if gs is not None else None
         S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
         g_t = None
         for i, grp in enumerate(groups):
             terms, (x, xs) = grp.terms, grp.inputs
-            S[i], _, grad_x[i] = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
+            S[i], _, grad_x[i] = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else _zeros(n, ns, x0), colscale=cs, w=alpha, b=gm,
                                                    want_gradx=need_x[i])
             if need_xs[i]:
                 if g_t is None:
@@ -642,7 +627,7 @@ class _PosteriorMarginals(torch.autograd.Function):
                         be.scale_cols_(g_t, cs)
                         g_t = g_t.t().contiguous()                       # (N*, N): 2 diag(gs) B^T, explicit
                     else:
-                        g_t = zeros(ns, n)
+                        g_t = _zeros(ns, n, x0)
                 _, _, grad_xs[i] = be.kmat_vjp_dense(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
         del g_t
         # through K: -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T) = 1/2 (A diag(g) A^T - sum(g) S)
@@ -658,7 +643,7 @@ class _PosteriorMarginals(torch.autograd.Function):
             cols.append(torch.zeros_like(x0[:, 0]))
             g.append(2.0)
         else:
-            kinv = zeros(n, n)
+            kinv = _zeros(n, n, x0)
         A = torch.stack(cols, dim=1)
         diag_g = None
         for i, grp in enumerate(groups):
@@ -686,27 +671,23 @@ class _PosteriorMarginals(torch.autograd.Function):
 # Posterior marginals ACROSS processes: one exact conditioning step on one or several observation sets, any one process p of the
 # measure predicted at xs -- a component of a sum, another observed process, a derivative (`post(f.diff())`), or values predicted from
 # observed slopes.  K is the block matrix of the observed processes (MultiOutputKernel), C = K(x_obs, xs) the stacked cross-covariances
-# with p; every block is a sum of groups s D^(a, b) k_g(u_g(x), u_g(y)) (kernels._block_groups), (a, b) the derivative slots of a
+# with p; every block is a sum of groups s D^(a, b) k_g(u_g(x), u_g(y)) (learnable._block_groups), (a, b) the derivative slots of a
 # DiffKernel, both None for a plain group.  Forward: the plain path, as it is.  Backward, from the stored factor and V = L^{-1} C, with
 # B = L^{-T} V, alpha = K^{-1} r, beta = B gm (the same algebra as above):
 #     dL/dC = alpha gm^T + 2 B diag(gs)                                   (N x N*, explicit)
 #     dL/dK = -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T)         (N x N, explicit and symmetric; its diagonal: d/dnoise)
 #     dL/dr = beta
 # -- one gpk_trsm_lower_t and one N x N x N* GEMM (the rank-one and rank-two parts are GEMMs of contraction length 1 and 2) -- and then
-# one reduction per group and block over the block's view of either cotangent: gpk_kmat_vjp_dense for a plain group, gpk_kmat_diff_vjp
-# for a derivative group; off-diagonal blocks of dL/dK count twice.  A mapped input that requires a gradient (the test inputs, a
-# learnable period, ...) gets it from the pass where it is the row input and from one more pass over the transposed view, with the
-# derivative slots exchanged, where it is the column input.  The one-sided derivative blocks have an input gradient (d <= 8), the mixed
-# block has none: the caller refuses that before anything is launched.
+# one reduction per group and block over the block's view of either cotangent (_walk_blocks), which also gives a mapped input that
+# requires a gradient (the test inputs, a learnable period, ...) its own.  The one-sided derivative blocks have an input gradient
+# (d <= 8), the mixed block has none: the caller refuses that before anything is launched.
 # ---------------------------------------------------------------------------------------------
 class _BlockPosteriorMarginals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, noise_vec, run, sizes, layout, nu, *tensors):
-        """``run()`` -> ``(chol, w, v, mu, s)`` as for ``_PosteriorMarginals``; ``sizes``: the rows of each observation set; ``layout``
-        = ``[(which, i, j, kinds, number of parameters, ua, ub, a, b)]``, one entry per group: ``which`` = ``"K"`` for block ``(i, j)``
-        of the lower block triangle of the observed covariance, ``"C"`` for the rows of set ``i`` of the cross-covariance; ``ua`` /
-        ``ub`` the positions of the group's row / column inputs among the ``nu`` mapped inputs that lead ``tensors``, ``(a, b)`` its
-        derivative slots; behind the inputs the groups' parameters (``_pack``; the group's factor is in the variances)."""
+        """``run()`` -> ``(chol, w, v, mu, s)`` as for ``_PosteriorMarginals``; ``sizes``: the rows of each observation set; ``layout``:
+        one ``Block`` per group; the ``nu`` mapped inputs lead ``tensors``, behind them the groups' parameters (``_pack``; the group's
+        factor is in the variances)."""
         chol, w, v, mu, s = run()
         params = tensors[nu:]
         ctx.chol, ctx.w, ctx.v, ctx.sizes, ctx.layout, ctx.us = chol, w, v, sizes, layout, tensors[:nu]
@@ -721,27 +702,14 @@ class _BlockPosteriorMarginals(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_mu, g_s):
         be = ops.get_backend()
-        chol, v, us = ctx.chol, ctx.v, ctx.us
+        us = ctx.us
         nu = len(us)
-        nothing = (None,) * (6 + nu + len(ctx.values))
         dt, dev = us[0].dtype, us[0].device
-        gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
-        gs = g_s.to(dt).contiguous() if g_s is not None else None
-        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
-            gs = None
-        if gm is None and gs is None:
-            return nothing
+        pre = _posterior_cotangents(be, ctx, g_mu, g_s, dt)
+        if pre is None:
+            return (None,) * (6 + nu + len(ctx.values))
+        gm, gs, alpha, bm, beta = pre
         need_u = [ctx.needs_input_grad[6 + a] for a in range(nu)]
-        transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
-        alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
-        bm = beta = None
-        if gs is not None:
-            bm = chol.solve_t_(v.plain() if transposed else be.copy(v))      # B = L^{-T} V (a private copy: the solve uses it up)
-            if gm is not None:
-                beta = be.gemv(bm, gm[:, None])[:, 0]
-        else:
-            vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[:, None])[:, 0]
-            beta = chol.solve_t(vg[:, None])[:, 0]
         n = sum(ctx.sizes)
         ns = gm.shape[0] if gm is not None else gs.shape[0]
         # the two cotangents, explicit
@@ -759,52 +727,14 @@ class _BlockPosteriorMarginals(torch.autograd.Function):
             be.gemm(alpha[:, None].contiguous(), gm[:, None].contiguous(), a_kmajor=True, b_kmajor=True, alpha=1.0, beta=1.0, out=cbar)
             be.gemm(torch.stack([beta, alpha], dim=1), torch.stack([alpha, beta], dim=1), a_kmajor=True, b_kmajor=True, alpha=-0.5,
                     beta=1.0, out=kbar)
-        offs = [0]
-        for rows in ctx.sizes:
-            offs.append(offs[-1] + rows)
-        cbar_t = None
-        grads, grad_us, pos = [None] * len(ctx.values), [None] * nu, 0
-
-        def add(a, gx):
-            grad_us[a] = gx if grad_us[a] is None else grad_us[a] + gx
-
-        def reduce(terms, x, y, a, b, g, want_gx):
-            if a is None and b is None:
-                S, _, gx = be.kmat_vjp_dense(terms, x, y, g, want_gradx=want_gx)
-                return S, gx
-            return be.kmat_diff_vjp(terms, x, y, a, b, g, want_gradx=want_gx)
-
-        for (which, i, j, kinds, npar, ua, ub, a, b) in ctx.layout:
-            terms, values = _unpack(kinds, ctx.values[pos: pos + npar])
-            if which == "K":
-                g = kbar[offs[i]: offs[i + 1], offs[j]: offs[j + 1]]
-                wgt = 1.0 if i == j else 2.0
-            else:
-                g = cbar[offs[i]: offs[i + 1], :]
-                wgt = 1.0
-            S, gx = reduce(terms, us[ua], us[ub], a, b, g, need_u[ua])
-            grads[pos: pos + npar] = _param_grads(kinds, values, S, ctx.param_meta[pos: pos + npar], wgt)
-            pos += npar
-            symmetric = which == "K" and i == j and ua == ub and a == b
-            if need_u[ua]:
-                add(ua, (2.0 if symmetric else wgt) * gx)
-            if need_u[ub] and not symmetric:
-                # the input is the column one: the transposed view (dL/dK is symmetric, explicitly), the derivative slots exchanged
-                if which == "K":
-                    gt = kbar[offs[j]: offs[j + 1], offs[i]: offs[i + 1]]
-                else:
-                    if cbar_t is None:
-                        cbar_t = cbar.t().contiguous()
-                    gt = cbar_t[:, offs[i]: offs[i + 1]]
-                _, gx = reduce(terms, us[ub], us[ua], b, a, gt, True)
-                add(ub, wgt * gx)
+        grad_us, grads = _walk_blocks(be, ctx.layout, ctx.sizes, ctx.values, ctx.param_meta, us, need_u, kbar, cbar)
         grad_r = beta[:, None] if (beta is not None and ctx.has_r and ctx.needs_input_grad[0]) else None
         grad_noise = torch.diagonal(kbar).clone() if (ctx.has_noise and ctx.needs_input_grad[1]) else None
         return (grad_r, grad_noise, None, None, None, None, *grad_us, *grads)
 
 
 def block_posterior_marginals(r, noise_vec, run, sizes, layout, us, params):
-    """Differentiable ``(mu, s)`` of ``_BlockPosteriorMarginals`` (``kernels._learnable_block_marginals`` builds the arguments)."""
+    """Differentiable ``(mu, s)`` of ``_BlockPosteriorMarginals`` (``learnable._block_marginals`` builds the arguments)."""
     return _BlockPosteriorMarginals.apply(r, noise_vec, run, sizes, layout, len(us), *us, *params)
 
 
@@ -833,7 +763,7 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, r, noise_vec, run, fitc, layout, *tensors):
         """``run()`` -> ``(chol_z, chol_a, chol_post, w, vz, va, mu, s)``: the plain HIP path of the pseudo-point posterior
-        (``kernels._sparse_posterior_parts``) -- the factors of ``K_z``, of ``A + eps I`` (the mean's) and of ``A + eps L_z^{-1} L_z^{-T}``
+        (``learnable._sparse_posterior_parts``) -- the factors of ``K_z``, of ``A + eps I`` (the mean's) and of ``A + eps L_z^{-1} L_z^{-T}``
         (the variance's), ``w = L_z^{-1} (mu_z - m(z))`` (M, 1), ``vz = L_z^{-1} K_s``, ``va = L_post^{-1} vz`` (M, N*) and the outputs;
         what a mean-only / variance-only call does not need is None.  ``layout`` / ``tensors``: ONE group, its inputs ``x`` (N, D), ``z``
         (M, D) and ``xs`` (N*, D) as the fused kernels see them, then its parameters; ``r`` (N, 1), ``noise_vec`` (N,)."""
@@ -850,7 +780,7 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
         be = ops.get_backend()
         chol_z, chol_a, chol_post, w, vz, va = ctx.parts
         grp, fitc = ctx.group, ctx.fitc
-        (x, z, xs), terms, kinds, nt = grp.inputs, grp.terms, grp.kinds, len(grp.kinds)
+        (x, z, xs), terms, kinds = grp.inputs, grp.terms, grp.kinds
         x, z, xs = x.detach(), z.detach(), xs.detach()
         n, m, ns = x.shape[0], z.shape[0], xs.shape[0]
         dt, dev = x.dtype, x.device
@@ -866,9 +796,6 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
         eps = float(config.epsilon)
         # (an ascent over xs alone -- an acquisition function on a fitted surrogate -- ends behind the k(z, xs) block: nothing of size N)
         model = need_r or need_noise or need_x or need_z or any(ctx.needs_input_grad[8:])
-
-        def zeros(rows, cols):          # an all-zero operand read through a zero row stride (no rows x cols buffer)
-            return torch.zeros((1, cols), dtype=dt, device=dev).expand(rows, cols)
 
         def outer(u, v):
             return u[:, None] * v[None, :]
@@ -896,14 +823,14 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
         # through k(z, xs): cotangent a gm^T + 2 (P - Q) diag(gs)
         cs = 2.0 * gs if gs is not None else None
         if model:
-            S, _, gz = be.kmat_vjp_dense(terms, z, xs, pq if pq is not None else zeros(m, ns), colscale=cs, w=a, b=gm, want_gradx=need_z)
+            S, _, gz = be.kmat_vjp_dense(terms, z, xs, pq if pq is not None else _zeros(m, ns, x), colscale=cs, w=a, b=gm, want_gradx=need_z)
         gxs = None
         if need_xs:
             if pq is not None:
                 be.scale_cols_(pq, cs)
                 g_t = pq.t().contiguous()                                          # (N*, M): 2 diag(gs) (P - Q)^T, explicit
             else:
-                g_t = zeros(ns, m)
+                g_t = _zeros(ns, m, x)
             _, _, gxs = be.kmat_vjp_dense(terms, xs, z, g_t, w=gm, b=a, want_gradx=True)
             del g_t
         del pq
@@ -927,7 +854,7 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
             g_d = -ek * (r - ak) / (d * d)
             gz_k = None
             for wv, bv in ranks:
-                s_k, _, gz_p = be.kmat_vjp_dense(terms, z, x, zeros(m, n), w=wv, b=bv, want_gradx=need_z)
+                s_k, _, gz_p = be.kmat_vjp_dense(terms, z, x, _zeros(m, n, x), w=wv, b=bv, want_gradx=need_z)
                 S = S + s_k
                 if need_z:
                     gz_k = gz_p if gz_k is None else gz_k + gz_p
@@ -961,10 +888,10 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
                 be.scale_cols_(g_k, cs_k)
                 g_t = g_k.t().contiguous()
             else:
-                g_t = zeros(n, m)
+                g_t = _zeros(n, m, x)
             del g_k
             for i, (wv, bv) in enumerate(ranks):
-                _, _, gx_p = be.kmat_vjp_dense(terms, x, z, g_t if i == 0 else zeros(n, m), w=bv, b=wv, want_gradx=True)
+                _, _, gx_p = be.kmat_vjp_dense(terms, x, z, g_t if i == 0 else _zeros(n, m, x), w=bv, b=wv, want_gradx=True)
                 gx = gx_p if gx is None else gx + gx_p
             del g_t
         else:
@@ -978,18 +905,9 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
             g_kz = g_kz - (0.5 * (1.0 + eps)) * (outer(e, a) + outer(a, e))
         s_kz, _, gz_kz = be.kmat_vjp_dense(terms, z, z, g_kz, want_gradx=need_z)
         S = S + s_kz
-        variances, scales, _ = grp.values
         gr = _param_grads(kinds, grp.values, S, [(S.device, S.dtype)] * len(grp.meta))
         if fitc:
-            # through k(x_i, x_i) in the effective noise: stationary terms are their variance there, whatever their shape
-            for t in range(nt):
-                if kinds[t] == "linear":
-                    xx = ((x * x).sum(-1) * g_d).sum() / scales[t] ** 2
-                    gr[t], gr[nt + t] = gr[t] + xx, gr[nt + t] - 2.0 * variances[t] / scales[t] * xx
-                    if need_x:
-                        gx = gx + (2.0 * variances[t] / scales[t] ** 2) * g_d[:, None] * x
-                else:
-                    gr[t] = gr[t] + g_d.sum()
+            gx = _diag_share(grp, x, g_d, gr, gx, need_x)                         # (through k(x_i, x_i) in the effective noise)
         grads = [None if g_ is None else g_.to(device=dv, dtype=dty) for g_, (dv, dty) in zip(gr, grp.meta)]
         grad_z = None
         if need_z:
@@ -1006,19 +924,6 @@ def sparse_posterior_marginals(kernel, x, z, xs, r, noise_vec, method, run):
         raise ValueError(f'Invalid approximation method "{method}".')
     layout, params = _pack_groups([kernel])
     return _SparsePosteriorMarginals.apply(r, noise_vec, run, method == "fitc", layout, x, z, xs, *params)
-
-
-def kdiag_terms(tensor_terms, x):
-    """``k(x_i, x_i)`` (N,) of a sum of primitives as a differentiable torch expression (O(N D)): stationary terms are their variance,
-    a linear term ``v |x_i|^2 / s^2``."""
-    out = None
-    for kind, v, s in tensor_terms:
-        if kind == "linear":
-            t = v * (x * x).sum(-1) / (s * s)
-        else:
-            t = v * torch.ones(x.shape[:-1], dtype=x.dtype, device=x.device)
-        out = t if out is None else out + t
-    return out
 
 
 def posterior_marginals(groups, r, noise_vec, run):

@@ -85,7 +85,9 @@ def sharded_elbo(obs, measure, group=None):
         if _collective(group):
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
 
-    if torch.is_grad_enabled() and obs._differentiable_requested(measure):
+    from . import learnable
+
+    if torch.is_grad_enabled() and learnable.requested(obs, measure):
         raise NotImplementedError(
             "gradients of the observation-sharded bound are not implemented (every rank would differentiate its own "
             "shard's bound): take them of `obs.elbo(measure)` on one rank, or wrap this call in torch.no_grad()"

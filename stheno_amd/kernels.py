@@ -953,8 +953,9 @@ class Sum(Kernel):
         view = self.input_scaled_view()
         if view is not None:
             return _Mapped(*view).elwise(x, y, **kw)
-        if y is None and _sparse_pair(self) is not None:                 # a pseudo-point posterior under learnable quantities
-            got = _learnable_sparse_marginals(None, self, uprank(x), kw.get("cache"))
+        if y is None:
+            from . import learnable                                       # (a pseudo-point posterior under learnable quantities)
+            got = learnable.marginals(None, self, uprank(x), kw.get("cache"))
             if got is not None:
                 return got[1]
         return self.a.elwise(x, y, **kw) + self.b.elwise(x, y, **kw)
@@ -1634,8 +1635,8 @@ class PosteriorKernel(Kernel):
     def __init__(self, k_ij, k_zi, k_zj, z, K_z, own_cross=False, exact=False):
         self.k_ij, self.k_zi, self.k_zj, self.z, self.K_z = k_ij, k_zi, k_zj, z, K_z
         self.own_cross = own_cross       # see _whiten
-        self.exact = exact               # exact conditioning on observations of the process itself (see _learnable_marginals)
-        self.sparse = None               # weak (obs, measure) of a pseudo-point conditioning (see _learnable_sparse_marginals)
+        self.exact = exact               # exact conditioning on observations of the process itself (see learnable.marginals)
+        self.sparse = None               # weak (obs, measure) of a pseudo-point conditioning (likewise)
 
     def num_outputs(self, x):
         return self.k_ij.num_outputs(x)
@@ -1659,8 +1660,9 @@ class PosteriorKernel(Kernel):
         return _add_diag(out, diag_add, diag_vec) if sym else out
 
     def elwise(self, x, y=None, *, cache=None):
+        from . import learnable
         x = uprank(x)
-        got = _learnable_marginals(None, self, x, cache)
+        got = learnable.marginals(None, self, x, cache)
         if got is not None:
             return got[1]
         out = self.k_ij.elwise(x)
@@ -1760,8 +1762,9 @@ class PosteriorMean(Mean):
                 chol.remember_residual(self._residual()[0], w)
 
     def __call__(self, x, cache=None):
+        from . import learnable
         x = uprank(x)
-        got = _learnable_marginals(self, None, x, cache) if self.sparse is None else _learnable_sparse_marginals(self, None, x, cache)
+        got = learnable.marginals(self, None, x, cache)
         if got is not None:
             return got[0]
         rhs = None
@@ -1782,368 +1785,6 @@ class PosteriorMean(Mean):
             v = v.plain()
         dot, _ = ops.get_backend().colreduce(v, w, want_dot=True, want_ss=False)
         return self.m_i(x) + dot[..., None]
-
-
-def _posterior_parts(pm, K_z, k, z, x, cache, own_cross):
-    """The plain HIP path of the posterior marginals, unchanged (``PosteriorMean.__call__`` / ``PosteriorKernel.elwise``): returns
-    ``(chol, w, v, mu, s)`` -- the factor, ``w = L^{-1} r`` (None without a mean), ``v = L^{-1} k(z, x)`` (or ``WhitenedT``),
-    ``mu = v^T w`` and ``s = |v_j|^2`` (N*,), the latter two from one pass over ``v``."""
-    rhs = None
-    if pm is not None and pm._w is None and own_cross and hasattr(K_z, "can_factor_with_rows"):
-        _, r = pm._residual()
-        if r.dim() == 2 and r.shape[-1] == 1 and not r.requires_grad:
-            rhs = (r, pm._took)
-    v = _whiten(cache, K_z, k, z, x, own_cross, rhs)
-    w = pm._whitened_residual() if pm is not None else None
-    be = ops.get_backend()
-    if isinstance(v, WhitenedT):
-        mu, s = be.rowreduce(v.zt, w, want_dot=w is not None, want_ss=True)
-    else:
-        mu = be.colreduce(v, w, want_dot=True, want_ss=False)[0] if w is not None else None
-        _, s = be.colreduce(v, want_ss=True)
-    return K_z.chol(), w, v, mu, s
-
-
-def _learnable_marginals(pm, pk, x, cache):
-    """Posterior mean / marginal variances of an EXACT posterior of one process under learnable quantities, through
-    ``autograd._PosteriorMarginals``: ``(mean column or None, marginal-variance column or None)`` for the posterior mean ``pm`` and /
-    or the posterior kernel ``pk`` at the test inputs ``x``.  None when nothing learnable is behind them, when grad is off, or when the
-    call is outside that path and outside the block path that takes over where the one-process case does not apply
-    (``_learnable_block_marginals``: another process than the observed one, several observation sets, derivatives) -- pseudo-point
-    posteriors (``_learnable_sparse_marginals``), chained conditioning, batched inputs, a block that is no sum of groups of primitives
-    behind input maps, dense noise: the plain path then runs exactly as before."""
-    if not torch.is_grad_enabled():
-        return None
-    src = pm if pm is not None else pk
-    if not getattr(src, "exact", False):
-        return None
-    K_z, k, z = src.K_z, src.k_zi, src.z
-    # (anything but one process predicted from its own observations -- a component of a sum, several observed processes, derivatives:
-    #  the block path, which answers None itself where it does not apply)
-    if pk is not None and not (pk.exact and pk.K_z is K_z and pk.z is z and pk.k_zi is k and pk.k_zj is k and pk.k_ij is k):
-        return _learnable_block_marginals(pm, pk, x, cache)
-    from .matrix import KernelDense
-
-    if not isinstance(K_z, KernelDense) or K_z.kernel is not k:
-        return _learnable_block_marginals(pm, pk, x, cache)
-    if not (torch.is_tensor(x) and torch.is_tensor(z) and x.dim() == 2 and z.dim() == 2 and x.shape[-1] == z.shape[-1]
-            and x.dtype == z.dtype and x.device == z.device):
-        return None
-    noise_vec = K_z.differentiable_noise()
-    if noise_vec is NotImplemented or (noise_vec is not None and noise_vec.dim() != 1):
-        return None
-    groups = _symmetric_groups(k)        # terms behind the same input map: one group is the plain case
-    if groups is None or not all(kern.tensor_terms() for kern, _, _ in groups):
-        return _learnable_block_marginals(pm, pk, x, cache)
-    from . import autograd as _ag
-
-    r = None
-    if pm is not None:
-        y, r = pm._residual()
-        if r.dim() != 2 or r.shape[-1] != 1:
-            return None
-        if pm._r_detached and not r.requires_grad:        # (formed under no_grad: form it again inside the graph)
-            r = y - pm.m_z(z)
-    learnable = (_ag.kernel_requires_grad(k) or x.requires_grad or z.requires_grad
-                 or (noise_vec is not None and noise_vec.requires_grad) or (r is not None and r.requires_grad))
-    if not learnable:
-        return None
-    mapped = [(kern, z if imap is None else imap(z), x if imap is None else imap(x)) for kern, imap, _ in groups]
-    for _, zin, xin in mapped:
-        if zin.requires_grad or xin.requires_grad:
-            _ag.check_input_dims(xin)
-    xd = x.detach()                  # (the plain path sees values only: the rows path stays open, one whitening serves mean and variance)
-    own_cross = src.own_cross
-
-    def run():
-        return _posterior_parts(pm, K_z, k, z, xd, cache, own_cross)
-
-    mu, s = _ag.posterior_marginals(mapped, r, noise_vec, run)
-    mean = pm.m_i(x) + mu[..., None] if pm is not None else None
-    vd = None
-    if pk is not None:
-        # the value of k(x, x) from the fused launch (the plain path's bits), its gradient from the same sum written in torch
-        kt = sum(_ag.kdiag_terms(kern.tensor_terms(), xin) for kern, _, xin in mapped)
-        vd = (k.elwise(xd) + (kt - kt.detach())[..., None]) - s[..., None]
-    return mean, vd
-
-
-def _block_groups(k):
-    """A kernel as groups ``s * D^(a, b) k_g(imap_x(x), imap_y(y))``: ``[(s, a, b, k_g, imap_x, imap_y)]`` with ``k_g`` a sum of
-    primitives, ``(a, b)`` the derivative slots of a ``DiffKernel`` (both ``None``: the plain case of ``_map_groups``) and ``s`` a
-    factor (a float, or the tensor a ``Scaled`` carries).  ``_map_groups`` extended to look inside ``DiffKernel``, ``Sum``, ``Scaled``
-    and ``Reversed``: what the blocks of several processes' covariance are made of.  ``[]`` for the zero kernel (independent
-    processes); None when the kernel has no such form."""
-    if isinstance(k, ZeroKernel):
-        return []
-    if isinstance(k, DiffKernel):
-        kern, imap, imap_y = k.k.input_scaled_view()
-        return [(1.0, k.dim_x, k.dim_y, kern, imap, imap_y)]
-    if not isinstance(k, Kernel) or isinstance(k, (MultiOutputKernel, _CrossKernel, PosteriorKernel, SubspaceKernel)):
-        return None
-    plain = _map_groups(k)
-    if plain is not None:
-        return [(1.0, None, None, kern, mx, my) for kern, mx, my in plain]
-    if isinstance(k, Sum):
-        ga, gb = _block_groups(k.a), _block_groups(k.b)
-        return None if ga is None or gb is None else ga + gb
-    if isinstance(k, Scaled):
-        g = _block_groups(k.k)
-        return None if g is None else [(s * k.v, a, b, kern, mx, my) for s, a, b, kern, mx, my in g]
-    if isinstance(k, Reversed):
-        g = _block_groups(k.k)      # (a sum of primitives is symmetric: the slots and the maps change places)
-        return None if g is None else [(s, b, a, kern, my, mx) for s, a, b, kern, mx, my in g]
-    return None
-
-
-def _group_factor(s, a, b, imap):
-    """The factor in front of a group's term table: ``s``, times the chain-rule factors ``1 / l_a``, ``1 / l_b`` of a derivative behind
-    per-dimension length scales (a torch expression where ``s`` or the scales are tensors)."""
-    f = s
-    if isinstance(imap, _ScaleMap):
-        for dim in (a, b):
-            if dim is not None:
-                f = f / (imap.param[dim] if torch.is_tensor(imap.param) else float(np.asarray(imap.param, dtype=np.float64).reshape(-1)[dim]))
-    return f
-
-
-def _group_diag(group, x):
-    """``s D^(a, b) k_g(imap(x_j), imap(x_j))`` (N,) of a group as a torch expression -- ``autograd.kdiag_terms`` for a plain group, the
-    closed form of ``DiffKernel.elwise`` for a derivative -- or None when the group sees its two arguments through different maps."""
-    from . import autograd as _ag
-
-    s, a, b, kern, mx, my = group
-    if not _same_map(mx, my):
-        return None
-    xm = x if mx is None else mx(x)
-    if a is None and b is None:
-        return s * _ag.kdiag_terms(kern.tensor_terms(), xm)
-    f = _group_factor(s, a, b, mx)
-    if a is not None and b is not None:
-        if a != b:
-            return torch.zeros(x.shape[:-1], dtype=x.dtype, device=x.device)
-        value = sum(var / (scale * scale) * _DIFF_AT_ZERO[kind] for kind, var, scale in kern.tensor_terms()) * f
-        return value * torch.ones(x.shape[:-1], dtype=x.dtype, device=x.device)
-    lin = sum(var / (scale * scale) for kind, var, scale in kern.tensor_terms() if kind == "linear") * f
-    return lin * xm[..., a if b is None else b]
-
-
-def _learnable_block_marginals(pm, pk, x, cache):
-    """What ``_learnable_marginals`` returns, for ONE exact conditioning step on a prior measure that the one-process case does not
-    cover: one or several observation sets (``z`` a tensor or a ``MultiInput``), a prediction of any one process of the measure -- a
-    component of a sum, another observed process, a derivative --, through ``autograd._BlockPosteriorMarginals``.  Every block of the
-    lower block triangle of the observed processes' covariance, every cross-kernel with the predicted process and that process's own
-    kernel has to be a sum of groups (``_block_groups``); None otherwise (the plain path then runs as before).  Refuses, before any
-    launch, the two gradients the derivative kernels do not provide."""
-    src = pm if pm is not None else pk
-    K_z, k_cross, z = src.K_z, src.k_zi, src.z
-    if pk is not None and not (pk.exact and pk.K_z is K_z and pk.z is z and pk.k_zi is k_cross and pk.k_zj is k_cross):
-        return None
-    from . import autograd as _ag
-    from .matrix import KernelDense
-
-    if not isinstance(K_z, KernelDense) or K_z.x is not z:
-        return None
-    kz = K_z.kernel
-    if isinstance(z, MultiInput):
-        if not (isinstance(kz, MultiOutputKernel) and isinstance(k_cross, _CrossKernel) and k_cross.mok is kz):
-            return None
-        kernels = kz.kernels
-        parts = kz._split(z)
-        if any(not torch.is_tensor(zi) or kernels[pid].num_outputs(zi) != zi.shape[-2] for pid, zi in parts):
-            return None                               # (nested product processes)
-        block = lambda i, j: kernels[parts[i][0]] if i == j else kernels[parts[i][0], parts[j][0]]      # noqa: E731
-        cross = lambda i: kernels[parts[i][0], k_cross.j]                                               # noqa: E731
-    else:
-        if isinstance(kz, MultiOutputKernel) or not torch.is_tensor(z):
-            return None
-        parts = [(None, z)]
-        block, cross = (lambda i, j: kz), (lambda i: k_cross)
-    ins = [zi for _, zi in parts] + [x]
-    if not (torch.is_tensor(x) and all(t.dim() == 2 and t.shape[-1] == x.shape[-1] and t.dtype == x.dtype and t.device == x.device for t in ins)):
-        return None
-    noise_vec = K_z.differentiable_noise()
-    if noise_vec is NotImplemented or (noise_vec is not None and noise_vec.dim() != 1):
-        return None
-    P = len(parts)
-    spec = []                                          # (which, i, j, group, row input, column input)
-    for i in range(P):
-        for j in range(i + 1):
-            groups = _block_groups(block(i, j))
-            if groups is None:
-                return None
-            spec += [("K", i, j, g, i, j) for g in groups]
-    for i in range(P):
-        groups = _block_groups(cross(i))
-        if groups is None:
-            return None
-        spec += [("C", i, 0, g, i, P) for g in groups]
-    own = _block_groups(pk.k_ij) if pk is not None else []
-    if own is None:
-        return None
-    r = None
-    if pm is not None:
-        y, r = pm._residual()
-        if r.dim() != 2 or r.shape[-1] != 1:
-            return None
-        if pm._r_detached and not r.requires_grad:        # (formed under no_grad: form it again inside the graph)
-            r = y - pm.m_z(z)
-    us, where, layout, params = [], {}, [], []
-
-    def mapped(i, imap):
-        """Position of ``imap(ins[i])`` among the mapped inputs (formed once per input and map, in torch)."""
-        key = (i, id(imap))
-        if key not in where:
-            where[key] = (len(us), imap)              # (the map is kept: its id cannot be recycled while the table lives)
-            us.append(ins[i] if imap is None else imap(ins[i]))
-        return where[key][0]
-
-    for which, i, j, (s, a, b, kern, mx, my), row, col in spec:
-        rows = kern.tensor_table()
-        if rows is None:
-            return None
-        if not rows:
-            continue
-        if (a is not None or b is not None) and ((mx is not None and mx.requires_grad) or (my is not None and my.requires_grad)):
-            raise NotImplementedError("gradients of a posterior with respect to per-dimension length scales under a derivative "
-                                      "(`k.stretch(vector)` behind `f.diff()`) are not implemented")
-        kinds, pr = _ag._pack(rows)
-        f = _group_factor(s, a, b, mx)
-        if torch.is_tensor(f) or f != 1.0:
-            pr[: len(kinds)] = [v * f for v in pr[: len(kinds)]]
-        layout.append((which, i, j, kinds, len(pr), mapped(row, mx), mapped(col, my), a, b))
-        params.extend(pr)
-    own_diag = [_group_diag(g, x) for g in own if g[3].tensor_table()]
-    if any(t is None for t in own_diag):
-        return None
-    kt = sum(own_diag) if own_diag else None
-    learnable = (any(p.requires_grad for p in params) or any(u.requires_grad for u in us) or (torch.is_tensor(kt) and kt.requires_grad)
-                 or (noise_vec is not None and noise_vec.requires_grad) or (r is not None and r.requires_grad))
-    if not learnable:
-        return None
-    for which, i, j, kinds, npar, ua, ub, a, b in layout:
-        if us[ua].requires_grad or us[ub].requires_grad:
-            if a is not None and b is not None:
-                raise NotImplementedError("gradients with respect to the inputs of a mixed derivative block (both the row and the column "
-                                          "process are derivatives: `xs.requires_grad` when a derivative is predicted from observed "
-                                          "derivatives, or inputs of derivative observations that require a gradient) are not implemented")
-            _ag.check_input_dims(us[ua] if us[ua].requires_grad else us[ub])
-    xd = x.detach()
-    own_cross = src.own_cross
-
-    def run():
-        return _posterior_parts(pm, K_z, k_cross, z, xd, cache, own_cross)
-
-    mu, s = _ag.block_posterior_marginals(r, noise_vec, run, tuple(zi.shape[-2] for _, zi in parts), tuple(layout), us, params)
-    mean = pm.m_i(x) + mu[..., None] if pm is not None else None
-    vd = None
-    if pk is not None:
-        # the value of k(x, x) from the plain path (its bits), its gradient from the same sum written in torch
-        vd = pk.k_ij.elwise(xd)
-        if torch.is_tensor(kt) and kt.requires_grad:
-            vd = vd + (kt - kt.detach())[..., None]
-        vd = vd - s[..., None]
-    return mean, vd
-
-
-def _sparse_pair(kernel):
-    """The link (weak references to ``(obs, measure)``) behind ``PosteriorKernel + SubspaceKernel`` of one pseudo-point conditioning
-    (``AbstractPseudoObservations.posterior_kernel``), else None."""
-    if isinstance(kernel, Sum) and isinstance(kernel.a, PosteriorKernel) and isinstance(kernel.b, SubspaceKernel):
-        link = getattr(kernel.a, "sparse", None)
-        if link is not None and getattr(kernel.b, "sparse", None) is link:
-            return link
-    return None
-
-
-def _sparse_posterior_parts(pm, pk, sk, k, z, x, cache, chol_a):
-    """The plain HIP path of the pseudo-point posterior marginals, unchanged (``PosteriorMean.__call__``, ``PosteriorKernel.elwise`` +
-    ``SubspaceKernel.elwise``): returns ``(chol_z, chol_a, chol_post, w, vz, va, mu, s)`` as ``autograd._SparsePosteriorMarginals``
-    takes them -- ``mu = vz^T w``, ``s = |vz_j|^2 - |va_j|^2``; what a mean-only (``pk`` None) or variance-only (``pm`` None) call does
-    not need is None."""
-    be = ops.get_backend()
-    K_z = (pm if pm is not None else pk).K_z
-    vz = _whiten(cache, K_z, k, z, x)
-    w = mu = va = s = chol_post = None
-    if pm is not None:
-        w = pm._whitened_residual()
-        mu = be.colreduce(vz, w, want_dot=True, want_ss=False)[0]
-    if pk is not None:
-        va = _whiten(cache, sk.A, k, z, x)
-        s = be.colreduce(vz, want_ss=True)[1] - be.colreduce(va, want_ss=True)[1]
-        chol_post = sk.A.chol().chols[1]
-    return K_z.chol(), chol_a, chol_post, w, vz, va, mu, s
-
-
-def _learnable_sparse_marginals(pm, kernel, x, cache):
-    """Posterior mean / marginal variances of a PSEUDO-POINT posterior (VFE / FITC / DTC) under learnable quantities, through
-    ``autograd._SparsePosteriorMarginals``: ``(mean column or None, marginal-variance column or None)`` for the posterior mean ``pm``
-    and / or the posterior kernel ``kernel`` (``PosteriorKernel + SubspaceKernel``) at the test inputs ``x``.  None when nothing
-    learnable is behind them, when grad is off, or when the call is outside the case the bound admits
-    (``AbstractPseudoObservations._differentiable``: noise-free inducing points of the observed process itself, one kernel that is a sum
-    of primitives behind one input map, diagonal noise, unbatched) at the inducing process: the plain path then runs as before."""
-    if not torch.is_grad_enabled():
-        return None
-    link = pm.sparse if pm is not None else _sparse_pair(kernel)
-    if link is None or (pm is not None and kernel is not None and _sparse_pair(kernel) is not link):
-        return None
-    obs, measure = link[0](), link[1]()
-    if obs is None or measure is None:
-        return None
-    from .matrix import Diagonal, Zero
-
-    p_x, xo, noise_x = obs.fdd.p, obs.fdd._xr, obs.fdd.noise
-    p_z, z, noise_z = obs.u.p, obs.u._xr, obs.u.noise
-    if isinstance(xo, MultiInput) or isinstance(z, MultiInput) or not isinstance(noise_x, Diagonal) or not isinstance(noise_z, Zero):
-        return None
-    k = measure.kernels[p_z]
-    view = k.input_scaled_view() if isinstance(k, Kernel) else None
-    if view is None or not _same_map(view[1], view[2]):
-        return None
-    if not (measure.kernels[p_x] is k and measure.kernels[p_z, p_x] is k):
-        return None
-    if not all(torch.is_tensor(t) and t.dim() == 2 and t.shape[-1] == z.shape[-1] and t.dtype == z.dtype and t.device == z.device
-               for t in (x, xo, z)):
-        return None
-    pk = sk = None
-    if kernel is not None:
-        pk, sk = kernel.a, kernel.b
-        if not (pk.k_ij is k and pk.k_zi is k and pk.k_zj is k and sk.k_zi is k and sk.k_zj is k and pk.z is z and sk.z is z):
-            return None
-    if pm is not None and not (pm.k_zi is k and pm.z is z and pm.m_i is measure.means[p_z] and (pk is None or pk.K_z is pm.K_z)):
-        return None
-    parts = obs._parts.get(measure)
-    if parts is None or parts["K_z"] is not (pm if pm is not None else pk).K_z or noise_x.diag().dim() != 1:
-        return None
-    kern, imap, _ = view                          # k(a, b) = kern(imap(a), imap(b))
-    if not kern.tensor_terms():
-        return None
-    from . import autograd as _ag
-
-    noise_vec = noise_x.diag()
-    learnable = _ag.kernel_requires_grad(k) or any(t.requires_grad for t in (x, xo, z, noise_vec, obs.y))
-    if not learnable and isinstance(measure.means[p_x], ZeroMean):
-        return None                               # (nothing learnable, and no mean that could hide a parameter: not even the residual)
-    r = obs.y - measure.means[p_x](xo)
-    if r.dim() != 2 or r.shape[-1] != 1 or not (learnable or r.requires_grad):
-        return None
-    xm, zm, xsm = (t if imap is None else imap(t) for t in (xo, z, x))
-    if xm.requires_grad or zm.requires_grad or xsm.requires_grad:
-        _ag.check_input_dims(xsm)
-    xd = x.detach()                  # (the plain path sees values only)
-    cache = {} if cache is None else cache        # (K_s is evaluated once for the two whitenings)
-
-    def run():
-        return _sparse_posterior_parts(pm, pk, sk, k, z, xd, cache, parts["chol_A"])
-
-    mu, s = _ag.sparse_posterior_marginals(kern, xm, zm, xsm, r, noise_vec, obs.method, run)
-    mean = pm.m_i(x) + mu[..., None] if pm is not None else None
-    vd = None
-    if pk is not None:
-        # the value of k(x, x) from the fused launch (the plain path's bits), its gradient from the same sum written in torch
-        kt = _ag.kdiag_terms(kern.tensor_terms(), xsm)
-        vd = (k.elwise(xd) + (kt - kt.detach())[..., None]) - s[..., None]
-    return mean, vd
 
 
 # ---------------------------------------------------------------------------
@@ -2178,12 +1819,9 @@ def mean_var_diag(mean, kernel, x):
     cache = {}
     x = uprank(x)
     with deferred_checks():          # (see mean_var)
-        if isinstance(mean, PosteriorMean) and isinstance(kernel, PosteriorKernel):
-            got = _learnable_marginals(mean, kernel, x, cache)       # (under learnable quantities: ONE autograd node for both)
-            if got is not None:
-                return got
-        if isinstance(mean, PosteriorMean) and mean.sparse is not None and _sparse_pair(kernel) is mean.sparse:
-            got = _learnable_sparse_marginals(mean, kernel, x, cache)
+        if isinstance(mean, PosteriorMean):
+            from . import learnable
+            got = learnable.marginals(mean, kernel, x, cache)        # (under learnable quantities: ONE autograd node for both)
             if got is not None:
                 return got
         m = _call_mean(mean, x, cache)

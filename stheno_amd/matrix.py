@@ -434,7 +434,7 @@ class Chol:
 
     def solve_t_(self, b):
         """``L^{-T} b`` with the transposed factor (``b``: (..., n, nrhs), unit inner stride; used up: take the RETURN value) -- the
-        backward of the posterior marginals (``autograd._PosteriorMarginals``).  The merged inverses are those of :meth:`_blocks`.
+        backward of the posterior marginals (``autograd._posterior_cotangents``, ``_SparsePosteriorMarginals``).  The merged inverses are those of :meth:`_blocks`.
         No refinement step: ``config.refine_solves`` / ``wants_refinement`` apply to the forward solves only, the backward takes the
         factor as it is."""
         if b.shape[-2] != self.n:

@@ -111,14 +111,9 @@ class FDD(Normal):
 
     def _learnable(self, x):
         """Does anything behind this log-density require a gradient (kernel hyper-parameters, inputs, noise, the data)?"""
-        from .. import autograd as _ag
-        from ..random import _x_requires_grad
+        from .. import learnable
 
-        nz = self.noise
-        noisy = ((isinstance(nz, Diagonal) and nz.diag().requires_grad)
-                 or (isinstance(nz, Dense) and nz.mat is not None and nz.mat.requires_grad))
-        return bool(noisy or _x_requires_grad(self._xr) or _ag.kernel_requires_grad(self.p.kernel)
-                    or (torch.is_tensor(x) and x.requires_grad))
+        return learnable.density_requires_grad(self.p.kernel, self._xr, self.noise, x)
 
     def _posterior_logpdf_via_prior(self, y):
         """A posterior log-density under learnable quantities, by the chain rule: with the process conditioned on exact

@@ -210,62 +210,14 @@ class AbstractPseudoObservations(AbstractObservations):
     def elbo(self, measure):
         """The evidence lower bound (``observations.py:213-222``).  If a kernel hyper-parameter, the
         noise, the inducing inputs or ``y`` carries a gradient, the bound is returned as a node of the
-        autograd graph (``stheno_amd.autograd.sparse_elbo``) and is not cached."""
-        diff = self._differentiable(measure)
+        autograd graph (``stheno_amd.learnable.elbo``) and is not cached."""
+        from .. import learnable
+        diff = learnable.elbo(self, measure)
         if diff is not None:
             return diff
         if measure not in self._elbo:
             self._compute(measure)
         return self._elbo[measure]
-
-    def _differentiable_requested(self, measure):
-        """Whether anything the bound depends on carries a gradient (kernel hyper-parameters, noise, inducing inputs, y)."""
-        from .. import autograd
-
-        p_x, x, noise_x = self.fdd.p, self.fdd._xr, self.fdd.noise
-        z = self.u._xr
-        k = measure.kernels[self.u.p]
-        view = k.input_scaled_view() if hasattr(k, "input_scaled_view") else None
-        if view is None or isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
-            return autograd.kernel_requires_grad(k) or self.y.requires_grad
-        kern, imap, _ = view
-        return (autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, self.y - measure.means[p_x](x))
-                or any(m is not None and m.requires_grad for m in view[1:]))
-
-    def _differentiable(self, measure):
-        from .. import autograd
-
-        if not torch.is_grad_enabled():
-            return None
-        p_x, x, noise_x = self.fdd.p, self.fdd._xr, self.fdd.noise
-        p_z, z, noise_z = self.u.p, self.u._xr, self.u.noise
-        if isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
-            return None
-        k = measure.kernels[p_z]
-        view = k.input_scaled_view()
-        if view is None or not _k._same_map(view[1], view[2]):
-            return None
-        kern, imap, _ = view                      # k(a, b) = kern(imap(a), imap(b))
-        y_bar = self.y - measure.means[p_x](x)
-        need = autograd.groups_need_grad([(kern, x)], noise_x.diag(), z, y_bar) or (imap is not None and imap.requires_grad)
-        if not need and p_x is not p_z:
-            # data on a process mapped from the inducing points' one (`g = f.shift(tau)`, `f.transform(net)`): a learnable map sits in
-            # the data's kernel and in the cross-kernel only -- outside this path, and refused below rather than detached
-            need = any(m is not None and m.requires_grad for other in (measure.kernels[p_x], measure.kernels[p_z, p_x])
-                       for g in (_k._map_groups(other) or []) for m in g[1:])
-        if not need:
-            return None
-        if not (measure.kernels[p_x] is k and measure.kernels[p_z, p_x] is k and isinstance(noise_z, Zero)
-                and x.dim() == 2 and z.dim() == 2):
-            raise NotImplementedError(
-                "gradients of the bound are implemented for noise-free inducing points of the observed "
-                "process itself (one kernel that is a sum of primitives), unbatched"
-            )
-        if imap is not None:                      # torch differentiates the map (d/d scales or period, d/dx, d/dz)
-            x, z = imap(x), imap(z)
-        if x.requires_grad:
-            autograd.check_input_dims(x)
-        return autograd.sparse_elbo(kern, x, z, noise_x.diag(), y_bar, self.method)
 
     def mu(self, measure):
         """Mean of the optimal approximating distribution (``observations.py:224-237``)."""
@@ -324,7 +276,7 @@ class AbstractPseudoObservations(AbstractObservations):
             self.K_z(measure),
         )
         sk = _k.SubspaceKernel(measure.kernels[self.u.p, p_i], measure.kernels[self.u.p, p_j], z, self.A(measure))
-        pk.sparse = sk.sparse = self._link(measure)      # (the marginals' differentiable path: kernels._learnable_sparse_marginals)
+        pk.sparse = sk.sparse = self._link(measure)      # (the marginals' differentiable path: learnable.marginals)
         return pk + sk
 
     def posterior_mean(self, measure, p):

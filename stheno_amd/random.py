@@ -47,13 +47,6 @@ class RandomVector(Random):
     """A random vector."""
 
 
-def _x_requires_grad(x):
-    """Whether (any component of) an input specification carries gradients."""
-    if torch.is_tensor(x):
-        return x.requires_grad
-    return any(_x_requires_grad(q) for _, q in getattr(x, "parts", ()))
-
-
 def _is_zero(x):
     return isinstance(x, (int, float)) and not isinstance(x, bool) and x == 0
 
@@ -245,60 +238,11 @@ class Normal(RandomVector):
             r = x
         else:
             r = x - self._mean_t
-        # hyper-parameter learning: differentiable path for a kernel-matrix variance
-        batched_ok = (r.dim() == 3 and r.shape[-1] == 1 and torch.is_tensor(getattr(var, "x", None)) and var.x.dim() == 3
-                      and tuple(var.x.shape[:-2]) == tuple(r.shape[:-2]))
-        if isinstance(var, KernelDense) and (r.dim() == 2 or batched_ok):
-            from . import autograd as _ag
-
-            noise_vec, noise_mat = var.differentiable_noise(), None
-            if noise_vec is NotImplemented and r.dim() == 2 and isinstance(var.noise, Dense) and var.noise.mat is not None \
-                    and var.noise.mat.dim() == 2:
-                noise_vec, noise_mat = None, var.noise.mat       # a dense noise covariance: its cotangent is that of K
-            if noise_vec is not None and noise_vec is not NotImplemented and noise_vec.dim() != r.dim() - 1:
-                noise_vec = NotImplemented
-            # k(x) = sum_g k_g(m_g(x)) with every k_g a sum of primitives (m_g: the division by per-dimension length scales, the periodic
-            # embedding, or none): the fused path runs k_g on the mapped inputs; torch differentiates the maps (d/dl, d/dperiod, d/dx).
-            # One group is the plain case; several go group by group through the unbatched log-density only.
-            # (a kernel matrix k(x) is symmetric: every group sees both arguments through the same map)
-            from .kernels import _symmetric_groups
-
-            groups = _symmetric_groups(var.kernel) if torch.is_tensor(var.x) else None
-            if groups is not None and len(groups) > 1 and r.dim() != 2:
-                groups = None
-            if noise_vec is not NotImplemented and groups is not None and all(kern.tensor_terms() is not None for kern, _, _ in groups):
-                mapped = [(kern, var.x if imap is None else imap(var.x)) for kern, imap, _ in groups]
-                if _ag.groups_need_grad(mapped, noise_vec, r, noise_mat):
-                    for _, xin in mapped:
-                        if xin.requires_grad:
-                            _ag.check_input_dims(xin)
-                    lp = _ag.gp_logpdf(mapped, noise_vec, r, noise_mat)
-                    if r.dim() == 3:
-                        return lp, True
-                    return (lp[0] if lp.shape[0] == 1 else lp), True
-        if torch.is_grad_enabled() and isinstance(var, KernelDense) and r.dim() == 2:
-            from . import autograd as _ag
-            from . import kernels as _kk
-
-            if isinstance(var.kernel, _kk.MultiOutputKernel):      # several processes observed jointly
-                noise_vec = var.differentiable_noise()
-                if noise_vec is None or (noise_vec is not NotImplemented and noise_vec.dim() == 1):
-                    lp = _ag.joint_logpdf(var.kernel, var.x, noise_vec, r, config.epsilon)
-                    if lp is not None:
-                        return (lp[0] if lp.shape[0] == 1 else lp), True
-        if torch.is_grad_enabled() and isinstance(var, KernelDense):
-            from . import autograd as _ag
-
-            nz = var.noise
-            noisy = (isinstance(nz, Diagonal) and nz.diag().requires_grad) or (isinstance(nz, Dense) and nz.mat is not None
-                                                                               and nz.mat.requires_grad)
-            if noisy or r.requires_grad or _x_requires_grad(var.x) or _ag.kernel_requires_grad(var.kernel):
-                raise NotImplementedError(
-                    "gradients of logpdf are implemented for one process (or one batch of independent data sets) whose kernel "
-                    "is a sum of primitives with scalar or per-point noise; this call (multi-process, posterior or "
-                    "dense-noise) would return a value cut off from the autograd graph -- wrap it in torch.no_grad() "
-                    "if that is intended"
-                )
+        if isinstance(var, KernelDense):     # hyper-parameter learning: the differentiable paths, or their refusal
+            from . import learnable
+            lp = learnable.logpdf(var, r)
+            if lp is not None:
+                return lp, True
         if isinstance(var, Zero):
             raise torch.linalg.LinAlgError("the variance is identically zero")
         with deferred_checks():      # the factor's `info` is read after the log-determinant and the solve are queued behind it

@@ -1,4 +1,4 @@
-"""Gradients through posteriors across processes (``autograd._BlockPosteriorMarginals``, ``kernels._learnable_block_marginals``) -- the
+"""Gradients through posteriors across processes (``autograd._BlockPosteriorMarginals``, ``learnable._block_marginals``) -- the
 host logic on a NumPy backend, against the dense torch reference of ``tests/block_posterior_cases.py``: a component of a sum, two
 observed processes, values and slopes observed together, a slope predicted from values, predictive noise; the values under
 ``torch.no_grad()``; the two refusals."""
@@ -8,6 +8,7 @@ import torch
 
 import stheno_amd as st
 from stheno_amd import kernels as K
+from stheno_amd import learnable as L
 from stheno_amd import ops
 
 from . import block_posterior_cases as C
@@ -75,20 +76,20 @@ def test_nothing_learnable_keeps_the_plain_path(block_backend):
 
 def test_block_groups():
     k = 1.5 * st.EQ().stretch(0.7) + 0.5 * st.Matern52()
-    (g,) = K._block_groups(k)
+    (g,) = L._block_groups(k)
     assert g[:3] == (1.0, None, None) and g[4] is None
-    (g,) = K._block_groups(k.diff(1, None))
+    (g,) = L._block_groups(k.diff(1, None))
     assert g[:3] == (1.0, 1, None) and g[3].terms() == k.terms()
-    (g,) = K._block_groups(reversed(k.diff(1, None)))
+    (g,) = L._block_groups(reversed(k.diff(1, None)))
     assert g[:3] == (1.0, None, 1)
-    g2 = K._block_groups(2.0 * k.diff(0) + k)
+    g2 = L._block_groups(2.0 * k.diff(0) + k)
     assert [(s, a, b) for s, a, b, *_ in g2] == [(2.0, 0, 0), (1.0, None, None)]
-    assert K._block_groups(K.ZeroKernel()) == []
+    assert L._block_groups(K.ZeroKernel()) == []
     ard = st.EQ().stretch(torch.tensor([0.5, 2.0], dtype=torch.float64))
-    (g,) = K._block_groups(ard.diff(1))
+    (g,) = L._block_groups(ard.diff(1))
     assert g[1:3] == (1, 1) and isinstance(g[4], K._ScaleMap)
-    assert float(K._group_factor(*g[:3], g[4])) == 0.25                     # 1 / l_1^2 rides in the variances
-    assert K._block_groups(st.EQ() * 1.0 + K.Reversed(K.PosteriorKernel(k, k, k, None, None))) is None
+    assert float(L._group_factor(*g[:3], g[4])) == 0.25                     # 1 / l_1^2 rides in the variances
+    assert L._block_groups(st.EQ() * 1.0 + K.Reversed(K.PosteriorKernel(k, k, k, None, None))) is None
 
 
 def _slopes_model(**grad):

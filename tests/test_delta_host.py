@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import stheno_amd.torch as st
-from stheno_amd import _native, autograd, kernels as K, ops
+from stheno_amd import _native, autograd, kernels as K, learnable, ops
 from stheno_amd.torch import EQ, RQ, Delta, Matern52
 
 from . import delta_reference as D
@@ -47,7 +47,7 @@ def test_delta_term_algebra():
     assert isinstance(v, K.InputScaled) and v.input_scaled_view()[0].terms() == [("delta", 1.0, 1.0)]
     # a learnable variance is a learnable hyper-parameter like any other; epsilon never is
     var = torch.tensor(0.1, dtype=torch.float64, requires_grad=True)
-    assert autograd.kernel_requires_grad(var * Delta()) and not autograd.kernel_requires_grad(0.1 * Delta())
+    assert learnable.kernel_requires_grad(var * Delta()) and not learnable.kernel_requires_grad(0.1 * Delta())
     assert (var * Delta()).tensor_terms()[0][1].requires_grad
     assert "Delta" in st.__all__ if hasattr(st, "__all__") else hasattr(st, "Delta")
     import stheno_amd

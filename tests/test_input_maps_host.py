@@ -466,7 +466,7 @@ def test_transform_learnability_rule(be):
     fixed = K._TransformMap(lambda a: torch.tanh(a))
     fixed(T(d["x"]))
     assert not fixed.requires_grad
-    from stheno_amd import autograd as ag
+    from stheno_amd import learnable as ag
     frozen = EQ().transform(net)
     frozen.pairwise(T(d["x"]))
     assert ag.kernel_requires_grad(frozen) is False

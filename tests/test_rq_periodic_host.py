@@ -153,7 +153,7 @@ def test_rq_term_algebra():
     k = 2 * RQ(a).stretch(1.5) + EQ()
     assert k.tensor_shapes()[0] is a and k.tensor_shapes()[1] is None and k.shapes() == [0.7, None]
     assert (RQ(a) + RQ(a)).tensor_shapes() == [a] and len((RQ(a) + RQ(torch.tensor(0.7))).tensor_terms()) == 2
-    from stheno_amd import autograd
+    from stheno_amd import learnable as autograd
     assert autograd.kernel_requires_grad(k) and not autograd.kernel_requires_grad(RQ(0.7) + EQ())
     for bad in (0.0, -1.0, torch.tensor(-0.5)):
         with pytest.raises(ValueError, match="positive"):

@@ -4,7 +4,7 @@ visit per leaf and per view, and the predicate "does this table carry a gradient
 import pytest
 import torch
 
-from stheno_amd import autograd, kernels as K
+from stheno_amd import kernels as K, learnable as autograd
 from stheno_amd.torch import EQ, RQ, Delta, Linear, ZeroKernel
 
 
