@@ -60,7 +60,7 @@ extern "C" {
 #define GPK_DIAG_BLOCK 128 /* order of the diagonal blocks whose inverses gpk_potrf leaves in `dinv` */
 
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
- * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp. */
+ * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -140,6 +140,36 @@ int gpk_kmat_diff(int dtype, const int* kinds, const double* variances, const do
 int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
               const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
               int64_t batch, void* stream);
+
+/* gpk_kmat with ONE TERM TABLE PER BATCH ENTRY: entry b is gpk_kmat's result for x[b], y[b] with the parameters of row b,
+ *   out[b][i][j] (+)= sum_t variances[b * s_terms + t] * kappa_kinds[t](x[b]_i, y[b]_j; inv_ls[b * s_terms + t], shapes[b * s_terms + t]).
+ * `kinds` stays a HOST array of nterms entries: the structure of the kernel is shared by the batch.  `variances`, `inv_ls` and `shapes`
+ * are DEVICE pointers to fp64 tables of `batch` rows of nterms values, s_terms (>= nterms, in elements) apart; `shapes` may be NULL
+ * exactly when no term is GPK_K_RQ or GPK_K_DELTA, and is read for those kinds alone.  Nothing is read back and nothing synchronises.
+ * Every other argument is gpk_kmat's, with gpk_kmat's meaning.
+ *   The workgroups of entry b load row b with uniform loads and derive what gpk_kmat derives on the host, in the same precision and
+ *   order (inv_ls^2 and 1 / (2 alpha) in fp64, then rounded to the dtype), once per workgroup; then they run the program gpk_kmat
+ *   selects for the same kinds (the single-kind EQ / Matern / RQ programs, EQ + Linear, the generic and the shaped term table) on the
+ *   same launch shape.  Entry b therefore holds the bits gpk_kmat writes for x[b], y[b] and row b's parameters (tests/test_batch_terms_gpu.py).
+ *   The values in device memory cannot be checked on the host: an inverse scale that is NaN, an RQ alpha <= 0 (its logarithm's argument
+ *   is negative or its exponent positive) or a NaN anywhere in a row gives NaN or Inf values in THAT BATCH ENTRY only; a Delta
+ *   epsilon <= 0 gives a term that is 0 everywhere.  gpk_kmat's -5 (a shape <= 0) is therefore never returned.
+ *   Returns, checked in this order behind the empty problem (n, m or batch <= 0: 0): -4 for nterms outside 0 .. GPK_MAX_TERMS,
+ *   -6 for n, m (more than 2^31 - 1, or more than 65535 row tiles of 32) or batch (> 65535) too large, -13 for d < 0, -1 for an unknown kind
+ *   or a shaped kind with shapes == NULL, -3 for variances == NULL or inv_ls == NULL with nterms > 0, -7 for s_terms < nterms. */
+int gpk_kmat_batch_terms(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                         int64_t s_terms, const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
+                         int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
+                         int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
+                         void* stream);
+
+/* gpk_kdiag with one term table per batch entry (tables as for gpk_kmat_batch_terms):
+ *   out[b][i] = sum_t variances[b * s_terms + t] * (kinds[t] == GPK_K_LINEAR ? |x[b]_i|^2 inv_ls[b * s_terms + t]^2 : 1).
+ * Returns -4, -1 (a shaped kind with shapes == NULL; kinds are not range-checked, as in gpk_kdiag), -3 and -7 as above, -6 for
+ * batch > 65535. */
+int gpk_kdiag_batch_terms(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                          int64_t s_terms, const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
+                          int64_t batch, void* stream);
 
 /* Number of elements of the `dinv` workspace gpk_potrf needs per batch entry. */
 int64_t gpk_dinv_elems(int64_t n);

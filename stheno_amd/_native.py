@@ -46,6 +46,18 @@ SIGNATURES = {
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64,
          _c_i64, _c_ptr],
     ),
+    # (per-batch term tables: kinds on the host; variances, inv_ls, shapes device pointers to fp64 [batch][nterms]; s_terms behind nterms)
+    "gpk_kmat_batch_terms": (
+        _c_int,
+        [_c_int, _p_int, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
+         _c_i64, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
+         _c_ptr],
+    ),
+    "gpk_kdiag_batch_terms": (
+        _c_int,
+        [_c_int, _p_int, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_i64,
+         _c_i64, _c_ptr],
+    ),
     "gpk_potrf": (_c_int, [_c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_int, _c_ptr]),
     "gpk_potrf_la_ws_elems": (_c_i64, [_c_i64, _c_int]),
     "gpk_potrf_la": (_c_int, [_c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr]),

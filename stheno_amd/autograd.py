@@ -101,11 +101,41 @@ def _unpack(kinds, params):
     """``(terms, values)``: the host descriptor for the fused kernels and the parameters' values
     ``(variances, scales, alphas or None)`` as floats."""
     nt = len(kinds)
+    if any(torch.is_tensor(p) and p.numel() > 1 for p in params):
+        return _unpack_per_batch(kinds, params)
     variances = [float(v) for v in params[:nt]]
     scales = [float(v) for v in params[nt:2 * nt]]
     alphas = [float(v) for v in params[2 * nt:3 * nt]] if len(params) > 2 * nt else None
     shapes = None if alphas is None else [a if k in ops._SHAPED else None for k, a in zip(kinds, alphas)]
     return ops.KTerms(list(zip(kinds, variances, scales)), shapes), (variances, scales, alphas)
+
+
+def _unpack_per_batch(kinds, params):
+    """``_unpack`` where some parameter comes once per batch entry (a ``(B, 1, 1)`` tensor): its values stay on the device, as a detached
+    fp64 vector ``(B,)``, in the descriptor (``ops.KTerms``, per batch) and in the values; the scalar parameters are floats as ever."""
+    nt = len(kinds)
+    vals = [p.detach().reshape(-1).to(torch.float64) if p.numel() > 1 else float(p) for p in params]
+    variances, scales = vals[:nt], vals[nt:2 * nt]
+    alphas = vals[2 * nt:3 * nt] if len(params) > 2 * nt else None
+    shapes = None if alphas is None else [a if k in ops._SHAPED else None for k, a in zip(kinds, alphas)]
+    return ops.KTerms(list(zip(kinds, variances, scales)), shapes), (variances, scales, alphas)
+
+
+def _param_grads_per_batch(kinds, values, S, meta, shapes):
+    """``_param_grads`` from one row of sums PER BATCH ENTRY, ``S`` (B, nt, 2 or 3), entry b's taken with entry b's parameters: a
+    per-batch parameter (``shapes``: the parameters' shapes) gets entry b's gradient at index b, a scalar one the sum over the batch."""
+    variances, scales, alphas = values
+    nt = len(kinds)
+    on = lambda v: v.to(device=S.device, dtype=S.dtype) if torch.is_tensor(v) else v      # noqa: E731
+    gr = [S[:, t, 0] for t in range(nt)] + [-2.0 * on(variances[t]) / on(scales[t]) * S[:, t, 1] for t in range(nt)]
+    if alphas is not None:
+        gr += [(on(variances[t]) * S[:, t, 2]) if kinds[t] in ops._LEARNABLE_SHAPE else None for t in range(nt)]
+    out = []
+    for g_, (dev, dt), shape in zip(gr, meta, shapes):
+        if g_ is not None:
+            g_ = (g_.reshape(shape) if len(shape) else g_.sum()).to(device=dev, dtype=dt)
+        out.append(g_)
+    return out
 
 
 def _param_grads(kinds, values, S, meta, wgt=1.0):
@@ -281,7 +311,11 @@ class _GPLogpdfBatched(torch.autograd.Function):
     """The same for stheno's batched computation (``README.md:744-766``): ``x`` (B, N, D), ``r`` (B, N, 1), optional
     per-point noise (B, N), hyper-parameters SHARED by the B independent GPs -- learning over a batch of data sets
     (the configuration that shards over GPUs).  Forward = the batched HIP path (one launch sequence for all B);
-    backward walks the batch: ``K_b^{-1}`` from the stored factor of entry b, one ``gpk_kmat_vjp`` pass, sums over b."""
+    backward walks the batch: ``K_b^{-1}`` from the stored factor of entry b, one ``gpk_kmat_vjp`` pass, sums over b.
+
+    A hyper-parameter may also come ONCE PER BATCH ENTRY, as a ``(B, 1, 1)`` tensor (restarts, one GP per task, a grid): the forward is
+    the same launch sequence on ``gpk_kmat_batch_terms``; the backward evaluates entry b with entry b's parameters and leaves its row of
+    sums at index b of such a parameter -- the scalar parameters still get the sum over b."""
 
     @staticmethod
     def forward(ctx, r, noise_vec, layout, *tensors):
@@ -296,6 +330,7 @@ class _GPLogpdfBatched(torch.autograd.Function):
         _, ss = be.colreduce(w, want_ss=True)                    # (B, 1)
         out = -(chol.logdet() + n * LOG_2_PI + ss[..., 0]) / 2   # (B,)
         ctx.chol, ctx.w, ctx.group, ctx.has_noise = chol, w, grp, noise_vec is not None
+        ctx.param_shapes = [tuple(p.shape) for p in tensors[1:]]
         return out
 
     @staticmethod
@@ -305,21 +340,31 @@ class _GPLogpdfBatched(torch.autograd.Function):
         x, terms = grp.inputs[0], grp.terms
         B = x.shape[0]
         g_host = [float(v) for v in grad_out.reshape(-1).tolist()]            # host sync: B scalars
-        S_tot = None
+        S_tot, S_each = None, []
+        per_batch = terms.batch is not None
         grad_r = torch.empty_like(w)
         grad_noise = torch.empty(w.shape[:-1], dtype=w.dtype, device=w.device) if ctx.has_noise else None
         grad_x = torch.empty_like(x) if ctx.needs_input_grad[3] else None
+        if grad_x is not None and per_batch:
+            grad_x = torch.empty(x.shape, dtype=x.dtype, device=x.device)       # (shared inputs arrive as an expanded view: a buffer of its own)
         for b in range(B):
             sl = lambda t: None if t is None else t[b:b + 1]      # noqa: E731
             cb = Chol(chol.l[b], sl(chol.dinv), sl(chol.info))                 # entry b as an unbatched factor (views)
+            tb = terms.entry(b)                                                # (the launch's own table, or entry b's)
             _, kinv, alpha = _inverse_parts(be, cb, w[b])
-            S, _, diag_g = be.kmat_vjp(terms, x[b], kinv, alpha, [g_host[b]])
-            S_tot = S if S_tot is None else S_tot + S
+            S, _, diag_g = be.kmat_vjp(tb, x[b], kinv, alpha, [g_host[b]])
+            if per_batch:
+                S_each.append(S)
+            else:
+                S_tot = S if S_tot is None else S_tot + S
             grad_r[b] = -alpha * g_host[b]
             if grad_noise is not None:
                 grad_noise[b] = diag_g
             if grad_x is not None:
-                grad_x[b] = _grad_inputs(be, terms, x[b], _cotangent(be, kinv, alpha, [g_host[b]]))
+                grad_x[b] = _grad_inputs(be, tb, x[b], _cotangent(be, kinv, alpha, [g_host[b]]))
+        if per_batch:
+            grads = _param_grads_per_batch(grp.kinds, grp.values, torch.stack(S_each), grp.meta, ctx.param_shapes)
+            return (grad_r, grad_noise, None, grad_x, *grads)
         return (grad_r, grad_noise, None, grad_x, *_param_grads(grp.kinds, grp.values, S_tot, grp.meta))
 
 

@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 106; }
+int gpk_version(void) { return 107; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -69,6 +69,23 @@ int gpk_kdiag(int dtype, const int* kinds, const double* variances, const double
               int64_t batch, void* stream) {
     D1(dtype, gpk_kdiag_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, sx, d, (T*)out, so,
                                   batch, (hipStream_t)stream));
+}
+
+int gpk_kmat_batch_terms(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                         int64_t s_terms, const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy,
+                         int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
+                         int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
+                         void* stream) {
+    D1(dtype, gpk_kmat_bt_launch<T>(kinds, variances, inv_ls, shapes, nterms, s_terms, (const T*)x, n, ldx, sx, (const T*)y, m,
+                                    ldy, sy, d, (T*)out, ld, so, batch, lower_only, symmetric, diag_add,
+                                    (const T*)diag_vec, s_diag, accumulate, (hipStream_t)stream));
+}
+
+int gpk_kdiag_batch_terms(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                          int64_t s_terms, const void* x, int64_t n, int64_t ldx, int64_t sx, int d, void* out, int64_t so,
+                          int64_t batch, void* stream) {
+    D1(dtype, gpk_kdiag_bt_launch<T>(kinds, variances, inv_ls, shapes, nterms, s_terms, (const T*)x, n, ldx, sx, d, (T*)out, so,
+                                     batch, (hipStream_t)stream));
 }
 
 int gpk_potrf(int dtype, void* a, int64_t n, int64_t ld, int64_t sa, int64_t batch, void* dinv,

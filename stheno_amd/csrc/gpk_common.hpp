@@ -269,6 +269,17 @@ template <typename T>
 int gpk_kdiag_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                      const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
                      int64_t batch, hipStream_t stream);
+// per-batch term tables (gpk_kmat_batch_terms, gpk_kdiag_batch_terms in gpk.h): kinds on the host, the three value tables on the device
+template <typename T>
+int gpk_kmat_bt_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int64_t s_terms,
+                       const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
+                       int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
+                       int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
+                       hipStream_t stream);
+template <typename T>
+int gpk_kdiag_bt_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int64_t s_terms,
+                        const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
+                        int64_t batch, hipStream_t stream);
 template <typename T>
 int gpk_scale_cols_launch(T* V, int64_t rows, int64_t cols, int64_t ld, int64_t sV, const T* s, int64_t ss,
                           int64_t batch, hipStream_t stream);

@@ -14,6 +14,9 @@
 // the X rows of the tile sit in LDS and are read as wave-uniform broadcasts, the
 // Y rows of a lane live in registers.  Squared distances are accumulated as
 // direct differences (no |a|^2 + |b|^2 - 2ab cancellation).
+//
+// gpk_kmat_batch_terms / gpk_kdiag_batch_terms: the same kernels with the template parameter BT -- the term parameters come from
+// fp64 device tables, one row per batch entry, instead of the kernel arguments (TermsArg / TermsReg / TermsLds below).
 #include "gpk_common.hpp"
 #include "gpk_kmat_tile.hpp"   // shared with gpk_kdiff.hip: tile helpers; brings gpk_kmat_plan.hpp (launch geometry) and gpk_kmat_math.hpp
 
@@ -48,17 +51,115 @@ struct KmatArgs {
     // argument offsets as before and compile to the code they compiled to without these two arrays.
     T shape[GPK_MAX_TERMS];
     T hshape[GPK_MAX_TERMS];
+    // per-batch term tables (gpk_kmat_batch_terms; the BT instantiations alone read them): fp64 device arrays [batch][nterms], row stride
+    // bt_stride; bt_shape may be null when no term is shaped.  Behind everything else again, for the same reason.
+    const double* bt_var;
+    const double* bt_ils;
+    const double* bt_shape;
+    int64_t bt_stride;
 };
+
+// Where a kernel program reads the parameters of its terms (the KINDS are always the launch's own: p.terms[t].kind).
+//   TermsArg: the kernel arguments -- gpk_kmat, one table per launch;
+//   TermsReg: terms 0 and 1 of the workgroup's batch entry in scalar registers -- the compile-time programs of gpk_kmat_batch_terms;
+//   TermsLds: the batch entry's whole table in LDS -- its term-table programs (a private array indexed by the term loop would go to scratch).
+template <typename T>
+struct TermsArg {
+    const KmatArgs<T>& p;
+    __device__ __forceinline__ T variance(int t) const { return p.terms[t].variance; }
+    __device__ __forceinline__ T ils2(int t) const { return p.terms[t].ils2; }
+    __device__ __forceinline__ T shape(int t) const { return p.shape[t]; }
+    __device__ __forceinline__ T hshape(int t) const { return p.hshape[t]; }
+};
+template <typename T>
+struct TermsReg {
+    T v[2], c[2], sh[2], hsh[2];
+    __device__ __forceinline__ T variance(int t) const { return v[t]; }
+    __device__ __forceinline__ T ils2(int t) const { return c[t]; }
+    __device__ __forceinline__ T shape(int t) const { return sh[t]; }
+    __device__ __forceinline__ T hshape(int t) const { return hsh[t]; }
+};
+template <typename T>
+struct TermsLds {
+    const T* tab;     // [4][GPK_MAX_TERMS]: variance, ils2, shape, hshape
+    __device__ __forceinline__ T variance(int t) const { return tab[t]; }
+    __device__ __forceinline__ T ils2(int t) const { return tab[GPK_MAX_TERMS + t]; }
+    __device__ __forceinline__ T shape(int t) const { return tab[2 * GPK_MAX_TERMS + t]; }
+    __device__ __forceinline__ T hshape(int t) const { return tab[3 * GPK_MAX_TERMS + t]; }
+};
+
+// a wave-uniform value into scalar registers
+__device__ __forceinline__ float gpk_uniform(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
+__device__ __forceinline__ double gpk_uniform(double x) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// Term t of batch entry b from the device tables, derived as the host derives a launch-wide table (gpk_pack_terms and the shape loop of the
+// launcher): products and quotients in fp64, then rounded to T.  The addresses are uniform over the workgroup: scalar loads, a handful of
+// vector instructions on uniform values once per workgroup, nothing per element.
+template <typename T>
+__device__ __forceinline__ void kmat_bt_term(const KmatArgs<T>& p, int64_t b, int t, T& v, T& c, T& sh, T& hsh) {
+    const int64_t o = b * p.bt_stride + t;
+    const int kind = p.terms[t].kind;
+    v = (T)p.bt_var[o];
+    const double il = p.bt_ils[o];
+    c = (T)(il * il);
+    sh = T(0);
+    hsh = T(0);
+    if (kind == GPK_K_RQ || kind == GPK_K_DELTA) {
+        const double s = p.bt_shape[o];
+        sh = (T)s;
+        if (kind == GPK_K_RQ) hsh = (T)(0.5 / s);
+    }
+}
+
+// The term source of a kernel: BT = per-batch tables, TABLE = a term-table program (else a compile-time program over NT <= 2 terms).
+// TABLE: thread 0 fills `btab`; the caller's next barrier publishes it.
+template <typename T, bool BT, bool TABLE, int NT>
+__device__ __forceinline__ auto kmat_term_source(const KmatArgs<T>& p, int64_t b, int tid, T* btab) {
+    if constexpr (!BT) {
+        return TermsArg<T>{p};
+    } else if constexpr (TABLE) {
+        for (int t = 0; t < p.nterms; ++t) {
+            T v, c, sh, hsh;
+            kmat_bt_term(p, b, t, v, c, sh, hsh);
+            if (tid == 0) {
+                btab[t] = v;
+                btab[GPK_MAX_TERMS + t] = c;
+                btab[2 * GPK_MAX_TERMS + t] = sh;
+                btab[3 * GPK_MAX_TERMS + t] = hsh;
+            }
+        }
+        return TermsLds<T>{btab};
+    } else {
+        TermsReg<T> r;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            r.v[t] = r.c[t] = r.sh[t] = r.hsh[t] = T(0);
+            if (t < NT) {
+                T v, c, sh, hsh;
+                kmat_bt_term(p, b, t, v, c, sh, hsh);
+                r.v[t] = gpk_uniform(v);
+                r.c[t] = gpk_uniform(c);
+                r.sh[t] = gpk_uniform(sh);
+                r.hsh[t] = gpk_uniform(hsh);
+            }
+        }
+        return r;
+    }
+}
 
 // SH: the term table may hold terms of the kinds with a shape parameter -- rational quadratic, Delta -- (a launch with shape
 // parameters).  A template parameter, not one more branch of the kind switch: the table program of kernels WITHOUT such a term stays
 // the code it was (the logarithm costs ~25 registers).
-template <typename T, bool SH>
-__device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
+template <typename T, bool SH, typename TS>
+__device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, const TS& ts, T r2, T dot) {
     T val = T(0);
     for (int t = 0; t < p.nterms; ++t) {
         const int kind = p.terms[t].kind;
-        const T q = r2 * p.terms[t].ils2;
+        const T q = r2 * ts.ils2(t);
         T k;
         if (kind == GPK_K_EQ) {
             k = gpk_exp<T>(T(-0.5) * q);
@@ -71,28 +172,29 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, T r2, T dot) {
             const T s = gpk_sqrtk<T>(T(5) * q);
             k = (T(1) + s + s * s * T(1.0 / 3.0)) * gpk_exp<T>(-s);
         } else if (kind == GPK_K_LINEAR) {
-            k = dot * p.terms[t].ils2;
+            k = dot * ts.ils2(t);
         } else if (SH && kind == GPK_K_RQ) {
             // (1 + u)^(-alpha), u = q / (2 alpha), as exp(-alpha log1p(u)): the exponent is <= 0 like every other on this path
-            k = gpk_exp<T>(-p.shape[t] * gpk_log1p<T>(q * p.hshape[t]));
+            k = gpk_exp<T>(-ts.shape(t) * gpk_log1p<T>(q * ts.hshape(t)));
         } else if (SH && kind == GPK_K_DELTA) {
             // 1 within epsilon (in q: the scaled squared distance), else 0 -- no transcendental; q is a sum of squared direct
             // differences, so coincident points give exactly 1; NaN inputs stay NaN like every other kind
-            k = q != q ? q : (q < p.shape[t] ? T(1) : T(0));
+            k = q != q ? q : (q < ts.shape(t) ? T(1) : T(0));
         } else {
             k = T(1);
         }
-        val += p.terms[t].variance * k;
+        val += ts.variance(t) * k;
     }
     return val;
 }
 
-template <typename T, bool DOT, int DC, bool SH>
+template <typename T, bool DOT, int DC, bool SH, bool BT>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
     constexpr int VEC = Traits<T>::VEC;
     constexpr int TN = 64 * VEC;
     __shared__ T xs[TM * DC];
+    __shared__ T btab[BT ? 4 * GPK_MAX_TERMS : 1];     // BT: the batch entry's term table
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -104,6 +206,8 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     const T* __restrict__ X = p.X + b * p.sX;
     const T* __restrict__ Y = p.Y + b * p.sY;
     T* __restrict__ out = p.out + b * p.sO;
+    const auto ts = kmat_term_source<T, BT, true, 0>(p, b, tid, btab);
+    if constexpr (BT) __syncthreads();     // (with d = 0 the chunk loop below has no barrier)
 
     const int colb = col0 + lane * VEC;   // first of this lane's VEC columns
 
@@ -157,7 +261,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             const int col = colb + v;
-            T val = eval_terms<T, SH>(p, r2[r][v], dt[r][v]);
+            T val = eval_terms<T, SH>(p, ts, r2[r][v], dt[r][v]);
             if (p.symmetric && col == row) kmat_add_diag(p, b, row, val);
             vals[v] = val;
         }
@@ -279,14 +383,14 @@ __device__ __forceinline__ double gpk_exp_neg_tab(double a, const double* tab) {
 __device__ __forceinline__ double gpk_exp_neg_t(double a, const double* tab) { return gpk_exp_neg_tab(a, tab); }
 __device__ __forceinline__ float gpk_exp_neg_t(float a, const float*) { return gpk_exp_neg(a); }
 
-template <typename T, int PROG>
-__device__ __forceinline__ T eval_prog(const KmatArgs<T>& p, T r2, T dot, const T* etab) {
-    if (PROG == PROG_GENERIC) return eval_terms<T, false>(p, r2, dot);
-    if (PROG == PROG_GENERIC_RQ) return eval_terms<T, true>(p, r2, dot);
-    const T v0 = p.terms[0].variance, c0 = p.terms[0].ils2;
+template <typename T, int PROG, typename TS>
+__device__ __forceinline__ T eval_prog(const KmatArgs<T>& p, const TS& ts, T r2, T dot, const T* etab) {
+    if (PROG == PROG_GENERIC) return eval_terms<T, false>(p, ts, r2, dot);
+    if (PROG == PROG_GENERIC_RQ) return eval_terms<T, true>(p, ts, r2, dot);
+    const T v0 = ts.variance(0), c0 = ts.ils2(0);
     if (PROG == PROG_EQ) return v0 * gpk_exp_neg_t(T(-0.5) * c0 * r2, etab);
-    if (PROG == PROG_EQ_LINEAR) return v0 * gpk_exp_neg_t(T(-0.5) * c0 * r2, etab) + p.terms[1].variance * p.terms[1].ils2 * dot;
-    if (PROG == PROG_RQ) return v0 * gpk_exp_neg_t(-p.shape[0] * gpk_log1p<T>(r2 * (c0 * p.hshape[0])), etab);    // (c0 / (2 alpha): uniform)
+    if (PROG == PROG_EQ_LINEAR) return v0 * gpk_exp_neg_t(T(-0.5) * c0 * r2, etab) + ts.variance(1) * ts.ils2(1) * dot;
+    if (PROG == PROG_RQ) return v0 * gpk_exp_neg_t(-ts.shape(0) * gpk_log1p<T>(r2 * (c0 * ts.hshape(0))), etab);    // (c0 / (2 alpha): uniform)
     // (the constants below are uniform: formed once per workgroup.  3 c0 r2 for (3 c0) r2 and v0 + v0 s + (v0 / 3) s^2 in Horner form
     // move a value by an ulp or two against the literal formula -- the price of 1 + 2 operations less per element)
     if (PROG == PROG_M12) return v0 * gpk_exp_neg_t(-gpk_sqrtk<T>(r2 * c0), etab);
@@ -298,7 +402,7 @@ __device__ __forceinline__ T eval_prog(const KmatArgs<T>& p, T r2, T dot, const 
     return fma(fma(v0 * T(1.0 / 3.0), sd, v0), sd, v0) * gpk_exp_neg_t(-sd, etab);
 }
 
-template <typename T, int PROG, bool DOT, int DC>
+template <typename T, int PROG, bool DOT, int DC, bool BT>
 __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
     constexpr int VEC = Traits<T>::VEC;
@@ -311,6 +415,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     constexpr bool ETAB = sizeof(T) == 8 && !TABLE;  // fp64: exp through the 2^(j/128) table (gpk_exp_neg_tab)
     constexpr bool PK32 = sizeof(T) == 4 && !TABLE;   // fp32: two values per instruction
     __shared__ T etab[ETAB ? 128 : 1];
+    __shared__ T btab[(BT && TABLE) ? 4 * GPK_MAX_TERMS : 1];     // BT, term-table programs: the batch entry's table
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -328,6 +433,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     const T* __restrict__ X = p.X + b * p.sX;
     const T* __restrict__ Y = p.Y + b * p.sY;
     T* __restrict__ out = p.out + b * p.sO;
+    const auto ts = kmat_term_source<T, BT, TABLE, (PROG == PROG_EQ_LINEAR ? 2 : 1)>(p, b, tid, btab);     // (TABLE: published by the barrier below)
 
     kmat_stage_band_x<T, DC>(p, X, tid, row0, xs);
     // A column tile of Y is TN points x d values, contiguous in memory when ldy == d: consecutive lanes fetch
@@ -391,8 +497,8 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         if (DOT) dot[h] = __builtin_elementwise_fma(xx, yy, dot[h]);
                     }
                 }
-                const float c0 = (float)p.terms[0].ils2, v0 = (float)p.terms[0].variance;
-                const float vl = (PROG == PROG_EQ_LINEAR) ? (float)(p.terms[1].variance * p.terms[1].ils2) : 0.f;
+                const float c0 = (float)ts.ils2(0), v0 = (float)ts.variance(0);
+                const float vl = (PROG == PROG_EQ_LINEAR) ? (float)(ts.variance(1) * ts.ils2(1)) : 0.f;
                 const gpk_f2 vv = {v0, v0};
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -403,7 +509,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         if (PROG == PROG_EQ_LINEAR) k = __builtin_elementwise_fma(dot[h], gpk_f2{vl, vl}, k);
                     } else if (PROG == PROG_RQ) {
                         // exp(-alpha log1p(u)): the logarithm has no packed form, the scaling and the exponential do
-                        const float cu = c0 * (float)p.hshape[0], na = -(float)p.shape[0];
+                        const float cu = c0 * (float)ts.hshape(0), na = -(float)ts.shape(0);
                         const gpk_f2 u = acc[h] * gpk_f2{cu, cu};
                         const gpk_f2 lg = {log1pf(u.x), log1pf(u.y)};
                         k = gpk_exp_neg_pk(lg * gpk_f2{na, na}) * vv;
@@ -436,7 +542,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         r2 += df * df;
                         if (DOT) dt += xr[j] * ya[j][v];
                     }
-                    T val = eval_prog<T, PROG>(p, r2, dt, etab);
+                    T val = eval_prog<T, PROG>(p, ts, r2, dt, etab);
                     if (has_diag && colb + v == row) kmat_add_diag(p, b, row, val);
                     vals[v] = val;
                 }
@@ -489,11 +595,49 @@ __global__ __launch_bounds__(256) void kdiag_kernel(KdiagArgs<T> p) {
     p.out[b * p.sO + i] = val;
 }
 
-}  // namespace
-
-// terms: host arrays of length nterms
+// gpk_kdiag_batch_terms: batch entry b's row of the device tables (uniform loads), derived like kmat_bt_term
 template <typename T>
-int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+__global__ __launch_bounds__(256) void kdiag_bt_kernel(KdiagArgs<T> p, const double* __restrict__ bt_var, const double* __restrict__ bt_ils,
+                                                       int64_t bt_stride) {
+    const int64_t b = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.n) return;
+    const T* x = p.X + b * p.sX + i * p.ldx;
+    T nrm = T(0);
+    for (int j = 0; j < p.d; ++j) nrm += x[j] * x[j];
+    T val = T(0);
+    for (int t = 0; t < p.nterms; ++t) {
+        const double il = bt_ils[b * bt_stride + t];
+        val += (T)bt_var[b * bt_stride + t] * (p.terms[t].kind == GPK_K_LINEAR ? nrm * (T)(il * il) : T(1));
+    }
+    p.out[b * p.sO + i] = val;
+}
+
+// The term table of a per-batch launch: the kinds alone (the values stay on the device).  GPK_OK, *shaped and *linear, or -1 for an unknown
+// kind (where `check_kinds`) or a shaped kind without a `shapes` table, -3 for a missing variance / scale table, -7 for rows that overlap.
+template <typename T>
+inline int gpk_pack_kinds(KTermT<T>* terms, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                          int64_t stride, bool check_kinds, bool* shaped, bool* linear) {
+    *shaped = *linear = false;
+    for (int t = 0; t < nterms; ++t) {
+        if (check_kinds && (kinds[t] < GPK_K_EQ || kinds[t] > GPK_K_DELTA)) return GPK_ERR_ARG(1);
+        if (kinds[t] == GPK_K_RQ || kinds[t] == GPK_K_DELTA) {
+            *shaped = true;
+            if (shapes == nullptr) return GPK_ERR_ARG(1);
+        }
+        if (kinds[t] == GPK_K_LINEAR) *linear = true;
+        terms[t].kind = kinds[t];
+        terms[t].variance = T(0);
+        terms[t].ils2 = T(0);
+    }
+    if (nterms > 0 && (variances == nullptr || inv_ls == nullptr)) return GPK_ERR_ARG(3);
+    if (stride < nterms) return GPK_ERR_ARG(7);
+    return GPK_OK;
+}
+
+// BT: variances, inv_ls, shapes are DEVICE tables [batch][nterms] of row stride bt_stride (gpk_kmat_batch_terms); else host arrays
+template <typename T, bool BT>
+int kmat_launch_any(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int64_t bt_stride,
                     const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
@@ -503,19 +647,29 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     if (n > INT32_MAX || m > INT32_MAX || batch > 65535) return GPK_ERR_ARG(6);
     if (d < 0) return GPK_ERR_ARG(13);
     bool shaped;      // some term is RQ or Delta: the term-table program that knows them (Delta has no program of its own)
-    if (const int st = gpk_check_terms(kinds, shapes, nterms, true, GPK_ERR_ARG(5), &shaped)) return st;
     constexpr int VEC = Traits<T>::VEC;
     KmatArgs<T> a;
+    a.bt_var = a.bt_ils = a.bt_shape = nullptr;
+    a.bt_stride = 0;
+    if constexpr (BT) {
+        bool linear;
+        if (const int st = gpk_pack_kinds(a.terms, kinds, variances, inv_ls, shapes, nterms, bt_stride, true, &shaped, &linear)) return st;
+        a.need_dot = linear;
+        for (int t = 0; t < GPK_MAX_TERMS; ++t) a.shape[t] = a.hshape[t] = T(0);
+        a.bt_var = variances; a.bt_ils = inv_ls; a.bt_shape = shapes; a.bt_stride = bt_stride;
+    } else {
+        if (const int st = gpk_check_terms(kinds, shapes, nterms, true, GPK_ERR_ARG(5), &shaped)) return st;
+        a.need_dot = gpk_pack_terms(a.terms, kinds, variances, inv_ls, nterms, false);
+        for (int t = 0; t < GPK_MAX_TERMS; ++t) {
+            const bool rq = t < nterms && kinds[t] == GPK_K_RQ, delta = t < nterms && kinds[t] == GPK_K_DELTA;
+            a.shape[t] = (rq || delta) ? (T)shapes[t] : T(0);
+            a.hshape[t] = rq ? (T)(0.5 / shapes[t]) : T(0);
+        }
+    }
     a.X = X; a.Y = Y; a.out = out; a.diag_vec = diag_vec;
     a.ldx = ldx; a.ldy = ldy; a.sX = sX; a.sY = sY; a.ld = ld; a.sO = sO; a.sDiag = sDiag;
     a.n = (int)n; a.m = (int)m; a.d = d;
     a.nterms = nterms;
-    a.need_dot = gpk_pack_terms(a.terms, kinds, variances, inv_ls, nterms, false);
-    for (int t = 0; t < GPK_MAX_TERMS; ++t) {
-        const bool rq = t < nterms && kinds[t] == GPK_K_RQ, delta = t < nterms && kinds[t] == GPK_K_DELTA;
-        a.shape[t] = (rq || delta) ? (T)shapes[t] : T(0);
-        a.hshape[t] = rq ? (T)(0.5 / shapes[t]) : T(0);
-    }
     a.diag_add = (T)diag_add;
     a.symmetric = symmetric; a.lower_only = lower_only; a.accumulate = accumulate;
     a.vec_ok = ((uintptr_t)out % 16 == 0) && (ld % VEC == 0) && (sO % VEC == 0);
@@ -534,7 +688,7 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
     a.ct = plan.ct; a.nbands = plan.nbands; a.compact = plan.compact;
     const dim3 grid(plan.gx, plan.gy, plan.gz);
     if (band) {
-#define GPK_BAND(PROGV, DOTV, DCV) hipLaunchKernelGGL((kmat_band_kernel<T, PROGV, DOTV, DCV>), grid, dim3(256), 0, stream, a)
+#define GPK_BAND(PROGV, DOTV, DCV) hipLaunchKernelGGL((kmat_band_kernel<T, PROGV, DOTV, DCV, BT>), grid, dim3(256), 0, stream, a)
         switch (prog) {
             case PROG_EQ: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ, false); break;
             case PROG_M12: GPK_KMAT_DC(d, GPK_BAND, PROG_M12, false); break;
@@ -553,12 +707,54 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
         GPK_CHECK_LAUNCH();
         return GPK_OK;
     }
-#define GPK_ONE_TILE(DOTV, SHV, DCV) hipLaunchKernelGGL((kmat_kernel<T, DOTV, DCV, SHV>), grid, dim3(256), 0, stream, a)
+#define GPK_ONE_TILE(DOTV, SHV, DCV) hipLaunchKernelGGL((kmat_kernel<T, DOTV, DCV, SHV, BT>), grid, dim3(256), 0, stream, a)
     if (shaped && a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, true);
     else if (shaped) GPK_KMAT_DC(d, GPK_ONE_TILE, false, true);
     else if (a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, false);
     else GPK_KMAT_DC(d, GPK_ONE_TILE, false, false);
 #undef GPK_ONE_TILE
+    GPK_CHECK_LAUNCH();
+    return GPK_OK;
+}
+
+}  // namespace
+
+// terms: host arrays of length nterms
+template <typename T>
+int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                    const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
+                    int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
+                    int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
+                    hipStream_t stream) {
+    return kmat_launch_any<T, false>(kinds, variances, inv_ls, shapes, nterms, 0, X, n, ldx, sX, Y, m, ldy, sY, d, out, ld, sO, batch,
+                                     lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
+}
+
+// kinds: host array; variances, inv_ls, shapes: device tables [batch][nterms], row stride s_terms
+template <typename T>
+int gpk_kmat_bt_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int64_t s_terms,
+                       const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
+                       int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
+                       int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
+                       hipStream_t stream) {
+    return kmat_launch_any<T, true>(kinds, variances, inv_ls, shapes, nterms, s_terms, X, n, ldx, sX, Y, m, ldy, sY, d, out, ld, sO, batch,
+                                    lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
+}
+
+template <typename T>
+int gpk_kdiag_bt_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int64_t s_terms,
+                        const T* X, int64_t n, int64_t ldx, int64_t sX, int d, T* out, int64_t sO,
+                        int64_t batch, hipStream_t stream) {
+    if (n <= 0 || batch <= 0) return GPK_OK;
+    if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
+    if (batch > 65535) return GPK_ERR_ARG(6);
+    KdiagArgs<T> a;
+    bool shaped, linear;      // (an RQ or Delta term is 1 on the diagonal whatever its shape: its table must be there, and is not read)
+    if (const int st = gpk_pack_kinds(a.terms, kinds, variances, inv_ls, shapes, nterms, s_terms, false, &shaped, &linear)) return st;
+    a.X = X; a.out = out; a.ldx = ldx; a.sX = sX; a.sO = sO;
+    a.n = (int)n; a.d = d; a.nterms = nterms;
+    dim3 grid((unsigned)gpk_cdiv(n, 256), (unsigned)batch);
+    hipLaunchKernelGGL((kdiag_bt_kernel<T>), grid, dim3(256), 0, stream, a, variances, inv_ls, s_terms);
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
@@ -587,6 +783,12 @@ int gpk_kdiag_launch(const int* kinds, const double* variances, const double* in
                                     int64_t, int64_t, int64_t, int, int, double, const T*, int64_t,   \
                                     int, hipStream_t);                                                \
     template int gpk_kdiag_launch<T>(const int*, const double*, const double*, const double*, int, const T*, int64_t, \
-                                     int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t);
+                                     int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t);            \
+    template int gpk_kmat_bt_launch<T>(const int*, const double*, const double*, const double*, int, int64_t, const T*, int64_t, \
+                                       int64_t, int64_t, const T*, int64_t, int64_t, int64_t, int, T*,   \
+                                       int64_t, int64_t, int64_t, int, int, double, const T*, int64_t,   \
+                                       int, hipStream_t);                                                \
+    template int gpk_kdiag_bt_launch<T>(const int*, const double*, const double*, const double*, int, int64_t, const T*, int64_t, \
+                                        int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t);
 GPK_INST(double)
 GPK_INST(float)

@@ -1364,6 +1364,53 @@ static std::vector<T> quarters(size_t n, int span) {
     for (auto& x : v) x = (T)((int)(rng() % (2 * span + 1)) - span) / (T)4;
     return v;
 }
+// gpk_kmat_batch_terms / gpk_kdiag_batch_terms (one term table per batch entry, on the device): entry b of ONE launch against gpk_kmat /
+// gpk_kdiag on entry b alone with row b of the tables as host arrays -- the same element program on the same numbers, so bit for bit.
+// Run under both values of knob 12: the one-tile kernel at d = 3 is a path the release library never takes.
+template <typename T>
+static void test_batch_terms() {
+    const int B = 3, n = 130, m = 97, pad = 2;
+    struct Case { const char* name; std::vector<int> kinds; };
+    const std::vector<Case> cases = {{"eq", {GPK_K_EQ}}, {"matern52", {GPK_K_MATERN52}}, {"rq", {GPK_K_RQ}}, {"eq+linear", {GPK_K_EQ, GPK_K_LINEAR}},
+                                     {"table3", {GPK_K_MATERN32, GPK_K_EQ, GPK_K_CONST}},
+                                     {"all8", {GPK_K_EQ, GPK_K_MATERN12, GPK_K_MATERN32, GPK_K_MATERN52, GPK_K_LINEAR, GPK_K_CONST, GPK_K_RQ, GPK_K_DELTA}}};
+    for (int d : {3, 9}) {
+        auto hx = randv<T>((size_t)B * n * d), hy = randv<T>((size_t)B * m * d);
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < 20 * d; ++i) hy[(size_t)b * m * d + i] = hx[(size_t)b * n * d + i];     // coincident points: the Delta term is 1 there
+        Dev<T> dX(hx.size()), dY(hy.size()), dO((size_t)B * n * m), dR((size_t)B * n * m), dOd((size_t)B * n), dRd((size_t)B * n);
+        dX.up(hx); dY.up(hy);
+        for (const Case& c : cases) {
+            const int nt = (int)c.kinds.size(), st_ = nt + pad;       // rows of the tables padded: the stride is not nterms
+            std::vector<double> var((size_t)B * st_, NAN), ils((size_t)B * st_, NAN), shp((size_t)B * st_, NAN);
+            for (int b = 0; b < B; ++b)
+                for (int t = 0; t < nt; ++t) {
+                    var[b * st_ + t] = 0.5 + 0.25 * ((b + t) % 5);
+                    ils[b * st_ + t] = 1.0 / (0.7 + 0.6 * ((b + 2 * t) % 3));
+                    shp[b * st_ + t] = c.kinds[t] == GPK_K_DELTA ? 1e-6 * (b + 1) : 0.8 + 1.1 * b;
+                }
+            Dev<double> dV(var.size()), dI(ils.size()), dS(shp.size());
+            dV.up(var); dI.up(ils); dS.up(shp);
+            int st = gpk_kmat_batch_terms(DT<T>::v, c.kinds.data(), dV.p, dI.p, dS.p, nt, st_, dX.p, n, d, (int64_t)n * d, dY.p, m, d, (int64_t)m * d, d,
+                                          dO.p, m, (int64_t)n * m, B, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+            st |= gpk_kdiag_batch_terms(DT<T>::v, c.kinds.data(), dV.p, dI.p, dS.p, nt, st_, dX.p, n, d, (int64_t)n * d, d, dOd.p, n, B, nullptr);
+            for (int b = 0; b < B; ++b) {
+                st |= gpk_kmat(DT<T>::v, c.kinds.data(), &var[b * st_], &ils[b * st_], &shp[b * st_], nt, dX.p + (size_t)b * n * d, n, d, 0,
+                               dY.p + (size_t)b * m * d, m, d, 0, d, dR.p + (size_t)b * n * m, m, 0, 1, 0, 0, 0.0, nullptr, 0, 0, nullptr);
+                st |= gpk_kdiag(DT<T>::v, c.kinds.data(), &var[b * st_], &ils[b * st_], &shp[b * st_], nt, dX.p + (size_t)b * n * d, n, d, 0, d,
+                                dRd.p + (size_t)b * n, 0, 1, nullptr);
+            }
+            HIPCHK(hipDeviceSynchronize());
+            const auto got = dO.down(), ref = dR.down(), gotd = dOd.down(), refd = dRd.down();
+            size_t bad = 0, nan = 0;
+            for (size_t i = 0; i < got.size(); ++i) { bad += memcmp(&got[i], &ref[i], sizeof(T)) != 0; nan += !std::isfinite((double)got[i]); }
+            for (size_t i = 0; i < gotd.size(); ++i) bad += memcmp(&gotd[i], &refd[i], sizeof(T)) != 0;
+            report(std::string("batch_terms ") + DT<T>::name() + " " + c.name + " d=" + std::to_string(d) + " differing elements (status " + std::to_string(st) + ")",
+                   (double)(bad + nan + (st != 0)), 0.0);
+        }
+    }
+}
+
 template <typename T>
 static void test_delta() {
     const double eps = 1e-6;
@@ -2686,6 +2733,11 @@ int main(int argc, char** argv) {
         }
         if (!strcmp(argv[i], "--diff")) {                      // only the checks of the derivative blocks (gpk_kmat_diff), both kernels
             test_diff<double>(); test_diff<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
+        if (!strcmp(argv[i], "--batch-terms")) {               // only the checks of the per-batch term tables, both kernels
+            for (int band = 1; band >= 0; --band) { gpk_tune(12, band); test_batch_terms<double>(); test_batch_terms<float>(); }
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }

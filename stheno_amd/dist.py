@@ -36,10 +36,20 @@ def _collective(group):
     return dist.is_available() and dist.is_initialized()
 
 
+def _refuse_per_batch(process):
+    """A per-batch hyper-parameter is indexed by the position in the WHOLE batch; a rank holds a shard of it."""
+    from . import kernels
+
+    if kernels.has_per_batch(getattr(process, "kernel", None)):
+        raise NotImplementedError(f"sharding a batch over ranks is not implemented with {kernels.PER_BATCH} (a rank would have to slice "
+                                  "every parameter by its shard): build the model per rank from that rank's slice of the parameters")
+
+
 def sharded_logpdf(process, x_local, noise, y_local, total, group=None):
     """Log-densities of ``total`` independent GPs, of which this rank holds the shard
     ``x_local`` (b_local, N, D) / ``y_local`` (b_local, N, 1) given by :func:`shard_bounds`.
     Returns the full ``(total,)`` vector on every rank."""
+    _refuse_per_batch(process)
     world, rank = _world(group)
     lo, hi = shard_bounds(total, world, rank)
     if x_local.shape[0] != hi - lo:
@@ -63,6 +73,7 @@ def sharded_logpdf(process, x_local, noise, y_local, total, group=None):
 
 def sharded_logpdf_sum(process, x_local, noise, y_local, group=None):
     """Sum of the log-densities over all ranks' GPs (one-scalar all-reduce)."""
+    _refuse_per_batch(process)
     s = process(x_local, noise).logpdf(y_local).sum().reshape(1)
     if _collective(group):
         dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group)

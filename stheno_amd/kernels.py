@@ -98,12 +98,47 @@ def num_elements(x):
     return x.shape[-2]
 
 
+PER_BATCH = "per-batch hyper-parameters"
+
+
+def _is_per_batch(v):
+    """A hyper-parameter given once per batch entry: a tensor of shape ``(B, 1, 1)``, ``B > 1`` -- the shape that broadcasts against a
+    ``(B, N, M)`` kernel matrix and ``(B, N, D)`` inputs.  (A 1-D tensor stays what it was: one length scale per input dimension in
+    ``stretch``, an error as a variance.)"""
+    return torch.is_tensor(v) and v.dim() == 3 and v.shape[0] > 1 and v.shape[1] == 1 and v.shape[2] == 1
+
+
+def _per_batch_size(v):
+    """``B`` of a per-batch value in either view -- ``(B, 1, 1)`` as the caller gave it, ``(B,)`` in the float view -- else None."""
+    return v.shape[0] if torch.is_tensor(v) and v.dim() in (1, 3) and v.numel() > 1 else None
+
+
+def _same_batch(a, b):
+    """Refuse to combine per-batch values of different batch sizes (torch would raise a broadcasting error, or broadcast)."""
+    na, nb = _per_batch_size(a), _per_batch_size(b)
+    if na is not None and nb is not None and na != nb:
+        raise ValueError(f"{PER_BATCH} of different batch sizes in one kernel: {na} and {nb}")
+
+
+def _times(a, b):
+    _same_batch(a, b)
+    return a * b
+
+
 def _as_float(v):
+    """The float view of a parameter: a Python double; for a per-batch parameter its values as a detached fp64 vector ``(B,)``."""
     if torch.is_tensor(v):
+        if _is_per_batch(v):
+            return v.detach().reshape(-1).to(torch.float64)
         if v.numel() != 1:
             raise ValueError("kernel hyper-parameters must be scalars")
         return float(v.detach())
     return float(v)
+
+
+def _as_factor(v):
+    """A parameter as a factor of an evaluated kernel matrix ``(..., N, M)``: a float, or the detached ``(B, 1, 1)`` values."""
+    return v.detach() if _is_per_batch(v) else _as_float(v)
 
 
 _UNSET = object()
@@ -112,7 +147,7 @@ _UNSET = object()
 def _is_vector_scale(scale):
     """One length scale per input dimension (torch tensor, NumPy array, list or tuple with more than one entry)?"""
     if torch.is_tensor(scale):
-        return scale.numel() > 1
+        return scale.numel() > 1 and not _is_per_batch(scale)
     if isinstance(scale, (list, tuple)):
         return True
     return np.ndim(scale) > 0 and np.size(scale) > 1
@@ -124,9 +159,11 @@ def _as_is(v):
 
 
 def _as_param(v):
-    """Keep scalar tensors (they may carry an autograd graph: learnable hyper-parameters),
-    turn everything else into a float."""
+    """Keep scalar tensors (they may carry an autograd graph: learnable hyper-parameters) and per-batch tensors ``(B, 1, 1)`` -- the
+    caller's object --, turn everything else into a float."""
     if torch.is_tensor(v):
+        if _is_per_batch(v):
+            return v
         if v.numel() != 1:
             raise ValueError("kernel hyper-parameters must be scalars")
         return v.reshape(())
@@ -142,7 +179,11 @@ class Kernel:
     kernels leave it at ``None`` and override ``pairwise`` / ``elwise``.  ``conv`` is applied to the node's OWN parameter before it is
     combined with its children's: ``_as_float`` for the float views (Python doubles: what the fused launches are handed),
     ``_as_is`` for the tensor views (the caller's tensors, so gradients can flow back to them).  The four public views below are
-    columns of that table; one call visits every leaf of the expression once."""
+    columns of that table; one call visits every leaf of the expression once.
+
+    A parameter given once per batch entry -- a tensor of shape ``(B, 1, 1)`` -- stays the caller's tensor in the tensor view and is
+    a detached fp64 vector ``(B,)`` in the float view; products with scalar parameters broadcast, so a table mixes both freely and
+    ``_kterms()`` hands the backends a per-batch descriptor (``ops.KTerms.batch``)."""
 
     stationary = False
 
@@ -256,6 +297,8 @@ class Kernel:
         ``k.stretch(l, 1)``, its kernel ``k.stretch(l, l)``).  The two-argument form always divides the INPUTS; the one-argument form
         of a periodic kernel hands the stretch to the kernel behind the embedding, as it always did."""
         if scale_y is not _UNSET:
+            if _is_per_batch(scale) or _is_per_batch(scale_y) or has_per_batch(self):
+                raise NotImplementedError(f"the two-argument stretch is not implemented with {PER_BATCH}")
             if _is_vector_scale(scale) or _is_vector_scale(scale_y):
                 raise NotImplementedError("the two-argument stretch takes scalars: per-dimension length scales that differ between the "
                                           "arguments are not implemented")
@@ -348,19 +391,21 @@ class RQ(_Primitive):
     stationary = True
 
     def __init__(self, alpha):
-        if torch.is_tensor(alpha):
+        if _is_per_batch(alpha):
+            self.alpha = alpha               # one alpha per batch entry: the caller's (B, 1, 1) tensor
+        elif torch.is_tensor(alpha):
             if alpha.numel() != 1:
                 raise ValueError("kernel hyper-parameters must be scalars")
             self.alpha = alpha if alpha.dim() == 0 else alpha.reshape(())
         else:
             self.alpha = float(alpha)
-        if not _as_float(self.alpha) > 0:
+        if not bool((torch.as_tensor(_as_float(self.alpha)) > 0).all()):
             raise ValueError("the shape parameter alpha of RQ must be positive")
 
     shape = property(lambda self: self.alpha)
 
     def __repr__(self):
-        return f"RQ({_as_float(self.alpha):g})"
+        return f"RQ({PER_BATCH})" if _is_per_batch(self.alpha) else f"RQ({_as_float(self.alpha):g})"
 
 
 class Delta(_Primitive):
@@ -373,6 +418,8 @@ class Delta(_Primitive):
     def __init__(self, epsilon=1e-6):
         if torch.is_tensor(epsilon) and epsilon.requires_grad:
             raise ValueError("the epsilon of Delta is not learnable (the kernel is piecewise constant in it); pass a number")
+        if _is_per_batch(epsilon):
+            raise ValueError("the epsilon of Delta is a number (a threshold shared by the batch), not one value per batch entry")
         self.epsilon = _as_float(epsilon)
         if not self.epsilon > 0:
             raise ValueError("the epsilon of Delta must be positive")
@@ -449,7 +496,7 @@ class Scaled(Kernel):
 
     def _table(self, conv):
         rows = self.k._table(conv)
-        return None if rows is None else [(kind, var * conv(self.v), s, a) for kind, var, s, a in rows]
+        return None if rows is None else [(kind, _times(var, conv(self.v)), s, a) for kind, var, s, a in rows]
 
     def input_scaled_view(self):
         v = self.k.input_scaled_view()
@@ -468,7 +515,7 @@ class Scaled(Kernel):
             if groups is not None:
                 return _sum_of_groups(groups).pairwise(x, y, **kw)
         da, dv = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
-        out = _as_float(self.v) * self.k.pairwise(x, y, **kw)
+        out = _as_factor(self.v) * self.k.pairwise(x, y, **kw)
         return _add_diag(out, da, dv) if y is None else out
 
     def elwise(self, x, y=None, **kw):
@@ -477,7 +524,7 @@ class Scaled(Kernel):
         view = self.input_scaled_view()
         if view is not None:
             return _Mapped(*view).elwise(x, y, **kw)
-        return _as_float(self.v) * self.k.elwise(x, y, **kw)
+        return _as_factor(self.v) * self.k.elwise(x, y, **kw)
 
     def __repr__(self):
         return f"{self.v} * {self.k!r}"
@@ -491,7 +538,7 @@ class Stretched(Kernel):
         self.stationary = k.stationary
 
     def _table(self, conv):
-        return [(kind, var, s * conv(self.scale), a) for kind, var, s, a in self.k._table(conv)]
+        return [(kind, var, _times(s, conv(self.scale)), a) for kind, var, s, a in self.k._table(conv)]
 
     def __repr__(self):
         return f"({self.k!r} > {self.scale})"
@@ -783,6 +830,9 @@ class InputScaled(_Mapped):
             return Kernel.stretch(self, scale, scale_y)
         if _is_vector_scale(scale):
             return InputScaled(self.k, self.scales * (scale if torch.is_tensor(scale) else torch.as_tensor(scale)).to(self.scales))
+        if _is_per_batch(scale):
+            raise NotImplementedError(f"a stretch by {PER_BATCH} of a kernel behind per-dimension length scales is not implemented: "
+                                      "stretch the kernel first, then by the vector (`k.stretch(l).stretch(vector)`)")
         return InputScaled(self.k, self.scales * _as_float(scale))
 
     def __repr__(self):
@@ -824,6 +874,24 @@ def _same_param(a, b):
     return (a is b) if (torch.is_tensor(a) or torch.is_tensor(b)) else (a == b)
 
 
+def has_per_batch(kernel, _depth=0):
+    """Does any hyper-parameter reachable from ``kernel`` come once per batch entry (a ``(B, 1, 1)`` tensor)?  What the paths that
+    do not admit such parameters ask before they refuse."""
+    if _depth > 16 or not isinstance(kernel, Kernel):
+        return False
+    rows = kernel.tensor_table()
+    if rows is not None:
+        return any(_is_per_batch(p) for row in rows for p in row[1:])
+    if isinstance(kernel, MultiOutputKernel):
+        return any(has_per_batch(kernel.kernels[p], _depth + 1) for p in kernel.pids)
+    for val in vars(kernel).values():
+        if _is_per_batch(val) or (isinstance(val, InputMap) and _is_per_batch(val.param)):
+            return True
+        if isinstance(val, Kernel) and has_per_batch(val, _depth + 1):
+            return True
+    return False
+
+
 def _merge(rows):
     """Add up the variances of rows with the same primitive, the same length scale and the same shape parameter (``p + p``
     has the kernel ``4 k``, not four terms; the fused kernels take at most 8 distinct terms)."""
@@ -831,6 +899,7 @@ def _merge(rows):
     for kind, var, scale, shp in rows:
         for i, (k2, v2, s2, a2) in enumerate(out):
             if k2 == kind and _same_param(scale, s2) and _same_param(shp, a2):
+                _same_batch(v2, var)
                 out[i] = (k2, v2 + var, s2, a2)
                 break
         else:
@@ -1100,6 +1169,8 @@ def _diff_kernel(k, a, b):
         return k
     if isinstance(k, ZeroKernel):
         return ZeroKernel()
+    if has_per_batch(k):
+        raise NotImplementedError(f"derivative kernels are not implemented with {PER_BATCH}")
     if isinstance(k, DiffKernel):
         if (a is not None and k.dim_x is not None) or (b is not None and k.dim_y is not None):
             raise NotImplementedError("second derivatives in one argument (f.diff().diff()) are not implemented: they need the third and "
@@ -1275,6 +1346,8 @@ class MultiOutputKernel(Kernel):
 
     def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None, out=None):
         kernels = self.kernels
+        if has_per_batch(self):
+            raise NotImplementedError(f"several processes observed or predicted jointly (a `MultiInput`) are not implemented with {PER_BATCH}")
         sym = y is None
         X = self._split(x)
         Y = X if sym else self._split(y)
@@ -1303,6 +1376,8 @@ class MultiOutputKernel(Kernel):
         if y is not None and y is not x:
             raise NotImplementedError("elwise is implemented for identical inputs")
         kernels = self.kernels
+        if has_per_batch(self):
+            raise NotImplementedError(f"several processes observed or predicted jointly (a `MultiInput`) are not implemented with {PER_BATCH}")
         return torch.cat([kernels[pi].elwise(xi) for pi, xi in self._split(x)], dim=-2)
 
     def __repr__(self):
@@ -1361,6 +1436,8 @@ class Mean:
     __radd__ = __add__
 
     def __mul__(self, other):
+        if _is_per_batch(other):
+            raise NotImplementedError(f"means scaled by {PER_BATCH} are not implemented")
         return ScaledMean(self, _as_float(other))
 
     __rmul__ = __mul__

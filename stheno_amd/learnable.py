@@ -154,6 +154,11 @@ def marginals(pm, kernel, x, cache):
     learnable is behind them or when the call is outside the three covered cases: the plain path then runs exactly as before."""
     if not torch.is_grad_enabled():
         return None
+    for k in (kernel, getattr(pm, "k_zi", None)):
+        if isinstance(k, _k.Kernel) and _k.has_per_batch(k) and kernel_requires_grad(k):
+            raise NotImplementedError(f"gradients of posterior means and marginal variances are not implemented with {_k.PER_BATCH}: "
+                                      "this call would return values cut off from the autograd graph -- wrap it in torch.no_grad() if "
+                                      "that is intended")
     if isinstance(kernel, _k.PosteriorKernel) or (kernel is None and pm.sparse is None):
         return _exact_marginals(pm, kernel, x, cache)
     link = pm.sparse if pm is not None else sparse_pair(kernel)
@@ -446,6 +451,11 @@ def logpdf(var, r):
         if lp is not None:
             return lp[0] if lp.shape[0] == 1 else lp
     if density_requires_grad(var.kernel, var.x, var.noise, r):
+        if isinstance(var.kernel, _k.Kernel) and _k.has_per_batch(var.kernel):
+            raise NotImplementedError(f"gradients of logpdf with {_k.PER_BATCH} are implemented for one batch of independent data sets whose "
+                                      "kernel is a sum of primitives behind ONE input map, with scalar or per-point noise; this call (sums "
+                                      "behind different maps, several processes, a posterior) would return a value cut off from the "
+                                      "autograd graph -- wrap it in torch.no_grad() if that is intended")
         raise NotImplementedError("gradients of logpdf are implemented for one process (or one batch of independent data sets) whose kernel "
                                   "is a sum of primitives with scalar or per-point noise; this call (multi-process, posterior or "
                                   "dense-noise) would return a value cut off from the autograd graph -- wrap it in torch.no_grad() "
@@ -483,6 +493,8 @@ def _joint_logpdf(var, r):
     diagonal or a block of the lower block triangle is not a sum of primitives behind input maps with scalar hyper-parameters (the
     caller then refuses)."""
     mok, x, noise_vec = var.kernel, var.x, _diagonal_noise(var)
+    if _k.has_per_batch(mok):
+        raise NotImplementedError(f"several processes observed jointly are not implemented with {_k.PER_BATCH}")
     if noise_vec is NotImplemented:
         return None
     kernels = mok.kernels
@@ -536,6 +548,8 @@ def elbo(obs, measure):
     if isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
         return None
     k = measure.kernels[p_z]
+    if _k.has_per_batch(k):
+        raise NotImplementedError(f"inducing points and the pseudo-point bound are not implemented with {_k.PER_BATCH}")
     view = k.input_scaled_view()
     if view is None or not _k._same_map(view[1], view[2]):
         return None

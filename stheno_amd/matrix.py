@@ -816,7 +816,7 @@ class KernelDense(Dense):
         tensor (its smallest entry lives on the device), dense noise.  Non-stationary terms (``Linear``) are left out of the trace:
         they add at most ``D`` large eigenvalues, the bound is a trigger for `config.refine_solves`, not a guarantee."""
         terms = self.kernel.terms() if hasattr(self.kernel, "terms") else None
-        if not terms or self.x.dim() != 2:
+        if not terms or self.x.dim() != 2 or any(torch.is_tensor(var) for _, var, _ in terms):      # (per-batch variances live on the device)
             return None
         noise = self.noise
         if noise is None or isinstance(noise, Zero):

@@ -91,6 +91,15 @@ class FDD(Normal):
         has learnable quantities (a posterior / multi-process / dense-noise case outside the differentiable paths)
         is refused, never returned silently detached."""
         posterior = not isinstance(self.p, int) and getattr(self.p.measure, "_conditioned_on", None) is not None
+        if torch.is_grad_enabled() and not isinstance(self.p, int) and _k.has_per_batch(self.p.kernel) and self._learnable(x):
+            # per-batch hyper-parameters: differentiable for ONE group of primitives behind one input map, on the batched fused path;
+            # everything else is refused here, before any launch
+            groups = _k._symmetric_groups(self.p.kernel)
+            if groups is None or len(groups) != 1:
+                raise NotImplementedError(
+                    f"gradients of a log-density with {_k.PER_BATCH} are implemented for a prior process whose kernel is a sum of "
+                    "primitives behind one input map; this one (sums behind different maps, a posterior, several processes) is not: "
+                    "wrap the call in torch.no_grad() for the value alone")
         if posterior and torch.is_grad_enabled() and self._learnable(x):
             # a posterior density under learnable quantities: the plain path would factorise the posterior covariance,
             # only for its value to be discarded -- go to the chain-rule form (two prior densities) at once

@@ -307,6 +307,8 @@ class AbstractPseudoObservations(AbstractObservations):
         be = ops.get_backend()
         p_x, x, noise_x = self.fdd.p, self.fdd._xr, self.fdd.noise
         p_z, z, noise_z = self.u.p, self.u._xr, self.u.noise
+        if any(_k.has_per_batch(measure.kernels[p]) for p in (p_z, p_x)):
+            raise NotImplementedError(f"inducing points and the pseudo-point bound are not implemented with {_k.PER_BATCH}")
 
         # (Round 5 built this cross-covariance TRANSPOSED, k(x, z), so that both operands of L_z^{-1} K_zx would be k-contiguous --
         # VERDICT r4 #7 -- and measured it on cfg5: the V GEMM 0.771 of the fp32 peak against 0.80 this way round, the step 57.7 ms

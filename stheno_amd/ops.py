@@ -35,38 +35,90 @@ _LEARNABLE_SHAPE = ("rq",)
 _SHAPE_NAME = {"rq": "alpha", "delta": "epsilon"}
 
 
+def _per_batch_value(v):
+    """A per-batch entry of a term table: a tensor with more than one element (``(B,)`` or ``(B, 1, 1)``)."""
+    return torch.is_tensor(v) and v.numel() > 1
+
+
 class KTerms:
     """A kernel as a sum of ``variance * kind(. / scale)`` terms (host-side descriptor).  ``shapes``: one entry per term, the shape
     parameter of the kinds that have one (``"rq"``: alpha > 0, ``"delta"``: epsilon > 0) and ``None`` for the others; ``self.shapes`` is ``None`` when no term
-    has one -- the library then gets a NULL ``shapes`` array."""
+    has one -- the library then gets a NULL ``shapes`` array.
+
+    Every entry is a float -- one table for the whole launch, handed to the library as host arrays -- unless some variance, scale or
+    shape is a tensor of ``B`` values: then the descriptor is PER BATCH (``self.batch == B``): such columns stay on their device
+    (``tables()``: fp64 ``(B, nterms)`` per column, floats broadcast), the values are not read on the host (so their signs are not checked:
+    a non-positive scale or alpha gives NaN in its batch entry), and the launch is ``gpk_kmat_batch_terms`` / ``gpk_kdiag_batch_terms``."""
+
+    batch = None
 
     def __init__(self, terms, shapes=None):
         terms = list(terms)
+        shapes = [None] * len(terms) if shapes is None else list(shapes)
         if len(terms) > _native.MAX_TERMS:
             raise ValueError(f"at most {_native.MAX_TERMS} kernel terms are supported")
-        self.terms = [(str(k), float(v), float(s)) for k, v, s in terms]
+        if len(shapes) != len(terms):
+            raise ValueError("one shape entry per term (None for the kinds without a shape parameter)")
+        sizes = sorted({v.numel() for row, a in zip(terms, shapes) for v in (row[1], row[2], a) if _per_batch_value(v)})
+        if sizes:
+            if len(sizes) > 1:
+                raise ValueError(f"per-batch hyper-parameters of different batch sizes in one kernel: {sizes[0]} and {sizes[1]}")
+            self.batch = sizes[0]
+        conv = (lambda v: v.detach().reshape(-1).to(torch.float64) if _per_batch_value(v) else float(v))      # noqa: E731
+        self.terms = [(str(k), conv(v), conv(s)) for k, v, s in terms]
         for k, _, s in self.terms:
             if k not in _KIND_IDS:
                 raise ValueError(f"unknown kernel kind {k!r}")
-            if not s > 0:
+            if not torch.is_tensor(s) and not s > 0:
                 raise ValueError("length scales must be positive")
-        shapes = [None] * len(self.terms) if shapes is None else list(shapes)
-        if len(shapes) != len(self.terms):
-            raise ValueError("one shape entry per term (None for the kinds without a shape parameter)")
         out = []
         for (k, _, _), a in zip(self.terms, shapes):
             if k in _SHAPED:
-                if a is None or not float(a) > 0:
+                if a is None or not (_per_batch_value(a) or float(a) > 0):
                     raise ValueError(f"a {k!r} term needs a positive shape parameter ({_SHAPE_NAME[k]}), got {a!r}")
-                out.append(float(a))
+                out.append(conv(a))
             else:
                 out.append(None)
         self.shapes = out if any(a is not None for a in out) else None
+        self._tables = self._entries = None
 
     def __len__(self):
         return len(self.terms)
 
+    def check_batch(self, size):
+        """A per-batch table serves inputs of exactly its own batch size."""
+        if self.batch is not None and self.batch != size:
+            raise ValueError(f"per-batch hyper-parameters for a batch of {self.batch} met inputs with a batch of {size}")
+
+    def tables(self, device):
+        """``(variances, inverse scales, shapes or None)`` of a per-batch descriptor: contiguous fp64 ``(B, nterms)`` tensors on
+        ``device`` (what ``gpk_kmat_batch_terms`` reads; 0 where a term has no shape)."""
+        if self._tables is None or self._tables[0].device != device:
+            def column(vals):
+                cols = [v.to(device) if torch.is_tensor(v) else torch.full((self.batch,), float(v), dtype=torch.float64, device=device) for v in vals]
+                return torch.stack(cols, dim=1).contiguous()
+            var = column([v for _, v, _ in self.terms])
+            ils = 1.0 / column([s for _, _, s in self.terms])
+            shp = None if self.shapes is None else column([0.0 if a is None else a for a in self.shapes])
+            self._tables = (var, ils, shp)
+        return self._tables
+
+    def entry(self, b):
+        """Batch entry ``b`` of a per-batch descriptor as a descriptor in floats (one device-to-host copy of the table, kept): what the
+        walks over the batch hand to the unbatched launches."""
+        if self.batch is None:
+            return self
+        if self._entries is None:
+            host = lambda v: v.tolist() if torch.is_tensor(v) else [float(v)] * self.batch      # noqa: E731
+            cols = [(k, host(v), host(s)) for k, v, s in self.terms]
+            shp = None if self.shapes is None else [None if a is None else host(a) for a in self.shapes]
+            self._entries = [KTerms([(k, v[i], s[i]) for k, v, s in cols], None if shp is None else [None if a is None else a[i] for a in shp])
+                             for i in range(self.batch)]
+        return self._entries[b]
+
     def c_arrays(self):
+        if self.batch is not None:
+            raise NotImplementedError("this launch takes one term table for the whole batch: it is not implemented with per-batch hyper-parameters")
         n = len(self.terms)
         kinds = (ctypes.c_int * max(n, 1))(*[_KIND_IDS[k] for k, _, _ in self.terms])
         var = (ctypes.c_double * max(n, 1))(*[v for _, v, _ in self.terms])
@@ -219,13 +271,29 @@ class HipBackend:
         dv = None
         if diag_vec is not None:
             dv = diag_vec.reshape(B, n).contiguous()
-        kinds, var, ils, nt = terms.c_arrays()
         tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
                 _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
                 self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
+        if terms.batch is not None:
+            # one term table per batch entry: the tables stay on the device (gpk_kmat_batch_terms); derivative blocks have no such entry
+            if entry != "gpk_kmat":
+                raise NotImplementedError("derivative kernels are not implemented with per-batch hyper-parameters")
+            terms.check_batch(B)
+            kinds, var, ils, shp, nt = self._batch_tables(terms, x3.device)
+            code = self.lib.gpk_kmat_batch_terms(_dtype_id(x3), kinds, self._ptr(var), self._ptr(ils), self._ptr(shp), nt, nt, *tail)
+            self._st(code, "gpk_kmat_batch_terms")
+            return out
+        kinds, var, ils, nt = terms.c_arrays()
         code = getattr(self.lib, entry)(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, *dims, *tail)
         self._st(code, entry)
         return out
+
+    @staticmethod
+    def _batch_tables(terms, device):
+        nt = len(terms)
+        kinds = (ctypes.c_int * max(nt, 1))(*[_KIND_IDS[k] for k, _, _ in terms.terms])
+        var, ils, shp = terms.tables(device)
+        return kinds, var, ils, shp, nt
 
     @_on_operand_device
     def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
@@ -247,6 +315,13 @@ class HipBackend:
         self._check(x3)
         B, n, d = x3.shape
         out = torch.empty(bshape + (n,), dtype=x.dtype, device=x.device)
+        if terms.batch is not None:
+            terms.check_batch(B)
+            kinds, var, ils, shp, nt = self._batch_tables(terms, x3.device)
+            code = self.lib.gpk_kdiag_batch_terms(_dtype_id(x3), kinds, self._ptr(var), self._ptr(ils), self._ptr(shp), nt, nt, self._ptr(x3), n,
+                                                  _ld(x3), _bs(x3), d, self._ptr(out), n, B, self._stream())
+            self._st(code, "gpk_kdiag_batch_terms")
+            return out
         kinds, var, ils, nt = terms.c_arrays()
         code = self.lib.gpk_kdiag(_dtype_id(x3), kinds, var, ils, terms.c_shapes(), nt, self._ptr(x3), n, _ld(x3), _bs(x3), d,
                                   self._ptr(out), n, B, self._stream())
@@ -724,7 +799,22 @@ class _HostDelta:
             out.copy_(res)
         return out
 
+    @staticmethod
+    def _batch3(terms, x):
+        """The inputs of a per-batch call as ``(B, N, D)`` (the batch sizes checked: what ``HipBackend`` does before its launch)."""
+        x3 = x if x.dim() == 3 else x.reshape((-1,) + tuple(x.shape[-2:])) if x.dim() > 3 else x.unsqueeze(0)
+        terms.check_batch(x3.shape[0])
+        return x3
+
     def kmat(self, terms, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        if terms.batch is not None:
+            # one term table per batch entry: the scalar form, entry by entry
+            x3 = self._batch3(terms, x)
+            y3 = None if y is None else self._batch3(terms, y)
+            dv = None if diag_vec is None else diag_vec.reshape(x3.shape[0], -1)
+            res = torch.stack([self.kmat(terms.entry(b), x3[b], None if y3 is None else y3[b], lower=lower, diag_add=diag_add,
+                                         diag_vec=None if dv is None else dv[b]) for b in range(x3.shape[0])])
+            return self._deliver(res.reshape(tuple(x.shape[:-2]) + tuple(res.shape[-2:])), out, accumulate)
         rest, delta, _ = self._split(terms)
         if not delta:
             return self._inner.kmat(terms, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out, accumulate=accumulate)
@@ -886,6 +976,9 @@ class _HostDelta:
         return self._t(S, x), (self._t(gradx, x) if want_gradx else None)
 
     def kdiag(self, terms, x):
+        if terms.batch is not None:
+            x3 = self._batch3(terms, x)
+            return torch.stack([self.kdiag(terms.entry(b), x3[b]) for b in range(x3.shape[0])]).reshape(tuple(x.shape[:-1]))
         rest, delta, _ = self._split(terms)
         if not delta:
             return self._inner.kdiag(terms, x)
