@@ -60,7 +60,8 @@ extern "C" {
 #define GPK_DIAG_BLOCK 128 /* order of the diagonal blocks whose inverses gpk_potrf leaves in `dinv` */
 
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
- * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms. */
+ * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms.
+ * 108: gpk_kmat_vjp_dense_batch, gpk_kmat_vjp_dense_batch_grid. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -449,6 +450,29 @@ int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, con
                        const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream);
+
+/* The same reduction for a BATCH of independent problems under ONE term table (gradients through batched posterior means and marginal
+ * variances under shared hyper-parameters): entry e reads x + e sx, y + e sy, g + e sg, colscale + e s_cs, w + e s_w, b + e s_b
+ * (batch strides in elements, offsets in 64 bits) and is reduced by the kernel of gpk_kmat_vjp_dense, the batch being the third grid
+ * dimension -- gpk_kmat_vjp_dense is the batch = 1 call of this entry and writes the same bits.  A batch stride of 0 is legal for every
+ * input: sx = 0 shares one data set among the entries, sg = 0 with ldg = 0 is an all-zero cotangent operand of one row (a loss that
+ * reaches the kernel matrix through w b^T only).  Outputs are packed per entry, to be summed by the caller as for the unbatched entry:
+ *   partial [batch][rowtiles * nchunks][NS * GPK_MAX_TERMS + 1],   colsum [batch][rowtiles][m]  (nullable),
+ *   gradx   [batch][nchunks][n][d]  (nullable; d <= 8),
+ * rowtiles and nchunks from gpk_kmat_vjp_dense_batch_grid: row tiles as for the unbatched entry, and
+ *   nchunks = clamp(cdiv(2048, rowtiles * batch), 1, column tiles)      (evened out over the column tiles),
+ * so the launch aims at the ~2048 workgroups the unbatched grid aims at; with many entries a workgroup walks a whole row of column
+ * tiles, its gradx accumulators in registers, and nchunks = 1.  Deterministic (no atomics).
+ * Returns the codes of gpk_kmat_vjp_dense for the arguments the two share -- 0 at once for n or m <= 0; -5 nterms outside
+ * 0 .. GPK_MAX_TERMS; -1 an unknown kind or missing `shapes`; -4 an RQ alpha <= 0; -5 a Delta epsilon <= 0; -7 n or m above 2^31 - 1;
+ * -17 exactly one of w, b given; -12 gradx != NULL with d > 8; -9 more than 65535 column chunks -- and -28 for batch > 65535 (the
+ * grid's limit).  batch <= 0 is an empty problem: 0, behind those checks.  gpk_kmat_vjp_dense_batch_grid: -4 for a NULL output. */
+int gpk_kmat_vjp_dense_batch_grid(int64_t n, int64_t m, int64_t batch, int64_t* rowtiles, int64_t* nchunks);
+int gpk_kmat_vjp_dense_batch(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                             const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy, int64_t sy, int d,
+                             const void* g, int64_t ldg, int64_t sg, const void* colscale, int64_t s_cs,
+                             const void* w, int64_t s_w, const void* b, int64_t s_b,
+                             void* partial, void* colsum, void* gradx, int64_t batch, void* stream);
 
 /* VJP of a derivative block: `g` (n x m, ldg, unit inner stride) is the explicit cotangent of the block gpk_kmat_diff writes for the
  * same (dim_x, dim_y) -- gradients of a posterior through the covariance of a process with its derivative and of two derivatives.

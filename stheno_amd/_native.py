@@ -131,6 +131,13 @@ SIGNATURES = {
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr,
          _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr],
     ),
+    # (a batch under one term table: a batch stride behind each input's leading dimension; batch in front of the stream)
+    "gpk_kmat_vjp_dense_batch_grid": (_c_int, [_c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "gpk_kmat_vjp_dense_batch": (
+        _c_int,
+        [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr,
+         _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr],
+    ),
     "gpk_kmat_diff_vjp": (
         _c_int,
         [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_int, _c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_int,

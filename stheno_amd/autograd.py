@@ -21,7 +21,8 @@ the reductions against it run once per group, on that group's term table and map
 torch, which carries it through the map to its parameter and to ``x``.  One group is the plain case: the same launches as ever.
 
 The posterior marginals (``post(xs).mean`` / ``.var_diag`` / ``.marginals()`` / ``.marginal_credible_bounds()``) have three functions
-further down: ``_PosteriorMarginals`` (an exact posterior of one process predicted from its own observations), ``_BlockPosteriorMarginals``
+further down: ``_PosteriorMarginals`` (an exact posterior of one process predicted from its own observations; a batch of them under
+shared hyper-parameters: ``_BatchedPosteriorMarginals``, every reduction one ``gpk_kmat_vjp_dense_batch`` launch), ``_BlockPosteriorMarginals``
 (one exact conditioning step ACROSS processes: a component of a sum, several observed processes, derivatives -- the blocks are sums of
 groups ``s D^(a, b) k_g(u_g(x), u_g(y))``, ``learnable._block_groups``, and a derivative group's cotangent is reduced by
 ``gpk_kmat_diff_vjp``) and ``_SparsePosteriorMarginals`` (pseudo-point posteriors).  Each runs the plain path as its forward, so the
@@ -713,6 +714,104 @@ class _PosteriorMarginals(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------
+# The same for a BATCH of independent exact posteriors under SHARED hyper-parameters: x (B, N, D), xs (B, N*, D), r (B, N, 1), noise
+# (B, N) -- a held-out predictive loss over B tasks, B acquisition ascents at once.  The forward is the plain batched path as it is; the
+# backward is the algebra above for all entries at once, on the batched factor: one batched back-substitution for B = L^{-T} V (or, for
+# a loss of the mean only, one single-column one for beta), and every reduction against a kernel matrix one launch of
+# gpk_kmat_vjp_dense_batch over all entries -- on (x, xs) with the rank-one part in w / b and 2 gs in colscale, on (xs, x) over the
+# explicit transpose for d/dxs, and on (x, x) over the explicit symmetric cotangent of K,
+#     G = -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T)
+# (one batched lower GEMM, gpk_symmetrize, and the rank-two part as a GEMM of contraction length 2), whose diagonal is d/dnoise and
+# whose input gradient counts twice.  The launch gives the sums per entry; the parameters are shared, so their gradients come from the
+# sum over the batch.  The number of backend calls does not depend on B.
+# ---------------------------------------------------------------------------------------------
+class _BatchedPosteriorMarginals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, noise_vec, run, layout, *tensors):
+        """As ``_PosteriorMarginals.forward``, every tensor with a leading batch dimension: ``run()`` -> ``(chol, w, v, mu, s)`` with the
+        batched factor, ``w`` (B, N, 1), ``v`` (B, N, N*), ``mu`` / ``s`` (B, N*); per group ``x`` (B, N, D_g) / ``xs`` (B, N*, D_g)."""
+        chol, w, v, mu, s = run()
+        ctx.groups = _split_groups(layout, tensors, 2)
+        ctx.chol, ctx.w, ctx.v = chol, w, v
+        ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
+        ctx.set_materialize_grads(False)
+        if mu is None:
+            mu = torch.zeros_like(s)
+        return mu, s
+
+    @staticmethod
+    def backward(ctx, g_mu, g_s):
+        be = ops.get_backend()
+        groups, chol, v = ctx.groups, ctx.chol, ctx.v
+        ng = len(groups)
+        x0, xs0 = groups[0].inputs
+        (nb, n), ns = x0.shape[:2], xs0.shape[1]
+        dt, dev = x0.dtype, x0.device
+        need_x = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
+        need_xs = [ctx.needs_input_grad[5 + 2 * i] for i in range(ng)]
+        gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
+        gs = g_s.to(dt).contiguous() if g_s is not None else None
+        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
+            gs = None
+        if gm is None and gs is None:
+            return (None,) * (4 + 2 * ng + sum(len(grp.meta) for grp in groups))
+        for grp, nx, nxs in zip(groups, need_x, need_xs):
+            if nx or nxs:
+                check_input_dims(grp.inputs[0])
+
+        def zeros(rows, cols):
+            return torch.zeros((1, 1, cols), dtype=dt, device=dev).expand(nb, rows, cols)
+
+        alpha = chol.solve_t(ctx.w)[..., 0] if gm is not None else None            # K^{-1} r   (B, N)
+        bm = beta = None
+        if gs is not None:
+            bm = chol.solve_t_(be.copy(v))                                          # B = L^{-T} V: ONE batched back-substitution
+            if gm is not None:
+                beta = be.gemv(bm, gm[..., None])[..., 0]
+        else:
+            beta = chol.solve_t(be.gemv(v, gm[..., None]))[..., 0]
+        # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs), the same for every group
+        cs = 2.0 * gs if gs is not None else None
+        S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
+        g_t = None
+        for i, grp in enumerate(groups):
+            terms, (x, xs) = grp.terms, grp.inputs
+            S[i], _, grad_x[i] = be.kmat_vjp_dense_batch(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
+                                                         want_gradx=need_x[i])
+            if need_xs[i]:
+                if g_t is None:
+                    if bm is not None:
+                        g_t = be.scale_cols_(be.copy(bm), cs).transpose(-1, -2).contiguous()     # (B, N*, N): 2 diag(gs) B^T, explicit
+                    else:
+                        g_t = zeros(ns, n)
+                _, _, grad_xs[i] = be.kmat_vjp_dense_batch(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
+        del g_t
+        # through K: the explicit symmetric cotangent, once
+        if bm is not None:
+            bs = be.scale_cols_(be.copy(bm), gs)
+            G = be.symmetrize_(be.gemm(bs, bm, a_kmajor=True, b_kmajor=True, alpha=-1.0, lower_only=True))
+            del bs, bm
+        else:
+            G = torch.zeros((nb, n, n), dtype=dt, device=dev)
+        if gm is not None:
+            be.gemm(torch.stack([beta, alpha], dim=-1), torch.stack([alpha, beta], dim=-1), a_kmajor=True, b_kmajor=True, alpha=-0.5,
+                    beta=1.0, out=G)
+        for i, grp in enumerate(groups):
+            u = grp.inputs[0]
+            S_k, _, gx = be.kmat_vjp_dense_batch(grp.terms, u, u, G, want_gradx=need_x[i])
+            S[i] = S[i] + S_k
+            if need_x[i]:
+                grad_x[i] = grad_x[i] + 2.0 * gx                       # (both arguments of k(x, x) move with x)
+        grads = []
+        for grp, S_g in zip(groups, S):
+            grads += _param_grads(grp.kinds, grp.values, S_g.sum(0), grp.meta)      # (shared by the batch)
+        grad_r = beta[..., None] if (beta is not None and ctx.needs_input_grad[0]) else None
+        grad_noise = torch.diagonal(G, dim1=-2, dim2=-1).clone() if (ctx.has_noise and ctx.needs_input_grad[1]) else None
+        inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
+        return (grad_r, grad_noise, None, None, *inputs, *grads)
+
+
+# ---------------------------------------------------------------------------------------------
 # Posterior marginals ACROSS processes: one exact conditioning step on one or several observation sets, any one process p of the
 # measure predicted at xs -- a component of a sum, another observed process, a derivative (`post(f.diff())`), or values predicted from
 # observed slopes.  K is the block matrix of the observed processes (MultiOutputKernel), C = K(x_obs, xs) the stacked cross-covariances
@@ -973,6 +1072,8 @@ def sparse_posterior_marginals(kernel, x, z, xs, r, noise_vec, method, run):
 
 def posterior_marginals(groups, r, noise_vec, run):
     """Differentiable ``(mu, s)`` of ``_PosteriorMarginals``; ``groups`` = ``[(k_g, x_g, xs_g)]``, every ``k_g`` a sum of primitives
-    evaluated on ``x_g`` / ``xs_g`` (already behind the group's input map, so torch carries the map's parameter)."""
+    evaluated on ``x_g`` / ``xs_g`` (already behind the group's input map, so torch carries the map's parameter).  Batched inputs
+    (B, N, D) / (B, N*, D), shared hyper-parameters: ``_BatchedPosteriorMarginals``."""
     layout, params = _pack_groups([kern for kern, _, _ in groups])
-    return _PosteriorMarginals.apply(r, noise_vec, run, layout, *[t for _, x, xs in groups for t in (x, xs)], *params)
+    fn = _BatchedPosteriorMarginals if groups[0][1].dim() == 3 else _PosteriorMarginals
+    return fn.apply(r, noise_vec, run, layout, *[t for _, x, xs in groups for t in (x, xs)], *params)

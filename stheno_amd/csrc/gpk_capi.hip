@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 107; }
+int gpk_version(void) { return 108; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -279,17 +279,33 @@ int gpk_kmat_vjp(int dtype, const int* kinds, const double* inv_ls, const double
 
 int gpk_kmat_vjp_dense_grid(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks) {
     if (rowtiles == nullptr || nchunks == nullptr) return GPK_ERR_ARG(3);
-    gpk_kmat_vjp_dense_grid_impl(n, m, rowtiles, nchunks, nullptr);
+    gpk_kmat_vjp_dense_grid_impl(n, m, 1, rowtiles, nchunks, nullptr);
     return GPK_OK;
+}
+
+int gpk_kmat_vjp_dense_batch_grid(int64_t n, int64_t m, int64_t batch, int64_t* rowtiles, int64_t* nchunks) {
+    if (rowtiles == nullptr || nchunks == nullptr) return GPK_ERR_ARG(4);
+    gpk_kmat_vjp_dense_grid_impl(n, m, batch, rowtiles, nchunks, nullptr);
+    return GPK_OK;
+}
+
+int gpk_kmat_vjp_dense_batch(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                             const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy, int64_t sy, int d,
+                             const void* g, int64_t ldg, int64_t sg, const void* colscale, int64_t s_cs,
+                             const void* w, int64_t s_w, const void* b, int64_t s_b,
+                             void* partial, void* colsum, void* gradx, int64_t batch, void* stream) {
+    D1(dtype, gpk_kmat_vjp_dense_batch_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, sx, (const T*)y, m, ldy, sy,
+                                                 d, (const T*)g, ldg, sg, (const T*)colscale, s_cs, (const T*)w, s_w, (const T*)b, s_b,
+                                                 (T*)partial, (T*)colsum, (T*)gradx, batch, (hipStream_t)stream));
 }
 
 int gpk_kmat_vjp_dense(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                        const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                        const void* g, int64_t ldg, const void* colscale, const void* w, const void* b,
                        void* partial, void* colsum, void* gradx, void* stream) {
-    D1(dtype, gpk_kmat_vjp_dense_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, (const T*)y, m,
-                                           ldy, d, (const T*)g, ldg, (const T*)colscale, (const T*)w,
-                                           (const T*)b, (T*)partial, (T*)colsum, (T*)gradx, (hipStream_t)stream));
+    D1(dtype, gpk_kmat_vjp_dense_batch_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, 0, (const T*)y, m, ldy, 0,
+                                                 d, (const T*)g, ldg, 0, (const T*)colscale, 0, (const T*)w, 0, (const T*)b, 0,
+                                                 (T*)partial, (T*)colsum, (T*)gradx, 1, (hipStream_t)stream));
 }
 
 int gpk_kmat_diff_vjp(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,

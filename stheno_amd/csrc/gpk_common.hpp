@@ -304,12 +304,14 @@ template <typename T>
 int gpk_kmat_vjp_launch(const int* kinds, const double* inv_ls, const double* shapes, int nterms, const T* X, int64_t n, int64_t ldx,
                         int d, const T* Kinv, int64_t ldk, const T* A, int C, int64_t lda, const double* g,
                         T* partial, T* diag_g, hipStream_t stream);
-void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk);
+void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t batch, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk);
+// the one launcher of the explicit-cotangent VJP: `batch` entries under one term table (batch strides in elements, 0 = shared);
+// gpk_kmat_vjp_dense is its batch = 1 call
 template <typename T>
-int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                              const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                              const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                              T* colsum, T* gradx, hipStream_t stream);
+int gpk_kmat_vjp_dense_batch_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                                    const T* X, int64_t n, int64_t ldx, int64_t sx, const T* Y, int64_t m, int64_t ldy, int64_t sy, int d,
+                                    const T* G, int64_t ldg, int64_t sg, const T* colscale, int64_t s_cs, const T* w, int64_t s_w,
+                                    const T* b, int64_t s_b, T* partial, T* colsum, T* gradx, int64_t batch, hipStream_t stream);
 // VJP of a derivative block (gpk_kmat_diff_vjp in gpk.h; gpk_vjp.hip): the grid and partial rows of gpk_kmat_vjp_dense_launch; status
 // codes are that entry's argument positions
 template <typename T>

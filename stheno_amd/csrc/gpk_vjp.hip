@@ -246,6 +246,11 @@ __global__ __launch_bounds__(256) void kmat_vjp_kernel(VjpArgs<T> p) {
 // A workgroup owns a 64-row tile and a CHUNK of 64-column tiles: the d/dX accumulators stay in
 // registers across the chunk, column sums leave per row tile; partial results are summed by the
 // caller (deterministic, no atomics).  HBM-bound: G is read exactly once.
+// A BATCH of independent problems under one term table is the third grid dimension: entry e = blockIdx.z reads its inputs at
+// e * (batch stride) elements (64-bit offsets; a stride of 0 shares one operand among the entries) and writes its own packed block of
+// every output.  The column chunks shrink in number as the batch grows (gpk_kmat_vjp_dense_grid_impl), so with many entries a
+// workgroup walks a whole row of column tiles with its d/dX accumulators in registers.  batch = 1 is the unbatched launch: entry 0,
+// offsets 0, the grid and every summation order it has always had.
 constexpr int DT = 64;
 
 template <typename T>
@@ -253,6 +258,7 @@ struct VjpDenseArgs {
     const T *X, *Y, *G, *cs, *w, *b;
     T *partial, *colsum, *gradx;
     int64_t ldx, ldy, ldg;
+    int64_t sx, sy, sg, scs, sw, sb;      // batch strides of the inputs, in elements (0: shared by the entries)
     int n, m, d, nterms, tiles_per_chunk, ctiles, nchunks;
     int kind[GPK_MAX_TERMS];
     T ils2[GPK_MAX_TERMS], var[GPK_MAX_TERMS];
@@ -303,6 +309,16 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
     const int rt = blockIdx.x, chunk = blockIdx.y;
     const int i0 = rt * DT;
     const bool want_gx = p.gradx != nullptr;     // launcher guarantees d <= VDC then
+    // this batch entry's operands (uniform: scalar registers); its outputs are packed [entry][...] with the unbatched shapes
+    const int64_t e = blockIdx.z;
+    const T* const X = p.X + e * p.sx;
+    const T* const Y = p.Y + e * p.sy;
+    const T* const G = p.G + e * p.sg;
+    const T* const cs = p.cs != nullptr ? p.cs + e * p.scs : nullptr;
+    const T* const w = p.w != nullptr ? p.w + e * p.sw : nullptr;
+    const T* const b = p.b != nullptr ? p.b + e * p.sb : nullptr;
+    T* const colsum = p.colsum != nullptr ? p.colsum + e * gridDim.x * p.m : nullptr;
+    T* const gradx = want_gx ? p.gradx + e * p.nchunks * p.n * p.d : nullptr;
 
     T s1[GPK_MAX_TERMS], s2[GPK_MAX_TERMS], s3[SH ? GPK_MAX_TERMS : 1];
 #pragma unroll
@@ -320,7 +336,7 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int i = i0 + ty * 4 + u;
-        wi[u] = (p.w != nullptr && i < p.n) ? p.w[i] : T(0);
+        wi[u] = (w != nullptr && i < p.n) ? w[i] : T(0);
     }
 
     const int ct_end = min((chunk + 1) * p.tiles_per_chunk, p.ctiles);
@@ -335,8 +351,8 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
             __syncthreads();
             for (int idx = tid; idx < DT * VDC; idx += 256) {
                 const int r = idx / VDC, c = idx % VDC;
-                xi[idx] = (i0 + r < p.n && dc + c < p.d) ? p.X[(int64_t)(i0 + r) * p.ldx + dc + c] : T(0);
-                yj[idx] = (j0 + r < p.m && dc + c < p.d) ? p.Y[(int64_t)(j0 + r) * p.ldy + dc + c] : T(0);
+                xi[idx] = (i0 + r < p.n && dc + c < p.d) ? X[(int64_t)(i0 + r) * p.ldx + dc + c] : T(0);
+                yj[idx] = (j0 + r < p.m && dc + c < p.d) ? Y[(int64_t)(j0 + r) * p.ldy + dc + c] : T(0);
             }
             __syncthreads();
 #pragma unroll
@@ -362,13 +378,13 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const int j = j0 + tx * 4 + v;
-            const T csj = (p.cs != nullptr && j < p.m) ? p.cs[j] : T(1);
-            const T bj = (p.b != nullptr && j < p.m) ? p.b[j] : T(0);
+            const T csj = (cs != nullptr && j < p.m) ? cs[j] : T(1);
+            const T bj = (b != nullptr && j < p.m) ? b[j] : T(0);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = i0 + ty * 4 + u;
                 T g = T(0);
-                if (i < p.n && j < p.m) g = p.G[(int64_t)i * p.ldg + j] * csj + wi[u] * bj;
+                if (i < p.n && j < p.m) g = G[(int64_t)i * p.ldg + j] * csj + wi[u] * bj;
                 Ge[u][v] = g;
             }
         }
@@ -409,7 +425,7 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
             }
         }
         // column sums over this row tile: 4 rows per thread, then the 16 ty-groups through LDS
-        if (p.colsum != nullptr) {
+        if (colsum != nullptr) {
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 T acc = T(0);
@@ -422,7 +438,7 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
                 T acc = T(0);
 #pragma unroll
                 for (int g = 0; g < 16; ++g) acc += csred[g * DT + tid];
-                if (j0 + tid < p.m) p.colsum[(int64_t)rt * p.m + j0 + tid] = acc;
+                if (j0 + tid < p.m) colsum[(int64_t)rt * p.m + j0 + tid] = acc;
             }
         }
         // d/dx_i: sum_j Ge [ cS (x_i - y_j) + cL y_j ]     (xi / yj still hold the only d-chunk)
@@ -448,7 +464,7 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
     }
 
     // per-term sums of the whole workgroup
-    T* out = p.partial + ((int64_t)rt * p.nchunks + chunk) * (NS * GPK_MAX_TERMS + 1);
+    T* out = p.partial + ((e * gridDim.x + rt) * p.nchunks + chunk) * (NS * GPK_MAX_TERMS + 1);
 #pragma unroll
     for (int t = 0; t < GPK_MAX_TERMS; ++t) {
 #pragma unroll
@@ -483,7 +499,7 @@ __global__ __launch_bounds__(256) void kmat_vjp_dense_kernel(VjpDenseArgs<T> p) 
 #pragma unroll
                 for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
                 const int i = i0 + ty * 4 + u;
-                if (tx == 0 && i < p.n && c < p.d) p.gradx[((int64_t)chunk * p.n + i) * p.d + c] = v;
+                if (tx == 0 && i < p.n && c < p.d) gradx[((int64_t)chunk * p.n + i) * p.d + c] = v;
             }
     }
 }
@@ -501,9 +517,11 @@ void vjp_pack_terms(const int* kinds, const double* variances, const double* inv
 
 }  // namespace
 
-void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk) {
+// Row tiles, column chunks and column tiles per chunk of a launch over `batch` entries: the chunks aim at ~2048 workgroups in all,
+// nchunks = clamp(cdiv(2048, rowtiles * batch), 1, column tiles), evened out over the column tiles.  batch = 1: the unbatched rule.
+void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t batch, int64_t* rowtiles, int64_t* nchunks, int64_t* tiles_per_chunk) {
     const int64_t rt = gpk_cdiv(n > 0 ? n : 1, DT), ct = gpk_cdiv(m > 0 ? m : 1, DT);
-    int64_t nc = gpk_cdiv(2048, rt);
+    int64_t nc = gpk_cdiv(2048, rt * (batch > 0 ? batch : 1));
     if (nc > ct) nc = ct;
     if (nc < 1) nc = 1;
     const int64_t tpc = gpk_cdiv(ct, nc);
@@ -512,12 +530,13 @@ void gpk_kmat_vjp_dense_grid_impl(int64_t n, int64_t m, int64_t* rowtiles, int64
     if (tiles_per_chunk) *tiles_per_chunk = tpc;
 }
 
-// SH = some term is RQ or Delta: the instantiation that reads `shapes` for them and writes the 3-wide partial rows
+// SH = some term is RQ or Delta: the instantiation that reads `shapes` for them and writes the 3-wide partial rows.  The one launcher
+// of kmat_vjp_dense_kernel: gpk_kmat_vjp_dense is its batch = 1 call (batch strides 0).  Status codes: include/gpk.h.
 template <typename T>
-int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
-                              const T* X, int64_t n, int64_t ldx, const T* Y, int64_t m, int64_t ldy, int d,
-                              const T* G, int64_t ldg, const T* colscale, const T* w, const T* b, T* partial,
-                              T* colsum, T* gradx, hipStream_t stream) {
+int gpk_kmat_vjp_dense_batch_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                                    const T* X, int64_t n, int64_t ldx, int64_t sx, const T* Y, int64_t m, int64_t ldy, int64_t sy, int d,
+                                    const T* G, int64_t ldg, int64_t sg, const T* colscale, int64_t s_cs, const T* w, int64_t s_w,
+                                    const T* b, int64_t s_b, T* partial, T* colsum, T* gradx, int64_t batch, hipStream_t stream) {
     if (n <= 0 || m <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(5);
     bool shaped;
@@ -525,31 +544,35 @@ int gpk_kmat_vjp_dense_launch(const int* kinds, const double* variances, const d
     if (n > INT32_MAX || m > INT32_MAX) return GPK_ERR_ARG(7);
     if ((w == nullptr) != (b == nullptr)) return GPK_ERR_ARG(17);
     if (gradx != nullptr && d > VDC) return GPK_ERR_ARG(12);     // d/dX is implemented for d <= 8
+    if (batch > 65535) return GPK_ERR_ARG(28);                   // (the grid's third dimension)
+    if (batch <= 0) return GPK_OK;
     VjpDenseArgs<T> a;
     a.X = X; a.Y = Y; a.G = G; a.cs = colscale; a.w = w; a.b = b;
     a.partial = partial; a.colsum = colsum; a.gradx = gradx;
     a.ldx = ldx; a.ldy = ldy; a.ldg = ldg;
+    a.sx = sx; a.sy = sy; a.sg = sg; a.scs = s_cs; a.sw = s_w; a.sb = s_b;
     a.n = (int)n; a.m = (int)m; a.d = d; a.nterms = nterms;
     int64_t rt, nc, tpc;
-    gpk_kmat_vjp_dense_grid_impl(n, m, &rt, &nc, &tpc);
+    gpk_kmat_vjp_dense_grid_impl(n, m, batch, &rt, &nc, &tpc);
     a.tiles_per_chunk = (int)tpc; a.nchunks = (int)nc; a.ctiles = (int)gpk_cdiv(m, DT);
     vjp_pack_terms<T>(kinds, variances, inv_ls, shapes, nterms, a.kind, a.ils2, a.var, a.shape);
     if (nc > 65535) return GPK_ERR_ARG(9);
+    const dim3 grid((unsigned)rt, (unsigned)nc, (unsigned)batch);
     if (shaped)
-        hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, true>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, true>), grid, dim3(256), 0, stream, a);
     else
-        hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, false>), dim3((unsigned)rt, (unsigned)nc), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL((kmat_vjp_dense_kernel<T, false>), grid, dim3(256), 0, stream, a);
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
-template int gpk_kmat_vjp_dense_launch<double>(const int*, const double*, const double*, const double*, int, const double*, int64_t,
-                                               int64_t, const double*, int64_t, int64_t, int, const double*, int64_t,
-                                               const double*, const double*, const double*, double*, double*,
-                                               double*, hipStream_t);
-template int gpk_kmat_vjp_dense_launch<float>(const int*, const double*, const double*, const double*, int, const float*, int64_t,
-                                              int64_t, const float*, int64_t, int64_t, int, const float*, int64_t,
-                                              const float*, const float*, const float*, float*, float*, float*,
-                                              hipStream_t);
+template int gpk_kmat_vjp_dense_batch_launch<double>(const int*, const double*, const double*, const double*, int, const double*, int64_t,
+                                                     int64_t, int64_t, const double*, int64_t, int64_t, int64_t, int, const double*,
+                                                     int64_t, int64_t, const double*, int64_t, const double*, int64_t, const double*,
+                                                     int64_t, double*, double*, double*, int64_t, hipStream_t);
+template int gpk_kmat_vjp_dense_batch_launch<float>(const int*, const double*, const double*, const double*, int, const float*, int64_t,
+                                                    int64_t, int64_t, const float*, int64_t, int64_t, int64_t, int, const float*, int64_t,
+                                                    int64_t, const float*, int64_t, const float*, int64_t, const float*, int64_t, float*,
+                                                    float*, float*, int64_t, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // VJP of a DERIVATIVE block (gpk_kmat_diff_vjp in gpk.h): the explicit cotangent g (n x m) of the block gpk_kmat_diff writes for the
@@ -873,7 +896,7 @@ int gpk_kmat_diff_vjp_launch(const int* kinds, const double* variances, const do
     const int mode = dim_y < 0 ? DMODE_DX : dim_x < 0 ? DMODE_DY : DMODE_DXY;
     if (gradx != nullptr && (mode == DMODE_DXY || d > VDC)) return GPK_ERR_ARG(19);     // d/dX: the one-sided modes, d <= 8
     int64_t rt, nc, tpc;
-    gpk_kmat_vjp_dense_grid_impl(n, m, &rt, &nc, &tpc);
+    gpk_kmat_vjp_dense_grid_impl(n, m, 1, &rt, &nc, &tpc);
     if (nc > 65535) return GPK_ERR_ARG(13);
     if (n <= 0 || m <= 0) return GPK_OK;
     VjpDiffArgs<T> a;

@@ -1650,6 +1650,16 @@ def _cross(cache, k, z, x):
     return cache[key][0]
 
 
+def note_built_from(mat, kernel, x, noise):
+    """``mat`` -- the materialised ``kernel(x) + noise`` of a BATCH under a sum of terms behind different input maps, which has no fused
+    build with the noise on the diagonal -- with ``(kernel, x, noise)`` noted on it (``built_from``): the values are the ones it has
+    always had; the differentiable path of the batched posterior marginals (``learnable._exact_marginals``) reads the note to know
+    whose matrix it is.  Anything else is handed back untouched."""
+    if torch.is_tensor(x) and x.dim() == 3 and isinstance(kernel, Kernel) and hasattr(mat, "chol") and _map_groups(kernel) is not None:
+        mat.built_from = (kernel, x, noise)
+    return mat
+
+
 class WhitenedT:
     """``k(x, z) L^{-T}`` (ns, n): the TRANSPOSE of the whitened cross-covariance ``L^{-1} k(z, x)`` -- what the factorisation with
     rows under the matrix leaves behind (``KernelDense.chol_with_rows``).  The consumers below take either form."""

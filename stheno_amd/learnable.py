@@ -82,13 +82,13 @@ def _diagonal_noise(K):
     return noise_vec
 
 
-def _residual_in_graph(pm, z):
-    """``(True, r)``: the residual ``r = y - m_z(z)`` (N, 1) of the posterior mean ``pm``, inside the graph (None without a mean);
-    ``(False, None)`` when it is not one column."""
+def _residual_in_graph(pm, z, batched=False):
+    """``(True, r)``: the residual ``r = y - m_z(z)`` (N, 1) -- ``batched``: (B, N, 1) -- of the posterior mean ``pm``, inside the graph
+    (None without a mean); ``(False, None)`` when it is not one column."""
     if pm is None:
         return True, None
     y, r = pm._residual()
-    if r.dim() != 2 or r.shape[-1] != 1:
+    if r.dim() != (3 if batched else 2) or r.shape[-1] != 1 or (batched and tuple(r.shape[:2]) != tuple(z.shape[:2])):
         return False, None
     if pm._r_detached and not r.requires_grad:        # (formed under no_grad: form it again inside the graph)
         r = y - pm.m_z(z)
@@ -191,25 +191,36 @@ def _exact_marginals(pm, pk, x, cache):
     """An EXACT posterior of one process predicted from its own observations, through ``autograd._PosteriorMarginals``.  Anything else
     behind an exact conditioning -- a component of a sum, several observed processes, derivatives -- is the block path's
     (``_block_marginals``), which answers None itself where it does not apply: pseudo-point posteriors, chained conditioning, batched
-    inputs, a block that is no sum of groups of primitives behind input maps, dense noise."""
+    inputs, a block that is no sum of groups of primitives behind input maps, dense noise.  BATCHED inputs -- ``x`` and the observed
+    inputs (B, ., D) with one batch size, scalar or (B, N) noise, hyper-parameters shared by the batch -- are the same case through
+    ``autograd._BatchedPosteriorMarginals``; per-batch hyper-parameters were refused by the caller, without a gradient they stay the
+    plain path's."""
     src = pm if pm is not None else pk
     if not getattr(src, "exact", False):
         return None
     K_z, k, z = src.K_z, src.k_zi, src.z
     if pk is not None and not (pk.exact and pk.K_z is K_z and pk.z is z and pk.k_zi is k and pk.k_zj is k and pk.k_ij is k):
         return _block_marginals(pm, pk, x, cache)
-    if not isinstance(K_z, KernelDense) or K_z.kernel is not k:
+    noted = getattr(K_z, "built_from", None)       # (a batch under a sum behind different maps: materialised, `kernels.note_built_from`)
+    if noted is not None and not isinstance(K_z, KernelDense) and noted[0] is k and noted[1] is z and torch.is_tensor(z) and z.dim() == 3:
+        observed = KernelDense(*noted)             # (never built: asked for its noise only)
+    else:
+        observed = K_z
+    if not isinstance(observed, KernelDense) or observed.kernel is not k:
         return _block_marginals(pm, pk, x, cache)
-    if not (torch.is_tensor(x) and torch.is_tensor(z) and x.dim() == 2 and z.dim() == 2 and x.shape[-1] == z.shape[-1]
+    if not (torch.is_tensor(x) and torch.is_tensor(z) and x.dim() == z.dim() and x.dim() in (2, 3) and x.shape[-1] == z.shape[-1]
             and x.dtype == z.dtype and x.device == z.device):
         return None
-    noise_vec = _diagonal_noise(K_z)
-    if noise_vec is NotImplemented:
+    batched = x.dim() == 3     # B independent posteriors under shared hyper-parameters: autograd._BatchedPosteriorMarginals
+    if batched and (x.shape[0] != z.shape[0] or _k.has_per_batch(k)):
+        return None
+    noise_vec = observed.differentiable_noise() if batched else _diagonal_noise(K_z)
+    if noise_vec is NotImplemented or (batched and noise_vec is not None and tuple(noise_vec.shape) != tuple(z.shape[:2])):
         return None
     groups = _k._symmetric_groups(k)        # terms behind the same input map: one group is the plain case
     if groups is None or not all(kern.tensor_terms() for kern, _, _ in groups):
-        return _block_marginals(pm, pk, x, cache)
-    ok, r = _residual_in_graph(pm, z)
+        return None if batched else _block_marginals(pm, pk, x, cache)
+    ok, r = _residual_in_graph(pm, z, batched)
     if not ok:
         return None
     if not (kernel_requires_grad(k) or x.requires_grad or z.requires_grad

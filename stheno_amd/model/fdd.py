@@ -80,7 +80,7 @@ class FDD(Normal):
                 return KernelDense(k, xr, nz)      # K + noise fused, factorised in place (a derivative kernel: one gpk_kmat_diff launch)
             if torch.is_tensor(xr) and xr.dim() == 2 and _k._map_groups(k) is not None:
                 return KernelDense(k, xr, nz)      # terms behind different input maps: one launch per group into the same buffer
-            return k(xr) + nz
+            return _k.note_built_from(k(xr) + nz, k, xr, nz)
 
         Normal.__init__(self, lambda: p.mean(xr), var, var_diag=var_diag, mean_var=mean_var,
                         mean_var_diag=mean_var_diag)

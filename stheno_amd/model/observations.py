@@ -110,7 +110,7 @@ def _kernel_matrix(kernel, x, noise, round_once=False):
         return KernelDense(kernel, x, noise)
     if torch.is_tensor(x) and x.dim() == 2 and _k._map_groups(kernel) is not None:
         return KernelDense(kernel, x, noise)       # (terms behind different input maps: built group by group into one buffer)
-    return kernel(x) + noise
+    return _k.note_built_from(kernel(x) + noise, kernel, x, noise)
 
 
 class AbstractObservations:

@@ -664,6 +664,55 @@ class HipBackend:
                 gradx.sum(0) if want_gradx else None)
 
     @_on_operand_device
+    def kmat_vjp_dense_batch(self, terms, x, y, g, colscale=None, w=None, b=None, want_colsum=False, want_gradx=False):
+        """``kmat_vjp_dense`` for a batch of independent problems under ONE term table, in one launch (``gpk_kmat_vjp_dense_batch``):
+        ``x`` (B, n, d), ``y`` (B, m, d), ``g`` (B, n, m) with unit inner stride, ``colscale`` (B, m), ``w`` (B, n), ``b`` (B, m).
+        Expanded (zero-stride) views pass through without a copy: shared inputs, the all-zero cotangent operand.  Returns PER ENTRY
+        ``(S (B, nt, 2 or 3), colsum (B, m) or None, gradx (B, n, d) or None)``: the sum over the batch, for a parameter the entries
+        share, is the caller's.  A per-batch term table is refused (``KTerms.c_arrays``)."""
+        self._check(x, y, g, colscale, w, b)
+        kinds, var, ils, nt = terms.c_arrays()
+        if x.dim() != 3 or y.dim() != 3 or g.dim() != 3:
+            raise ValueError("batched operands are (B, n, d), (B, m, d) and (B, n, m)")
+        B, n, d = x.shape
+        m = y.shape[1]
+        if y.shape[0] != B or y.shape[2] != d or tuple(g.shape) != (B, n, m) or (m > 1 and g.stride(2) != 1):
+            raise ValueError("cotangent must be a (B, n, m) tensor with unit inner stride over (B, n, d) and (B, m, d) inputs")
+
+        def rows(t):          # (B, r, c) with unit inner stride; a zero batch stride stays
+            return t if (t.stride(2) == 1 or t.shape[2] == 1) and (t.stride(1) >= t.shape[2] or t.shape[1] == 1) else t.contiguous()
+
+        def vec(t, size):     # (B, size) with unit inner stride
+            if t is None:
+                return None, 0
+            if tuple(t.shape) != (B, size):
+                raise ValueError(f"expected a ({B}, {size}) operand, got {tuple(t.shape)}")
+            t = t if (t.stride(1) == 1 or size == 1) else t.contiguous()
+            return t, (t.stride(0) if B > 1 else 0)
+
+        x, y = rows(x), rows(y)
+        cs, s_cs = vec(colscale, m)
+        w, s_w = vec(w, n)
+        b, s_b = vec(b, m)
+        rt, nc = ctypes.c_int64(), ctypes.c_int64()
+        self._st(self.lib.gpk_kmat_vjp_dense_batch_grid(n, m, B, ctypes.byref(rt), ctypes.byref(nc)), "gpk_kmat_vjp_dense_batch_grid")
+        rt, nc = rt.value, nc.value
+        ns = 2 if terms.shapes is None else 3
+        width = ns * _native.MAX_TERMS + 1
+        partial = torch.zeros((B, rt * nc, width), dtype=x.dtype, device=x.device)
+        colsum = torch.zeros((B, rt, m), dtype=x.dtype, device=x.device) if want_colsum else None
+        gradx = torch.zeros((B, nc, n, d), dtype=x.dtype, device=x.device) if want_gradx else None
+        bs = lambda t: t.stride(0) if B > 1 else 0      # noqa: E731
+        code = self.lib.gpk_kmat_vjp_dense_batch(
+            _dtype_id(x), kinds, var, ils, terms.c_shapes(), nt, self._ptr(x), n, x.stride(1), bs(x), self._ptr(y), m, y.stride(1), bs(y), d,
+            self._ptr(g), g.stride(1), bs(g), self._ptr(cs), s_cs, self._ptr(w), s_w, self._ptr(b), s_b,
+            self._ptr(partial), self._ptr(colsum), self._ptr(gradx), B, self._stream())
+        self._st(code, "gpk_kmat_vjp_dense_batch")
+        tot = partial.sum(1)
+        return (tot[:, : ns * nt].reshape(B, nt, ns), colsum.sum(1) if want_colsum else None,
+                (gradx[:, 0] if nc == 1 else gradx.sum(1)) if want_gradx else None)
+
+    @_on_operand_device
     def kmat_diff_vjp(self, terms, x, y, dim_x, dim_y, g, want_gradx=False):
         """Sums over the explicit cotangent ``g`` (n, m) of the derivative block ``kmat_diff(terms, x, y, dim_x, dim_y)``, which is never
         formed (``gpk_kmat_diff_vjp``): returns ``(S, gradx)`` with ``S[t] = (sum g beta_t, sum g c dbeta_t/dc[, sum g dbeta_t/dalpha_t])``
