@@ -56,6 +56,7 @@ extern "C" {
 #define GPK_GEMM_TRI_K 2
 #define GPK_GEMM_TRI_K_LOWER 4
 #define GPK_GEMM_TRI_K_LOWER_B 8
+/* bit 4 (16), no name: the in-place panel solve of gpk_potrf -- B (n <= 128 rows, k-major) is lower triangular from column 0 and the multiply-adds right of its diagonal are skipped per 16-column fragment */
 
 #define GPK_DIAG_BLOCK 128 /* order of the diagonal blocks whose inverses gpk_potrf leaves in `dinv` */
 

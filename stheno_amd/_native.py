@@ -20,6 +20,12 @@ K_EQ, K_MATERN12, K_MATERN32, K_MATERN52, K_LINEAR, K_CONST, K_RQ, K_DELTA = ran
 MAX_TERMS = 8
 DIAG_BLOCK = 128
 
+class gpk_update_t(ctypes.Structure):
+    """One segment of ``gpk_gemm_update2`` (``include/gpk.h``)."""
+    _fields_ = [("m", _c_i64), ("n", _c_i64), ("k", _c_i64), ("a", _c_ptr), ("lda", _c_i64), ("b", _c_ptr), ("ldb", _c_i64),
+                ("cin", _c_ptr), ("ldcin", _c_i64), ("c", _c_ptr), ("ldc", _c_i64), ("lower_only", _c_int)]
+
+
 #: name -> (restype, argtypes); mirrors include/gpk.h declaration by declaration.
 SIGNATURES = {
     "gpk_version": (_c_int, []),

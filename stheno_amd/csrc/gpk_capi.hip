@@ -18,7 +18,7 @@
 
 template <typename T>
 static int update2(const gpk_update_t* upd, int nupd, double alpha, void* ctrl, int reserve, hipStream_t stream) {
-    if (upd == nullptr || nupd < 1 || nupd > 2) return GPK_ERR_ARG(3);
+    if (upd == nullptr || nupd < 1 || nupd > 2) return GPK_ERR_ARG(2);      // (the launcher's own code for a bad segment count; 3 is alpha = 0)
     GpkSeg<T> seg[2];
     for (int i = 0; i < nupd; ++i)
         seg[i] = GpkSeg<T>{upd[i].m, upd[i].n, upd[i].k, (const T*)upd[i].a, upd[i].lda, (const T*)upd[i].b, upd[i].ldb,

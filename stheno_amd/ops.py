@@ -499,11 +499,12 @@ class HipBackend:
 
     @_on_operand_device
     def gemm(self, a, b, *, a_kmajor=True, b_kmajor=True, alpha=1.0, beta=0.0, out=None, lower_only=False,
-             tri_k=False, tri_k_lower=False):
+             tri_k=False, tri_k_lower=False, tri_k_lower_b=False, panel_solve=False):
         """``out[m, n] = alpha * sum_k a(m, k) b(n, k) + beta * out``.
 
         ``a_kmajor``: ``a`` is stored (M, K); otherwise (K, M).  ``b_kmajor``: ``b`` is stored
-        (N, K); otherwise (K, N)."""
+        (N, K); otherwise (K, N).  ``tri_k`` / ``tri_k_lower`` / ``tri_k_lower_b``: the ``GPK_GEMM_TRI_K*`` flags of ``include/gpk.h``
+        (the operands vanish where the k loop is cut short); ``panel_solve``: flag bit 16, the in-place panel solve of the Cholesky."""
         a3, bshape = _as3(a)
         b3, _ = _as3(b)
         self._check(a3, b3, out)
@@ -519,15 +520,20 @@ class HipBackend:
         o3, _ = _as3_out(out)
         code = self.lib.gpk_gemm(_dtype_id(a3), int(a_kmajor), int(b_kmajor), M, N, K, float(alpha), self._ptr(a3),
                                  _ld(a3), _bs(a3), self._ptr(b3), _ld(b3), _bs(b3), float(beta), self._ptr(o3),
-                                 _ld(o3), _bs(o3), B, int(lower_only) | (2 if tri_k else 0) | (4 if tri_k_lower else 0),
-                                 self._stream())
+                                 _ld(o3), _bs(o3), B, int(lower_only) | (2 if tri_k else 0) | (4 if tri_k_lower else 0)
+                                 | (8 if tri_k_lower_b else 0) | (16 if panel_solve else 0), self._stream())
         self._st(code, "gpk_gemm")
         return out
 
     @_on_operand_device
-    def gemm_colscale(self, a, b, colscale=None, *, want_colss=False, a_kmajor=True, b_kmajor=True, tri_k_lower=False):
+    def gemm_colscale(self, a, b, colscale=None, *, want_colss=False, a_kmajor=True, b_kmajor=True, tri_k_lower=False, alpha=1.0,
+                      flags=0, out=None, colss_rows=None):
         """``out[m, n] = sum_k a(m, k) b(n, k) * colscale[n]`` (unbatched) and, with ``want_colss``, the column sums of squares of the
-        UNSCALED product -- both in the epilogue of the one GEMM (``gpk_gemm_colscale``).  Returns ``(out, colss or None)``."""
+        UNSCALED product -- both in the epilogue of the one GEMM (``gpk_gemm_colscale``).  Returns ``(out, colss or None)``.
+
+        ``alpha`` scales the product, ``flags`` are or-ed into the library's flag word, ``out`` receives the product (unit inner stride)
+        and ``colss_rows``, a ``(gpk_gemm_colss_rows(M), N)`` view with unit inner stride, receives the per-slab partial sums, which are
+        then returned as they are instead of their sum."""
         M, K = (a.shape[0], a.shape[1]) if a_kmajor else (a.shape[1], a.shape[0])
         N, K2 = (b.shape[0], b.shape[1]) if b_kmajor else (b.shape[1], b.shape[0])
         if a.dim() != 2 or b.dim() != 2 or K != K2:
@@ -535,20 +541,56 @@ class HipBackend:
         a3, _ = _as3(a)
         b3, _ = _as3(b)
         self._check(a3, b3, None)
-        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
-        part = None
-        if want_colss:
+        if out is None:
+            out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+        self._check(out, colss_rows)
+        part = colss_rows
+        if want_colss and part is None:
             part = torch.empty((int(self.lib.gpk_gemm_colss_rows(M)), N), dtype=a.dtype, device=a.device)
         if colscale is not None:
             colscale = colscale.to(dtype=a.dtype).contiguous()
             if colscale.shape != (N,):
                 raise ValueError("colscale must have one entry per column")
-        code = self.lib.gpk_gemm_colscale(_dtype_id(a3), int(a_kmajor), int(b_kmajor), M, N, K, 1.0, self._ptr(a3), _ld(a3), self._ptr(b3),
-                                          _ld(b3), self._ptr(out), N, 4 if tri_k_lower else 0,
+        code = self.lib.gpk_gemm_colscale(_dtype_id(a3), int(a_kmajor), int(b_kmajor), M, N, K, float(alpha), self._ptr(a3), _ld(a3), self._ptr(b3),
+                                          _ld(b3), self._ptr(out), _ld(out.unsqueeze(0)), (4 if tri_k_lower else 0) | int(flags),
                                           self._ptr(colscale) if colscale is not None else None,
-                                          self._ptr(part) if part is not None else None, N, self._stream())
+                                          self._ptr(part) if part is not None else None,
+                                          N if colss_rows is None else colss_rows.stride(0), self._stream())
         self._st(code, "gpk_gemm_colscale")
+        if colss_rows is not None:
+            return out, colss_rows
         return out, (part.sum(0) if part is not None else None)       # (64 x N partial sums: a statistics buffer, added up by torch)
+
+    @_on_operand_device
+    def gemm_update2(self, updates, alpha, reserve_cus=False, ctrl=None):
+        """Up to two rank-k updates ``c = cin + alpha * a b^T`` in one persistent launch (``gpk_gemm_update2``).  ``updates``: dicts with
+        the matrices ``a`` (m, k), ``b`` (n, k), ``c`` (m, n), optionally ``cin`` (default: ``c``, in place) and ``lower_only``; unit inner
+        strides.  ``ctrl``: 256 bytes of device scratch (allocated when not given; the call zeroes it)."""
+        ts = [t for u in updates for t in (u["a"], u["b"], u["c"], u.get("cin"))]
+        self._check(*ts)
+        first = updates[0]["c"] if updates else None
+        if ctrl is None and first is not None:
+            ctrl = torch.empty((64,), dtype=torch.int32, device=first.device)
+        arr = (_native.gpk_update_t * max(len(updates), 1))()
+        for i, u in enumerate(updates):
+            a, b, c = u["a"], u["b"], u["c"]
+            cin = u.get("cin")
+            cin = c if cin is None else cin
+            for t in (a, b, c, cin):
+                if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+                    raise ValueError("gemm_update2 takes matrices with a unit inner stride")
+            m, k = a.shape
+            n = b.shape[0]
+            if b.shape[1] != k or tuple(c.shape) != (m, n) or tuple(cin.shape) != (m, n):
+                raise ValueError("gemm_update2: shapes do not match")
+            ld = lambda t: _ld(t.unsqueeze(0))      # noqa: E731
+            arr[i] = _native.gpk_update_t(m, n, k, a.data_ptr(), ld(a), b.data_ptr(), ld(b), cin.data_ptr(), ld(cin), c.data_ptr(), ld(c),
+                                          int(bool(u.get("lower_only", False))))
+        dt = _dtype_id(first) if first is not None else _native.GPK_F64
+        cp = ctypes.c_void_p(ctrl) if isinstance(ctrl, int) else self._ptr(ctrl)      # (an integer: a raw address, 0 = NULL)
+        code = self.lib.gpk_gemm_update2(dt, arr, len(updates), float(alpha), cp, int(bool(reserve_cus)), self._stream())
+        self._st(code, "gpk_gemm_update2")
+        return [u["c"] for u in updates]
 
     @_on_operand_device
     def gemv(self, a, x, *, alpha=1.0, beta=0.0, out=None):
