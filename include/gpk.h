@@ -62,7 +62,8 @@ extern "C" {
 
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
  * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms.
- * 108: gpk_kmat_vjp_dense_batch, gpk_kmat_vjp_dense_batch_grid. */
+ * 108: gpk_kmat_vjp_dense_batch, gpk_kmat_vjp_dense_batch_grid.
+ * 109: gpk_kmat_scaled. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -99,6 +100,35 @@ int gpk_kmat(int dtype, const int* kinds, const double* variances, const double*
              int64_t sy, int d, void* out, int64_t ld, int64_t so, int64_t batch, int lower_only,
              int symmetric, double diag_add, const void* diag_vec, int64_t s_diag, int accumulate,
              void* stream);
+
+/* gpk_kmat with a ROW FACTOR and a COLUMN FACTOR applied at the store:
+ *   out[b][i][j] (+)= row_scale[b * s_rs + i] * col_scale[b * s_cs + j] * sum_t variances[t] * kappa_kinds[t](x[b]_i, y[b]_j)
+ * and, on i == j of a symmetric launch, + diag_add + diag_vec[i], UNSCALED, as in gpk_kmat.  The kernel of a process times a function,
+ * fn(x) k(x, y) fn(y), and its one-sided cross-kernels: replaces mlkernels `k * TensorProductKernel(fn)` behind `GP.__mul__`,
+ * stheno/model/measure.py:242-251.  A sum  fn k_a fn + k_b  is one gpk_kmat launch and one accumulating launch of this entry into the same
+ * buffer: no n x m temporary for the scaled summand.
+ *   row_scale: n values per batch entry, col_scale: m values; DEVICE pointers, unit stride, the launch's dtype.  s_rs, s_cs: batch strides in
+ *   elements; 0 shares one vector among the entries.  Either pointer may be NULL: all ones, no multiplication.  With both NULL the entry
+ *   IS gpk_kmat (the unscaled kernels: gpk_kmat's bits).
+ *   Every other argument is gpk_kmat's, with gpk_kmat's meaning, checks and return codes.  gpk_kmat's codes (-1, -4, -5, -6, -13) stand
+ *   for arguments in front of the four new ones, so none of them shifts; the scales have no code of their own (they cannot be checked
+ *   on the host).  An empty problem (n, m or batch <= 0) returns 0.
+ *   Value contract (csrc/selftest.cpp `--scaled`, tests/test_kmat_scaled_gpu.py):
+ *    - the launch takes the program and the launch plan gpk_kmat takes for the same arguments -- the single-kind EQ / Matern / RQ
+ *      programs, EQ + Linear, the generic and the shaped term table, the packed fp32 path, the fp64 table exponential, the row-band walk
+ *      for d <= 8, the one-tile kernel beyond, the compact lower-triangle grid -- so with p the value gpk_kmat computes, an element is
+ *      fl(fl(p * rs_i) * cs_j): the bits of the two multiplications applied to gpk_kmat's output.  A missing scale skips its multiplication;
+ *    - the diagonal addition and the accumulate follow as in gpk_kmat; their add may fuse with the last multiplication (one rounding
+ *      instead of two);
+ *    - a NaN scale gives NaN in its row or column only; a zero scale gives exact zeros where p is finite.
+ *   rs of a row is wave-uniform (the row-band kernel stages a band's 32 values in LDS beside its x rows, the one-tile kernel loads it as
+ *   a uniform value), cs of a lane's columns is one small load per column tile, fetched with the next tile's y values.  There is no
+ *   per-batch-term-table form. */
+int gpk_kmat_scaled(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                    const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy, int64_t sy, int d,
+                    const void* row_scale, int64_t s_rs, const void* col_scale, int64_t s_cs,
+                    void* out, int64_t ld, int64_t so, int64_t batch, int lower_only, int symmetric,
+                    double diag_add, const void* diag_vec, int64_t s_diag, int accumulate, void* stream);
 
 /* Derivative blocks of the kernel matrix: dim_x >= 0 differentiates w.r.t. x[:, dim_x], dim_y >= 0 w.r.t. y[:, dim_y]; -1: not.
  * At least one of them is >= 0 (both -1: the argument error for dim_x -- gpk_kmat is the call for that).

@@ -6,7 +6,7 @@ API surface for that path (``stheno/__init__.py:1-28``)."""
 from . import B  # noqa: F401
 from .kernels import (  # noqa: F401
     EQ, RQ, Delta, DiffKernel, DiffMean, Exp, Kernel, Linear, Matern12, Matern32, Matern52, OneKernel, OneMean, Periodic, PosteriorKernel,
-    PosteriorMean, SubspaceKernel, ZeroKernel, ZeroMean,
+    PosteriorMean, ScaleFn, SubspaceKernel, ZeroKernel, ZeroMean,
 )
 from .lazy import LazyMatrix, LazyVector  # noqa: F401
 from .matrix import Dense, Diagonal, Zero, deferred_checks  # noqa: F401

@@ -40,6 +40,13 @@ SIGNATURES = {
          _c_i64, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
          _c_ptr],
     ),
+    # (row_scale, s_rs, col_scale, s_cs between d and out; everything else as gpk_kmat)
+    "gpk_kmat_scaled": (
+        _c_int,
+        [_c_int, _p_int, _p_dbl, _p_dbl, _p_dbl, _c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64,
+         _c_i64, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_dbl, _c_ptr, _c_i64, _c_int,
+         _c_ptr],
+    ),
     # (dim_x, dim_y between nterms and x; everything from x on as gpk_kmat)
     "gpk_kmat_diff": (
         _c_int,

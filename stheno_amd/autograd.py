@@ -308,6 +308,81 @@ class _GPLogpdf(torch.autograd.Function):
         return (grad_r, grad_noise, grad_nm, None, *grad_us, *grads)
 
 
+class _GPLogpdfScaled(torch.autograd.Function):
+    """``_GPLogpdf`` for a kernel with function-scaled groups, ``K = sum_g diag(s_g) k_g(u_g) diag(s_g)`` (a group without a function:
+    ``s_g`` absent) -- the kernel of ``(1 + a) * net + b``.  ``s_g = fn(x)`` is formed in torch by the caller and is an input here, so the
+    graph carries the gradient on into the function's parameters."""
+
+    @staticmethod
+    def forward(ctx, r, noise_vec, layout, scaled, *tensors):
+        """``scaled``: one bool per group; ``tensors`` = the groups' inputs ``u_g`` (n, D_g), then one scale ``s_g`` (n,) per scaled
+        group, then the parameters group after group (``_pack``).  Returns (C,)."""
+        be = ops.get_backend()
+        ng = len(layout)
+        ns = sum(scaled)
+        groups = _split_groups(layout, tensors[:ng] + tensors[ng + ns:])
+        it = iter(tensors[ng: ng + ns])
+        scales = [next(it).detach() if sc else None for sc in scaled]
+        n, C = r.shape
+        k = None
+        for grp, s in zip(groups, scales):
+            # the first group writes the lower triangle with the (unscaled) diagonal additions, the others add to it
+            kw = dict(lower=True, diag_add=config.epsilon, diag_vec=noise_vec) if k is None else dict(lower=True, out=k, accumulate=True)
+            if s is None:
+                k = be.kmat(grp.terms, grp.inputs[0], None, **kw)
+            else:
+                k = be.kmat_scaled(grp.terms, grp.inputs[0], None, s, s, **kw)
+        chol = Chol.factor_(k)
+        w = chol.solve(r)
+        _, ss = be.colreduce(w, want_ss=True)
+        out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
+        ctx.chol, ctx.w, ctx.groups, ctx.scales, ctx.has_noise = chol, w, groups, scales, noise_vec is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        be = ops.get_backend()
+        chol, w, groups, scales = ctx.chol, ctx.w, ctx.groups, ctx.scales
+        n, C = w.shape
+        ng, ns = len(groups), sum(s is not None for s in scales)
+        if C > 8:
+            raise NotImplementedError("backward through logpdf supports at most 8 columns of y")
+        if any(ctx.needs_input_grad[4: 4 + ng]):
+            raise NotImplementedError("gradients with respect to the inputs of a function-scaled kernel are not implemented")
+        g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
+        _, kinv, alpha = _inverse_parts(be, chol, w)
+        G = _cotangent(be, kinv, alpha, g)                       # explicit: a scaled group has no implicit form
+        diag_g = torch.diagonal(G).clone()
+        grads, grad_s, pos = [], [], 4 + ng
+        for grp, s in zip(groups, scales):
+            u = grp.inputs[0]
+            if s is None:
+                S_g, _, _ = be.kmat_vjp_dense(grp.terms, u, u, G)
+            else:
+                # d/d theta of sum_ij G_ij s_i s_j k_ij: the row factor in the cotangent G_r = diag(s) G, the column factor as `colscale`
+                Gr = G * s[:, None]
+                S_g, _, _ = be.kmat_vjp_dense(grp.terms, u, u, Gr, colscale=s)
+                gs = None
+                if ctx.needs_input_grad[pos]:
+                    # d/ds_j = 2 sum_i s_i G_ij k_ij (G and K are symmetric): the column sums of G_r . K -- never a scaled sum divided
+                    # by s_j, which may vanish
+                    _, colsum, _ = be.kmat_vjp_dense(grp.terms, u, u, Gr, want_colsum=True)
+                    gs = 2.0 * colsum
+                grad_s.append(gs)
+                pos += 1
+            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
+        grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype))
+        return (grad_r, diag_g if ctx.has_noise else None, None, None, *([None] * ng), *grad_s, *grads)
+
+
+def gp_logpdf_scaled(groups, noise_vec, r):
+    """Differentiable log-density of ``r`` under ``N(0, sum_g diag(s_g) k_g(u_g) diag(s_g) + diag(noise_vec) + eps I)``; ``groups`` =
+    ``[(k_g, u_g, s_g)]`` with ``s_g`` (n,) a torch expression in the graph, or None for a group without a function.  Unbatched."""
+    layout, params = _pack_groups([kern for kern, _, _ in groups])
+    scaled = tuple(s is not None for _, _, s in groups)
+    return _GPLogpdfScaled.apply(r, noise_vec, layout, scaled, *[u for _, u, _ in groups], *[s for _, _, s in groups if s is not None], *params)
+
+
 class _GPLogpdfBatched(torch.autograd.Function):
     """The same for stheno's batched computation (``README.md:744-766``): ``x`` (B, N, D), ``r`` (B, N, 1), optional
     per-point noise (B, N), hyper-parameters SHARED by the B independent GPs -- learning over a batch of data sets

@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 108; }
+int gpk_version(void) { return 109; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -52,6 +52,16 @@ int gpk_kmat(int dtype, const int* kinds, const double* variances, const double*
     D1(dtype, gpk_kmat_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, sx, (const T*)y, m,
                                  ldy, sy, d, (T*)out, ld, so, batch, lower_only, symmetric, diag_add,
                                  (const T*)diag_vec, s_diag, accumulate, (hipStream_t)stream));
+}
+
+int gpk_kmat_scaled(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                    const void* x, int64_t n, int64_t ldx, int64_t sx, const void* y, int64_t m, int64_t ldy, int64_t sy, int d,
+                    const void* row_scale, int64_t s_rs, const void* col_scale, int64_t s_cs,
+                    void* out, int64_t ld, int64_t so, int64_t batch, int lower_only, int symmetric,
+                    double diag_add, const void* diag_vec, int64_t s_diag, int accumulate, void* stream) {
+    D1(dtype, gpk_kmat_scaled_launch<T>(kinds, variances, inv_ls, shapes, nterms, (const T*)x, n, ldx, sx, (const T*)y, m,
+                                        ldy, sy, d, (const T*)row_scale, s_rs, (const T*)col_scale, s_cs, (T*)out, ld, so, batch,
+                                        lower_only, symmetric, diag_add, (const T*)diag_vec, s_diag, accumulate, (hipStream_t)stream));
 }
 
 int gpk_kmat_diff(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,

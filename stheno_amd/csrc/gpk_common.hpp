@@ -258,6 +258,13 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
                     hipStream_t stream);
+// the same with a row and a column factor at the store (gpk_kmat_scaled in gpk.h): rs, s_rs, cs, s_cs behind d
+template <typename T>
+int gpk_kmat_scaled_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                           const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
+                           int64_t sY, int d, const T* rs, int64_t s_rs, const T* cs, int64_t s_cs, T* out, int64_t ld, int64_t sO,
+                           int64_t batch, int lower_only, int symmetric, double diag_add, const T* diag_vec, int64_t sDiag,
+                           int accumulate, hipStream_t stream);
 // derivative blocks of the kernel matrix (gpk_kmat_diff in gpk.h; gpk_kdiff.hip): status codes are that entry's argument positions
 template <typename T>
 int gpk_kmat_diff_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,

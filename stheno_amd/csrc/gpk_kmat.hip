@@ -57,6 +57,11 @@ struct KmatArgs {
     const double* bt_ils;
     const double* bt_shape;
     int64_t bt_stride;
+    // row and column factors (gpk_kmat_scaled; the SC instantiations alone read them): rs[b * s_rs + i], cs[b * s_cs + j], either may be
+    // null (all ones).  Behind everything else once more.
+    const T* rs;
+    const T* cs;
+    int64_t s_rs, s_cs;
 };
 
 // Where a kernel program reads the parameters of its terms (the KINDS are always the launch's own: p.terms[t].kind).
@@ -94,6 +99,18 @@ __device__ __forceinline__ double gpk_uniform(double x) {
     const uint64_t u = __builtin_bit_cast(uint64_t, x);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// gpk_kmat_scaled: the factor of row `row` (wave-uniform: one scalar value per row, no vector register) and the factors of a lane's VEC
+// columns from `colb` on.  A missing vector and the positions past the edge read as 1, which changes no bit of a product.
+template <typename T>
+__device__ __forceinline__ T kmat_row_scale(const KmatArgs<T>& p, int64_t b, int row) {
+    return (p.rs != nullptr && row < p.n) ? gpk_uniform(p.rs[b * p.s_rs + row]) : T(1);
+}
+template <typename T, int VEC>
+__device__ __forceinline__ void kmat_col_scale(const KmatArgs<T>& p, int64_t b, int colb, T (&c)[VEC]) {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) c[v] = (p.cs != nullptr && colb + v < p.m) ? p.cs[b * p.s_cs + colb + v] : T(1);
 }
 
 // Term t of batch entry b from the device tables, derived as the host derives a launch-wide table (gpk_pack_terms and the shape loop of the
@@ -188,7 +205,8 @@ __device__ __forceinline__ T eval_terms(const KmatArgs<T>& p, const TS& ts, T r2
     return val;
 }
 
-template <typename T, bool DOT, int DC, bool SH, bool BT>
+// SC: gpk_kmat_scaled -- every value times rs[row] and then cs[col], in front of the diagonal addition
+template <typename T, bool DOT, int DC, bool SH, bool BT, bool SC>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
     constexpr int VEC = Traits<T>::VEC;
@@ -210,6 +228,8 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     if constexpr (BT) __syncthreads();     // (with d = 0 the chunk loop below has no barrier)
 
     const int colb = col0 + lane * VEC;   // first of this lane's VEC columns
+    T csv[VEC];
+    if constexpr (SC) kmat_col_scale<T, VEC>(p, b, colb, csv);     // in flight under the whole chunk loop
 
     T r2[RW][VEC];
     T dt[RW][VEC];
@@ -257,11 +277,14 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs<T> p) {
     for (int r = 0; r < RW; ++r) {
         const int row = row0 + wave * RW + r;
         if (row >= p.n) continue;
+        T rsr = T(1);
+        if constexpr (SC) rsr = kmat_row_scale(p, b, row);
         T vals[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             const int col = colb + v;
             T val = eval_terms<T, SH>(p, ts, r2[r][v], dt[r][v]);
+            if constexpr (SC) val = (val * rsr) * csv[v];
             if (p.symmetric && col == row) kmat_add_diag(p, b, row, val);
             vals[v] = val;
         }
@@ -402,7 +425,7 @@ __device__ __forceinline__ T eval_prog(const KmatArgs<T>& p, const TS& ts, T r2,
     return fma(fma(v0 * T(1.0 / 3.0), sd, v0), sd, v0) * gpk_exp_neg_t(-sd, etab);
 }
 
-template <typename T, int PROG, bool DOT, int DC, bool BT>
+template <typename T, int PROG, bool DOT, int DC, bool BT, bool SC>
 __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     typedef typename Traits<T>::vec_t vec_t;
     constexpr int VEC = Traits<T>::VEC;
@@ -416,6 +439,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
     constexpr bool PK32 = sizeof(T) == 4 && !TABLE;   // fp32: two values per instruction
     __shared__ T etab[ETAB ? 128 : 1];
     __shared__ T btab[(BT && TABLE) ? 4 * GPK_MAX_TERMS : 1];     // BT, term-table programs: the batch entry's table
+    __shared__ T rss[SC ? TM : 1];                                // SC: the row factors of the band
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -457,6 +481,16 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
             if (idx < TN * DC) ys[buf][(idx % DC) * TNP + idx / DC] = stage[k];
         }
     };
+    // SC: the factors of the band's rows, staged in LDS beside its X rows (read back as wave-uniform broadcasts, one per row and tile:
+    // held in registers for the whole walk they cost a wave of occupancy), and of the lane's columns -- this tile's in csv, the next
+    // tile's fetched into csn together with its Y values
+    T csv[VEC], csn[VEC];
+    if constexpr (SC) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) csn[v] = T(1);
+        if (tid < TM) rss[tid] = (p.rs != nullptr && row0 + tid < p.n) ? p.rs[b * p.s_rs + row0 + tid] : T(1);      // (published by the barrier below)
+        kmat_col_scale<T, VEC>(p, b, ct0 * TN + lane * VEC, csv);
+    }
     fetch_y(ct0 * TN);
     commit_y(0);
     if (ETAB && tid < 128) etab[tid] = (T)gpk_exp2_128[tid];
@@ -467,6 +501,9 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
         if (col0 >= p.m || (p.lower_only && col0 > row0 + TM - 1)) break;       // (uniform over the workgroup)
         const bool more = (c + 1 < CT) && (col0 + TN < p.m) && !(p.lower_only && col0 + TN > row0 + TM - 1);
         if (more) fetch_y(col0 + TN);                 // next tile's Y: in flight under this tile's arithmetic
+        if constexpr (SC) {
+            if (more) kmat_col_scale<T, VEC>(p, b, col0 + TN + lane * VEC, csn);
+        }
         T ya[DC][VEC];
 #pragma unroll
         for (int j = 0; j < DC; ++j) {
@@ -482,6 +519,8 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
             T xr[DC];              // this row of the band: wave-uniform LDS broadcast reads
 #pragma unroll
             for (int j = 0; j < DC; ++j) xr[j] = xs[(wave * RW + r) * DC + j];
+            T rsr = T(1);
+            if constexpr (SC) rsr = rss[wave * RW + r];
             T vals[VEC];
             if constexpr (PK32) {
                 // fp32, every compile-time kernel program: the row's four values as two pairs on the packed fp32 instructions (see gpk_exp_neg_pk)
@@ -524,6 +563,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         else if (PROG == PROG_M32) k = __builtin_elementwise_fma(sd, vv, vv) * e;
                         else k = __builtin_elementwise_fma(__builtin_elementwise_fma(sd, gpk_f2{v0 * (1.f / 3.f), v0 * (1.f / 3.f)}, vv), sd, vv) * e;
                     }
+                    if constexpr (SC) k = (k * gpk_f2{(float)rsr, (float)rsr}) * gpk_f2{(float)csv[2 * h], (float)csv[2 * h + 1]};
                     vals[2 * h] = (T)k.x;
                     vals[2 * h + 1] = (T)k.y;
                 }
@@ -543,6 +583,7 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
                         if (DOT) dt += xr[j] * ya[j][v];
                     }
                     T val = eval_prog<T, PROG>(p, ts, r2, dt, etab);
+                    if constexpr (SC) val = (val * rsr) * csv[v];
                     if (has_diag && colb + v == row) kmat_add_diag(p, b, row, val);
                     vals[v] = val;
                 }
@@ -568,6 +609,10 @@ __global__ __launch_bounds__(256) void kmat_band_kernel(KmatArgs<T> p) {
             }
         }
         if (more) commit_y((c + 1) & 1);     // the other buffer: nobody reads it during this iteration
+        if constexpr (SC) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) csv[v] = csn[v];
+        }
         __syncthreads();
     }
 }
@@ -635,12 +680,43 @@ inline int gpk_pack_kinds(KTermT<T>* terms, const int* kinds, const double* vari
     return GPK_OK;
 }
 
-// BT: variances, inv_ls, shapes are DEVICE tables [batch][nterms] of row stride bt_stride (gpk_kmat_batch_terms); else host arrays
+// The launch of the program `prog` (term-table programs: `shaped`) on the plan's grid; SC: the scaled kernels (never with BT)
+template <typename T, bool BT, bool SC>
+void kmat_dispatch(const KmatArgs<T>& a, dim3 grid, int prog, bool shaped, bool band, int d, hipStream_t stream) {
+    if (band) {
+#define GPK_BAND(PROGV, DOTV, DCV) hipLaunchKernelGGL((kmat_band_kernel<T, PROGV, DOTV, DCV, BT, SC>), grid, dim3(256), 0, stream, a)
+        switch (prog) {
+            case PROG_EQ: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ, false); break;
+            case PROG_M12: GPK_KMAT_DC(d, GPK_BAND, PROG_M12, false); break;
+            case PROG_M32: GPK_KMAT_DC(d, GPK_BAND, PROG_M32, false); break;
+            case PROG_M52: GPK_KMAT_DC(d, GPK_BAND, PROG_M52, false); break;
+            case PROG_EQ_LINEAR: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ_LINEAR, true); break;
+            case PROG_RQ: GPK_KMAT_DC(d, GPK_BAND, PROG_RQ, false); break;
+            default:
+                if (shaped) {
+                    if (a.need_dot) GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC_RQ, true);
+                    else GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC_RQ, false);
+                } else if (a.need_dot) GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC, true);
+                else GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC, false);
+        }
+#undef GPK_BAND
+        return;
+    }
+#define GPK_ONE_TILE(DOTV, SHV, DCV) hipLaunchKernelGGL((kmat_kernel<T, DOTV, DCV, SHV, BT, SC>), grid, dim3(256), 0, stream, a)
+    if (shaped && a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, true);
+    else if (shaped) GPK_KMAT_DC(d, GPK_ONE_TILE, false, true);
+    else if (a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, false);
+    else GPK_KMAT_DC(d, GPK_ONE_TILE, false, false);
+#undef GPK_ONE_TILE
+}
+
+// BT: variances, inv_ls, shapes are DEVICE tables [batch][nterms] of row stride bt_stride (gpk_kmat_batch_terms); else host arrays.
+// rs, cs: the row and column factors of gpk_kmat_scaled (both null: the unscaled kernels, whatever the strides)
 template <typename T, bool BT>
 int kmat_launch_any(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms, int64_t bt_stride,
                     const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
-                    int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
-                    int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
+                    int64_t sY, int d, const T* rs, int64_t s_rs, const T* cs, int64_t s_cs, T* out, int64_t ld, int64_t sO, int64_t batch,
+                    int lower_only, int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
                     hipStream_t stream) {
     if (n <= 0 || m <= 0 || batch <= 0) return GPK_OK;
     if (nterms < 0 || nterms > GPK_MAX_TERMS) return GPK_ERR_ARG(4);
@@ -651,6 +727,7 @@ int kmat_launch_any(const int* kinds, const double* variances, const double* inv
     KmatArgs<T> a;
     a.bt_var = a.bt_ils = a.bt_shape = nullptr;
     a.bt_stride = 0;
+    a.rs = rs; a.cs = cs; a.s_rs = s_rs; a.s_cs = s_cs;
     if constexpr (BT) {
         bool linear;
         if (const int st = gpk_pack_kinds(a.terms, kinds, variances, inv_ls, shapes, nterms, bt_stride, true, &shaped, &linear)) return st;
@@ -687,32 +764,12 @@ int kmat_launch_any(const int* kinds, const double* variances, const double* inv
     const KmatPlan plan = gpk_kmat_plan(n, m, batch, VEC, lower_only, symmetric, band, g_kmat_compact);
     a.ct = plan.ct; a.nbands = plan.nbands; a.compact = plan.compact;
     const dim3 grid(plan.gx, plan.gy, plan.gz);
-    if (band) {
-#define GPK_BAND(PROGV, DOTV, DCV) hipLaunchKernelGGL((kmat_band_kernel<T, PROGV, DOTV, DCV, BT>), grid, dim3(256), 0, stream, a)
-        switch (prog) {
-            case PROG_EQ: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ, false); break;
-            case PROG_M12: GPK_KMAT_DC(d, GPK_BAND, PROG_M12, false); break;
-            case PROG_M32: GPK_KMAT_DC(d, GPK_BAND, PROG_M32, false); break;
-            case PROG_M52: GPK_KMAT_DC(d, GPK_BAND, PROG_M52, false); break;
-            case PROG_EQ_LINEAR: GPK_KMAT_DC(d, GPK_BAND, PROG_EQ_LINEAR, true); break;
-            case PROG_RQ: GPK_KMAT_DC(d, GPK_BAND, PROG_RQ, false); break;
-            default:
-                if (shaped) {
-                    if (a.need_dot) GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC_RQ, true);
-                    else GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC_RQ, false);
-                } else if (a.need_dot) GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC, true);
-                else GPK_KMAT_DC(d, GPK_BAND, PROG_GENERIC, false);
-        }
-#undef GPK_BAND
-        GPK_CHECK_LAUNCH();
-        return GPK_OK;
+    if constexpr (BT) {
+        kmat_dispatch<T, true, false>(a, grid, prog, shaped, band, d, stream);
+    } else {
+        if (rs != nullptr || cs != nullptr) kmat_dispatch<T, false, true>(a, grid, prog, shaped, band, d, stream);
+        else kmat_dispatch<T, false, false>(a, grid, prog, shaped, band, d, stream);
     }
-#define GPK_ONE_TILE(DOTV, SHV, DCV) hipLaunchKernelGGL((kmat_kernel<T, DOTV, DCV, SHV, BT>), grid, dim3(256), 0, stream, a)
-    if (shaped && a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, true);
-    else if (shaped) GPK_KMAT_DC(d, GPK_ONE_TILE, false, true);
-    else if (a.need_dot) GPK_KMAT_DC(d, GPK_ONE_TILE, true, false);
-    else GPK_KMAT_DC(d, GPK_ONE_TILE, false, false);
-#undef GPK_ONE_TILE
     GPK_CHECK_LAUNCH();
     return GPK_OK;
 }
@@ -726,8 +783,19 @@ int gpk_kmat_launch(const int* kinds, const double* variances, const double* inv
                     int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                     int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
                     hipStream_t stream) {
-    return kmat_launch_any<T, false>(kinds, variances, inv_ls, shapes, nterms, 0, X, n, ldx, sX, Y, m, ldy, sY, d, out, ld, sO, batch,
-                                     lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
+    return kmat_launch_any<T, false>(kinds, variances, inv_ls, shapes, nterms, 0, X, n, ldx, sX, Y, m, ldy, sY, d, nullptr, 0, nullptr, 0, out, ld,
+                                     sO, batch, lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
+}
+
+// gpk_kmat_scaled: out (+)= rs_i cs_j k(x_i, y_j); rs, cs: device vectors of n and m values per batch entry, nullable
+template <typename T>
+int gpk_kmat_scaled_launch(const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
+                           const T* X, int64_t n, int64_t ldx, int64_t sX, const T* Y, int64_t m, int64_t ldy,
+                           int64_t sY, int d, const T* rs, int64_t s_rs, const T* cs, int64_t s_cs, T* out, int64_t ld, int64_t sO,
+                           int64_t batch, int lower_only, int symmetric, double diag_add, const T* diag_vec, int64_t sDiag,
+                           int accumulate, hipStream_t stream) {
+    return kmat_launch_any<T, false>(kinds, variances, inv_ls, shapes, nterms, 0, X, n, ldx, sX, Y, m, ldy, sY, d, rs, s_rs, cs, s_cs, out, ld,
+                                     sO, batch, lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
 }
 
 // kinds: host array; variances, inv_ls, shapes: device tables [batch][nterms], row stride s_terms
@@ -737,8 +805,8 @@ int gpk_kmat_bt_launch(const int* kinds, const double* variances, const double* 
                        int64_t sY, int d, T* out, int64_t ld, int64_t sO, int64_t batch, int lower_only,
                        int symmetric, double diag_add, const T* diag_vec, int64_t sDiag, int accumulate,
                        hipStream_t stream) {
-    return kmat_launch_any<T, true>(kinds, variances, inv_ls, shapes, nterms, s_terms, X, n, ldx, sX, Y, m, ldy, sY, d, out, ld, sO, batch,
-                                    lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
+    return kmat_launch_any<T, true>(kinds, variances, inv_ls, shapes, nterms, s_terms, X, n, ldx, sX, Y, m, ldy, sY, d, nullptr, 0, nullptr, 0, out,
+                                    ld, sO, batch, lower_only, symmetric, diag_add, diag_vec, sDiag, accumulate, stream);
 }
 
 template <typename T>
@@ -782,6 +850,9 @@ int gpk_kdiag_launch(const int* kinds, const double* variances, const double* in
                                     int64_t, int64_t, const T*, int64_t, int64_t, int64_t, int, T*,   \
                                     int64_t, int64_t, int64_t, int, int, double, const T*, int64_t,   \
                                     int, hipStream_t);                                                \
+    template int gpk_kmat_scaled_launch<T>(const int*, const double*, const double*, const double*, int, const T*, int64_t, \
+                                           int64_t, int64_t, const T*, int64_t, int64_t, int64_t, int, const T*, int64_t, const T*, int64_t, T*, \
+                                           int64_t, int64_t, int64_t, int, int, double, const T*, int64_t, int, hipStream_t); \
     template int gpk_kdiag_launch<T>(const int*, const double*, const double*, const double*, int, const T*, int64_t, \
                                      int64_t, int64_t, int, T*, int64_t, int64_t, hipStream_t);            \
     template int gpk_kmat_bt_launch<T>(const int*, const double*, const double*, const double*, int, int64_t, const T*, int64_t, \

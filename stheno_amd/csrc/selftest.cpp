@@ -5,6 +5,7 @@
 //     ./gpk_selftest --perf     + timings (HIP events) of the hot kernels
 //     ./gpk_selftest --rq       only the checks of the term kind with a shape parameter (rational quadratic)
 //     ./gpk_selftest --delta    only the checks of the Delta term kind
+//     ./gpk_selftest --scaled   only the checks of the kernel matrix with row and column factors (gpk_kmat_scaled), both kernels
 //     ./gpk_selftest --diff     only the checks of the derivative blocks of the kernel matrix (gpk_kmat_diff)
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -367,6 +368,89 @@ static void test_kmat() {
         for (int i = 0; i < n; ++i) { double nr = 0; for (int k = 0; k < d; ++k) nr += (double)X[i * d + k] * X[i * d + k]; ref[i] = 0.7 + 1.3 * 0.25 * nr; }
         report(std::string("kdiag_") + DT<T>::name(), st ? INFINITY : relerr(dO.down(), ref), DT<T>::eps * 50);
     }
+}
+
+// gpk_kmat_scaled (--scaled): the value contract of gpk.h.  K = gpk_kmat's output for the same arguments (itself held to the host loop
+// above, at that loop's tolerance); an element of the scaled launch has the BITS of fl(fl(K rs_i) cs_j) -- a missing scale skips its
+// multiplication, both missing: K's bits --, and an element that receives an addition a (the diagonal of a symmetric launch, every
+// element of an accumulating one) lies within eps (|v| + |a|) of v + a.  `which`: 3 = both scales, 1 = rows, 2 = columns, 0 = neither;
+// `shared`: one vector for the whole batch (stride 0).  Reported: the number of elements outside the contract (0 passes).
+template <typename T>
+static void test_scaled_case(std::vector<int> kinds, int n, int m, int d, int batch, bool sym, bool lower, bool acc, bool dvec, int which,
+                             bool shared) {
+    const int nt = (int)kinds.size();
+    std::vector<double> var(nt), il(nt), shp(nt, 0.0);
+    bool shaped = false;
+    for (int t = 0; t < nt; ++t) {
+        var[t] = 0.5 + 0.3 * t; il[t] = 1.0 / (0.7 + 0.2 * t);
+        if (kinds[t] == GPK_K_RQ) { shp[t] = 1.5 + t; shaped = true; }
+    }
+    if (sym) m = n;
+    auto X = randv<T>((size_t)batch * n * d), Y = sym ? X : randv<T>((size_t)batch * m * d);
+    const int64_t ld = m + 3;
+    auto O = randv<T>((size_t)batch * n * ld);
+    auto dv = randv<T>((size_t)batch * n), rs = randv<T>((size_t)batch * n), cs = sym ? rs : randv<T>((size_t)batch * m);
+    rs[n / 3] = T(0);
+    if (sym) cs = rs; else cs[m / 3] = T(0);
+    Dev<T> dX(X.size()), dY(Y.size()), dO(O.size()), dK(O.size()), dD(dv.size()), dR(rs.size()), dC(cs.size());
+    dX.up(X); dY.up(Y); dO.up(O); dK.zero(); dD.up(dv); dR.up(rs); dC.up(cs);
+    const double* shapes = shaped ? shp.data() : nullptr;
+    const double dadd = sym ? 0.25 : 0.0;
+    int st = gpk_kmat(DT<T>::v, kinds.data(), var.data(), il.data(), shapes, nt, dX.p, n, d, (int64_t)n * d, sym ? dX.p : dY.p, m, d, (int64_t)m * d, d,
+                      dK.p, ld, (int64_t)n * ld, batch, 0, sym, 0.0, nullptr, 0, 0, nullptr);
+    const int64_t srs = shared ? 0 : n, scs = shared ? 0 : m;
+    st |= gpk_kmat_scaled(DT<T>::v, kinds.data(), var.data(), il.data(), shapes, nt, dX.p, n, d, (int64_t)n * d, sym ? dX.p : dY.p, m, d, (int64_t)m * d,
+                          d, (which & 1) ? dR.p : nullptr, srs, (which & 2) ? dC.p : nullptr, scs, dO.p, ld, (int64_t)n * ld, batch, lower, sym, dadd,
+                          dvec ? dD.p : nullptr, n, acc, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    auto got = dO.down(), K = dK.down();
+    const int TN = 64 * (16 / (int)sizeof(T));
+    const long double eps = std::numeric_limits<T>::epsilon();
+    long bad = 0;
+    for (int b = 0; b < batch; ++b)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < m; ++j) {
+                const size_t o = (size_t)b * n * ld + (size_t)i * ld + j;
+                if (lower && (j / TN) * TN > (i / 32) * 32 + 31) { bad += got[o] != O[o]; continue; }      // untouched
+                volatile T v = K[o];
+                if (which & 1) v = v * rs[(shared ? 0 : (size_t)b * n) + i];
+                if (which & 2) v = v * cs[(shared ? 0 : (size_t)b * m) + j];
+                long double a = acc ? (long double)O[o] : 0.0L, aa = std::fabs(a);
+                const bool diag = sym && i == j;
+                if (diag) { a += dadd; aa += dadd; if (dvec) { a += dv[(size_t)b * n + i]; aa += std::fabs((long double)dv[(size_t)b * n + i]); } }
+                if (!acc && !diag) bad += memcmp(&got[o], const_cast<T*>(&v), sizeof(T)) != 0;
+                else bad += !(std::fabs((long double)got[o] - ((long double)v + a)) <= eps * (std::fabs((long double)v) + aa));
+            }
+    for (size_t b = 0; b < (size_t)batch * n; ++b)      // the padding behind every row stays what it was
+        for (int64_t j = m; j < ld; ++j) bad += got[b * ld + j] != O[b * ld + j];
+    char nm[200];
+    snprintf(nm, sizeof nm, "kmat_scaled_%s k%d.. nt%d n%d m%d d%d b%d sym%d low%d acc%d dv%d sc%d sh%d st%d", DT<T>::name(), kinds[0], nt, n, m, d,
+             batch, sym, lower, acc, dvec, which, shared, st);
+    report(nm, st ? INFINITY : (double)bad, 0.5);
+}
+template <typename T>
+static void test_scaled() {
+    const int TN = 64 * (16 / (int)sizeof(T));
+    // every program: the single-kind ones, EQ + Linear, the generic and the shaped term table, on the row-band walk (d <= 8) ...
+    for (std::vector<int> kinds : {std::vector<int>{GPK_K_EQ}, {GPK_K_MATERN12}, {GPK_K_MATERN32}, {GPK_K_MATERN52}, {GPK_K_RQ}, {GPK_K_EQ, GPK_K_LINEAR},
+                                   {GPK_K_MATERN52, GPK_K_MATERN32, GPK_K_CONST}, {GPK_K_RQ, GPK_K_EQ, GPK_K_LINEAR}}) {
+        test_scaled_case<T>(kinds, 33, TN + 1, 8, 1, false, false, false, false, 3, false);
+        test_scaled_case<T>(kinds, 65, 2 * TN + 3, 3, 2, false, false, false, false, 3, false);
+    }
+    // ... and on the one-tile kernel with two and three dimension chunks
+    for (int d : {9, 17}) {
+        test_scaled_case<T>({GPK_K_EQ}, 33, TN + 1, d, 1, false, false, false, false, 3, false);
+        test_scaled_case<T>({GPK_K_RQ, GPK_K_EQ, GPK_K_LINEAR}, 33, TN + 1, d, 1, false, false, true, false, 3, false);
+    }
+    // a missing scale, both missing, a vector shared by the batch, the smallest launch
+    for (int which : {0, 1, 2}) test_scaled_case<T>({GPK_K_EQ}, 31, TN - 1, 3, 2, false, false, false, false, which, false);
+    test_scaled_case<T>({GPK_K_MATERN32}, 33, 2 * TN + 1, 2, 3, false, false, false, false, 3, true);
+    test_scaled_case<T>({GPK_K_EQ}, 1, 1, 1, 1, false, false, false, false, 3, false);
+    // accumulate; the symmetric launches: the diagonal additions stay unscaled, the compact lower-triangle grid leaves the upper tiles
+    test_scaled_case<T>({GPK_K_EQ, GPK_K_LINEAR}, 65, 2 * TN + 3, 4, 1, false, false, true, false, 3, false);
+    test_scaled_case<T>({GPK_K_EQ}, 300, 300, 8, 2, true, false, false, true, 3, false);
+    test_scaled_case<T>({GPK_K_EQ}, 3 * TN + 5, 3 * TN + 5, 8, 1, true, true, false, true, 3, false);
+    test_scaled_case<T>({GPK_K_MATERN52, GPK_K_MATERN32, GPK_K_CONST}, 3 * TN + 5, 3 * TN + 5, 2, 1, true, true, true, true, 3, false);
 }
 
 // ----------------------------------------------------------------------------
@@ -2741,6 +2825,11 @@ int main(int argc, char** argv) {
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
+        if (!strcmp(argv[i], "--scaled")) {                    // only the checks of gpk_kmat_scaled, both kernels
+            for (int band = 1; band >= 0; --band) { gpk_tune(12, band); test_scaled<double>(); test_scaled<float>(); }
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
         if (!strcmp(argv[i], "--delta")) {                     // only the checks of the Delta kind
             test_delta<double>(); test_delta<float>();
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
@@ -2819,6 +2908,7 @@ int main(int argc, char** argv) {
         test_rq<double>(); test_rq<float>();
         test_delta<double>(); test_delta<float>();
         test_diff<double>(); test_diff<float>();
+        test_scaled<double>(); test_scaled<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

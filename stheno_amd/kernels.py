@@ -27,7 +27,7 @@ __all__ = [
     "Kernel", "EQ", "RQ", "Delta", "Periodic", "Exp", "Matern12", "Matern32", "Matern52", "Linear", "OneKernel", "ZeroKernel",
     "Mean", "ZeroMean", "OneMean", "PosteriorKernel", "PosteriorMean", "SubspaceKernel",
     "mean_var", "mean_var_diag", "uprank", "num_elements",
-    "MultiInput", "MultiOutputKernel", "MultiOutputMean", "InputScaled", "DiffKernel", "DiffMean",
+    "MultiInput", "MultiOutputKernel", "MultiOutputMean", "InputScaled", "DiffKernel", "DiffMean", "ScaleFn", "FnScaled",
 ]
 
 
@@ -282,8 +282,13 @@ class Kernel:
     __radd__ = __add__
 
     def __mul__(self, other):
+        # (a Kernel is itself callable: asked first)
         if isinstance(other, Kernel):
             raise NotImplementedError("products of kernels are outside the accelerated path")
+        if callable(other) and not torch.is_tensor(other):
+            # k * fn: fn(x) k(x, y) fn(y), mlkernels' k * TensorProductKernel(fn)
+            fn = other if isinstance(other, ScaleFn) else ScaleFn(other)
+            return _fn_scaled(self, fn, fn)
         v = _as_param(other)
         if isinstance(self, ZeroKernel) or (not torch.is_tensor(v) and v == 0):
             return ZeroKernel()
@@ -296,6 +301,7 @@ class Kernel:
         ``k.stretch(l_x, l_y)``: ``k(x / l_x, y / l_y)``, scalars only (the cross-kernel of ``f.stretch(l)`` with ``f`` is
         ``k.stretch(l, 1)``, its kernel ``k.stretch(l, l)``).  The two-argument form always divides the INPUTS; the one-argument form
         of a periodic kernel hands the stretch to the kernel behind the embedding, as it always did."""
+        _refuse_fn_scaled(self, "input maps (stretch)")
         if scale_y is not _UNSET:
             if _is_per_batch(scale) or _is_per_batch(scale_y) or has_per_batch(self):
                 raise NotImplementedError(f"the two-argument stretch is not implemented with {PER_BATCH}")
@@ -313,6 +319,7 @@ class Kernel:
         """``k.shift(c)``: ``k(x - c, y - c)`` (a stationary kernel is its own shift: ``k`` itself comes back);
         ``k.shift(c_x, c_y)``: ``k(x - c_x, y - c_y)``.  ``c``: a number, a 0-dim tensor or one entry per input dimension, kept as
         given (a learnable lag); the number ``0`` leaves that argument as it is."""
+        _refuse_fn_scaled(self, "input maps (shift)")
         if c_y is _UNSET:
             if self.stationary:
                 return self
@@ -323,6 +330,7 @@ class Kernel:
     def select(self, dims, dims_y=_UNSET):
         """``k.select(dims)``: ``k(x[:, dims], y[:, dims])``; ``k.select(dims_x, dims_y)``: one selection per argument, ``None`` leaves
         that argument as it is.  ``dims``: an input dimension or a sequence of them."""
+        _refuse_fn_scaled(self, "input maps (select)")
         mx = None if dims is None else _SelectMap(dims)
         return _behind(self, mx, mx if dims_y is _UNSET else (None if dims_y is None else _SelectMap(dims_y)))
 
@@ -330,12 +338,14 @@ class Kernel:
         """``k.transform(fn)``: ``k(fn(x), fn(y))`` for a callable from ``(..., N, D)`` to ``(..., N, D')`` -- a warping, a feature
         map, a small ``torch.nn`` network whose parameters are learnt through ``logpdf``; ``k.transform(fn_x, fn_y)``: one per argument,
         ``None`` is the identity."""
+        _refuse_fn_scaled(self, "input maps (transform)")
         mx = None if fn is None else _TransformMap(fn)
         return _behind(self, mx, mx if fn_y is _UNSET else (None if fn_y is None else _TransformMap(fn_y)))
 
     def periodic(self, period):
         """``k.periodic(p)``: ``k`` on ``(sin(2 pi x / p), cos(2 pi x / p))`` (mlkernels' ``Periodic``).  ``p``: a positive scalar,
         or one period per input dimension."""
+        _refuse_fn_scaled(self, "input maps (periodic)")
         return Periodic(self, period)
 
     def diff(self, *dims):
@@ -346,6 +356,7 @@ class Kernel:
             dims = (dims[0], dims[0])
         if len(dims) != 2:
             raise TypeError("diff(dim) or diff(dim_x, dim_y)")
+        _refuse_fn_scaled(self, "derivatives")
         return _diff_kernel(self, *(None if v is None else _as_dim(v) for v in dims))
 
     def __reversed__(self):
@@ -514,6 +525,9 @@ class Scaled(Kernel):
             groups = _map_groups(self)
             if groups is not None:
                 return _sum_of_groups(groups).pairwise(x, y, **kw)
+        groups = _scaled_groups(self)
+        if groups is not None:                     # ... and so does a sum with function-scaled groups, with or without a view
+            return _pairwise_groups(groups, x, y, kw)
         da, dv = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
         out = _as_factor(self.v) * self.k.pairwise(x, y, **kw)
         return _add_diag(out, da, dv) if y is None else out
@@ -1011,6 +1025,11 @@ class Sum(Kernel):
                 out = g.pairwise(xr, yr, out=out, accumulate=not first, diag_add=da if first else 0.0, diag_vec=dv if first else None, **kw)
                 first = False
             return out
+        groups = _scaled_groups(self)
+        if groups is not None:
+            # some groups between two functions, fn_x(x) k_g(x, y) fn_y(y): the same walk, such a group as ONE scaled launch
+            # (`kmat_scaled`) -- no N x M temporary for the scaled summand
+            return _pairwise_groups(groups, x, y, kw)
         da, dv = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
         kw.pop("lower", None)
         out = self.a.pairwise(x, y, **kw) + self.b.pairwise(x, y, **kw)
@@ -1142,6 +1161,297 @@ def _stretch_groups(k, s):
             cx = _chain(m, gx)
             out.append((kern, cx, cx if gx is gy else _chain(m, gy)))
     return _sum_of_groups(out)
+
+
+# ---------------------------------------------------------------------------
+# a kernel between two functions: fn_x(x) k(x, y) fn_y(y), the kernel of a process times a function (stheno/model/measure.py:242-251)
+# ---------------------------------------------------------------------------
+FN_SCALED = "function-scaled"
+
+
+class ScaleFn:
+    """A function of the inputs that multiplies a process: ``fn`` takes the upranked inputs ``(..., N, D)`` and returns one value per
+    point, ``(..., N)`` or ``(..., N, 1)``.  Any callable (an ``nn.Module`` included).  ``self(x)`` is a torch expression ``(..., N)`` in the
+    inputs' dtype, ``values(x)`` the same numbers cut off from the graph (what the fused launch sees).  Two are the same only if they
+    hold the same callable OBJECT; ``requires_grad`` follows :class:`_TransformMap`'s probe rule."""
+
+    def __init__(self, fn):
+        if not callable(fn):
+            raise TypeError("a process is multiplied by a callable from (..., N, D) to (..., N)")
+        self.fn = fn
+        self._probe = None
+
+    def __call__(self, x):
+        p = self._probe
+        if p is None or p.shape[-1] != x.shape[-1] or p.dtype != x.dtype or p.device != x.device:
+            self._probe = x.detach()[(0,) * (x.dim() - 2)][:1].clone()
+        out = self.fn(x)
+        if torch.is_tensor(out) and out.dim() == x.dim() and out.shape[-1] == 1:
+            out = out[..., 0]
+        if not (torch.is_tensor(out) and tuple(out.shape) == tuple(x.shape[:-1])):
+            raise ValueError(f"a function that multiplies a process maps inputs (..., N, D) to (..., N) or (..., N, 1); got "
+                             f"{tuple(getattr(out, 'shape', ()))} for inputs {tuple(x.shape)}")
+        return out.to(x.dtype)
+
+    def values(self, x):
+        with torch.no_grad():
+            return self(x.detach())
+
+    @property
+    def requires_grad(self):
+        if self._probe is None or self._probe.shape[-2] == 0:
+            return True
+        try:
+            with torch.enable_grad():
+                out = self.fn(self._probe)
+        except Exception:        # (a probe row the function cannot take: unknown, and unknown counts as learnable)
+            return True
+        return bool(torch.is_tensor(out) and out.requires_grad)
+
+    def same(self, other):
+        return type(other) is type(self) and other.fn is self.fn
+
+    def __repr__(self):
+        return getattr(self.fn, "__name__", type(self.fn).__name__)
+
+
+class _ProductFn(ScaleFn):
+    """``a(x) b(x)``: what ``(k * fn1) * fn2`` puts on a side."""
+
+    def __init__(self, a, b):
+        self.a, self.b = a, b
+        self.fn = self
+
+    def __call__(self, x):
+        return self.a(x) * self.b(x)
+
+    @property
+    def requires_grad(self):
+        return self.a.requires_grad or self.b.requires_grad
+
+    def same(self, other):
+        return type(other) is type(self) and self.a.same(other.a) and self.b.same(other.b)
+
+    def __repr__(self):
+        return f"{self.a!r} * {self.b!r}"
+
+
+def _same_fn(a, b):
+    return (a is b) or (a is not None and b is not None and a.same(b))
+
+
+def _fn_product(a, b):
+    return b if a is None else a if b is None else _ProductFn(a, b)
+
+
+def _fn_scaled(k, fx, fy):
+    """``fx(x) k(x, y) fy(y)`` as a kernel (``None``: that side as it is).  Zero stays zero, the functions of a kernel that sits
+    between two already are multiplied, a numeric factor stays outside, and a sum that is no sum of groups is scaled summand by summand."""
+    if (fx is None and fy is None) or isinstance(k, ZeroKernel):
+        return k
+    if isinstance(k, FnScaled):
+        px = _fn_product(k.fx, fx)
+        return FnScaled(k.k, px, px if (k.fx is k.fy and fx is fy) else _fn_product(k.fy, fy))
+    if isinstance(k, Sum) and _map_groups(k) is None:
+        return _fn_scaled(k.a, fx, fy) + _fn_scaled(k.b, fx, fy)
+    return FnScaled(k, fx, fy)
+
+
+def _contains_fn_scaled(k, _depth=0):
+    """Does a function-scaled kernel sit anywhere in ``k``?"""
+    if isinstance(k, FnScaled):
+        return True
+    return any(True for _ in _fn_scaled_nodes(k, _depth))
+
+
+def _fn_scaled_nodes(k, _depth=0):
+    """Every function-scaled kernel reachable from ``k`` (through sums, factors, posterior kernels, the blocks of several processes)."""
+    if isinstance(k, FnScaled):
+        yield k
+    if _depth > 16 or not isinstance(k, Kernel):
+        return
+    if isinstance(k, MultiOutputKernel):
+        for p in k.pids:
+            yield from _fn_scaled_nodes(k.kernels[p], _depth + 1)
+        return
+    for v in vars(k).values():
+        if isinstance(v, Kernel):
+            yield from _fn_scaled_nodes(v, _depth + 1)
+
+
+def prime_scale_fns(k, x):
+    """Give every function behind ``k`` that has not seen an input yet its probe row from ``x`` (a tensor, or a multi-process input whose
+    first part serves): a guard that asks ``requires_grad`` before the first evaluation then gets the probe's answer, not "unknown"."""
+    while isinstance(x, MultiInput):
+        x = x.parts[0][1] if x.parts else None
+    if not torch.is_tensor(x) or x.dim() < 2 or x.shape[-2] == 0:
+        return
+    def leaves(fn):
+        if isinstance(fn, _ProductFn):
+            yield from leaves(fn.a)
+            yield from leaves(fn.b)
+        elif fn is not None:
+            yield fn
+
+    row = None
+    for node in _fn_scaled_nodes(k):
+        for fn in (*leaves(node.fx), *leaves(node.fy)):
+            if fn._probe is None:
+                row = x.detach()[(0,) * (x.dim() - 2)][:1].clone() if row is None else row
+                fn._probe = row
+
+
+def _refuse_fn_scaled(k, what):
+    if _contains_fn_scaled(k):
+        raise NotImplementedError(f"{what} of a {FN_SCALED} kernel (the kernel of a process times a function) are not implemented: map "
+                                  "or differentiate the process first, multiply then")
+
+
+class FnScaled(Kernel):
+    """``fn_x(x) k(x, y) fn_y(y)``: the kernel of a process times a function (both sides hold the same :class:`ScaleFn`) and its
+    cross-kernels with other processes (one side is ``None``).  Built by ``k * fn``.
+
+    Where ``k`` is a sum of groups of primitives behind input maps, every group is ONE launch of ``kmat_scaled`` -- the two factors are
+    applied where the tile is stored, the diagonal additions stay unscaled -- written or accumulated into the caller's buffer like any
+    other group: lower-triangle-only and factorisable in place where both sides hold the same function.  Over any other kernel (a
+    posterior kernel) the inner kernel is evaluated and scaled in torch.  Values only, like every plain evaluation: the differentiable
+    log-density takes the kernel apart through ``_scaled_groups`` and forms ``fn(x)`` in torch."""
+
+    def __init__(self, k, fx, fy=_UNSET):
+        self.k, self.fx, self.fy = k, fx, (fx if fy is _UNSET else fy)
+
+    @property
+    def symmetric(self):
+        return _same_fn(self.fx, self.fy)
+
+    def num_outputs(self, x):
+        return self.k.num_outputs(x)
+
+    def __mul__(self, other):
+        if isinstance(other, Kernel) or (callable(other) and not torch.is_tensor(other)):
+            return super().__mul__(other)
+        inner = self.k * other                     # c * (k * fn): the factor goes into the group's variances
+        return inner if isinstance(inner, ZeroKernel) else FnScaled(inner, self.fx, self.fy)
+
+    __rmul__ = __mul__
+
+    def pairwise(self, x, y=None, **kw):
+        groups = _scaled_groups(self)
+        if groups is not None:
+            return _pairwise_groups(groups, x, y, kw)
+        x = uprank(x)
+        yr = x if y is None else uprank(y)
+        if isinstance(x, MultiInput) or isinstance(yr, MultiInput):
+            raise ValueError("FnScaled is a single-output kernel; it cannot take multi-process inputs")
+        out, accumulate = kw.pop("out", None), kw.pop("accumulate", False)
+        da, dv, lower = kw.pop("diag_add", 0.0), kw.pop("diag_vec", None), kw.pop("lower", False)
+        if y is None and not self.symmetric:
+            if lower or da or dv is not None:
+                raise ValueError("a kernel between two different functions is not symmetric: k(x) is the full block, without `lower` and "
+                                 "without additions to the diagonal")
+            y = x
+        res = self.k.pairwise(x, y, **kw)          # (any other inner kernel: evaluated, then scaled in torch)
+        if self.fx is not None:
+            res = res * self.fx.values(x)[..., :, None]
+        if self.fy is not None:
+            res = res * self.fy.values(yr)[..., None, :]
+        if y is None:
+            res = _add_diag(res if (self.fx is not None or self.fy is not None) else res.clone(), da, dv)
+        if out is None:
+            return res
+        if accumulate:
+            out += res
+        else:
+            out.copy_(res)
+        return out
+
+    def elwise(self, x, y=None, *, cache=None):
+        if y is not None and y is not x:
+            raise NotImplementedError("elwise is implemented for identical inputs")
+        if not self.symmetric:
+            raise NotImplementedError("elwise is implemented for the same function on both sides")
+        x = uprank(x)
+        s = self.fx.values(x)
+        return (s * s)[..., None] * self.k.elwise(x, cache=cache)
+
+    def __reversed__(self):
+        inner = reversed(self.k)
+        return self if (inner is self.k and self.fx is self.fy) else FnScaled(inner, self.fy, self.fx)
+
+    def __repr__(self):
+        return f"({self.fx!r} {self.k!r} {self.fy!r})"
+
+
+def _scaled_groups(k):
+    """``_map_groups`` with a function on either side of a group: ``[(k_g, imap_x, imap_y, fn_x, fn_y)]`` with ``k(x, y) = sum_g
+    fn_x(x) k_g(imap_x(x), imap_y(y)) fn_y(y)``, every ``k_g`` a sum of primitives, a missing function ``None``; None when the kernel has
+    no such form.  What ``_map_groups`` knows comes back as it lists it, between two ``None``."""
+    groups = _map_groups(k)
+    if groups is not None:
+        return [(kern, mx, my, None, None) for kern, mx, my in groups]
+    if isinstance(k, FnScaled):
+        inner = _scaled_groups(k.k)
+        if inner is None:
+            return None
+        out = []
+        for kern, mx, my, gx, gy in inner:
+            px = _fn_product(gx, k.fx)
+            out.append((kern, mx, my, px, px if (gx is gy and k.fx is k.fy) else _fn_product(gy, k.fy)))
+        return out
+    if isinstance(k, Sum):
+        ga, gb = _scaled_groups(k.a), _scaled_groups(k.b)
+        return None if ga is None or gb is None else ga + gb
+    if isinstance(k, Scaled):
+        g = _scaled_groups(k.k)
+        return None if g is None else [(Scaled(kern, k.v), mx, my, fx, fy) for kern, mx, my, fx, fy in g]
+    return None
+
+
+def _symmetric_scaled_groups(k):
+    """``_scaled_groups(k)`` if every group sees both arguments through the same map and between the same function, else None."""
+    groups = _scaled_groups(k)
+    if groups is None or not all(_same_map(mx, my) and _same_fn(fx, fy) for _, mx, my, fx, fy in groups):
+        return None
+    return groups
+
+
+def _pairwise_groups(groups, x, y, kw):
+    """The groups of ``_scaled_groups`` into ONE buffer: the first launch writes it (with the diagonal), the others add to it; a plain
+    group is a ``kmat`` launch, a group between functions a ``kmat_scaled`` launch.  ``lower`` / ``out`` / ``accumulate`` keep their meaning."""
+    kw = dict(kw)
+    kw.pop("cache", None)
+    out, da, dv = kw.pop("out", None), kw.pop("diag_add", 0.0), kw.pop("diag_vec", None)
+    first = not kw.pop("accumulate", False)
+    xr = uprank(x)
+    yr = None if y is None else uprank(y)
+    if isinstance(xr, MultiInput) or isinstance(yr, MultiInput):
+        raise ValueError("a sum of (function-scaled) groups is a single-output kernel; it cannot take multi-process inputs")
+    for kern, mx, my, fx, fy in groups:
+        args = dict(out=out, accumulate=not first, diag_add=da if first else 0.0, diag_vec=dv if first else None, **kw)
+        if fx is None and fy is None:
+            out = _Mapped(kern, mx, my).pairwise(xr, yr, **args)
+        else:
+            out = _scaled_launch(kern, mx, my, fx, fy, xr, yr, **args)
+        first = False
+    return out
+
+
+def _scaled_launch(kern, mx, my, fx, fy, x, y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+    """One group between functions as one ``kmat_scaled`` launch on the mapped inputs (values only)."""
+    kt = kern._kterms()
+    xm = x.detach() if mx is None else mx.values(x)
+    sx = None if fx is None else fx.values(x)
+    be = ops.get_backend()
+    if y is None and _same_map(mx, my) and _same_fn(fx, fy):
+        return be.kmat_scaled(kt, xm, None, sx, sx, lower=lower, diag_add=diag_add, diag_vec=diag_vec, out=out, accumulate=accumulate)
+    if y is None:
+        if lower or diag_add or diag_vec is not None:
+            raise ValueError("a kernel between two different functions (or behind two different input maps) is not symmetric: k(x) is the "
+                             "full block, without `lower` and without additions to the diagonal")
+        y = x
+    ym = y.detach() if my is None else my.values(y)
+    sy = None if fy is None else fy.values(y)
+    return be.kmat_scaled(kt, xm, ym, sx, sy, out=out, accumulate=accumulate)
 
 
 # ---------------------------------------------------------------------------
@@ -1436,6 +1746,9 @@ class Mean:
     __radd__ = __add__
 
     def __mul__(self, other):
+        if callable(other) and not torch.is_tensor(other) and not isinstance(other, Mean):
+            # m * fn: the mean of f * fn, evaluated in torch inside the graph; zero stays zero
+            return self if isinstance(self, ZeroMean) else ProductMean(self, other if isinstance(other, ScaleFn) else ScaleFn(other))
         if _is_per_batch(other):
             raise NotImplementedError(f"means scaled by {PER_BATCH} are not implemented")
         return ScaledMean(self, _as_float(other))
@@ -1579,6 +1892,30 @@ class SumMean(Mean):
 
     def __repr__(self):
         return f"{self.a!r} + {self.b!r}"
+
+
+class ProductMean(Mean):
+    """``fn(x) m(x)``: the mean of the process ``f * fn`` (``measure.py:242-251``).  A torch expression: the parameters behind ``fn`` and
+    behind ``m`` get their gradient through it."""
+
+    def __init__(self, m, fn):
+        self.m, self.fn = m, fn
+
+    def __call__(self, x, cache=None):
+        x = uprank(x)
+        if isinstance(x, MultiInput):
+            raise ValueError("the mean of a process times a function is the mean of one process; it cannot take multi-process inputs")
+        return _call_mean(self.m, x, cache) * self.fn(x)[..., None]
+
+    def diff(self, dim=0):
+        raise NotImplementedError("derivatives of a function-scaled mean (the mean of f * fn) are not implemented")
+
+    def _behind(self, imap):
+        raise NotImplementedError("input maps (shift / stretch / select / transform) of a function-scaled mean (the mean of f * fn) are not "
+                                  "implemented: map the process first, multiply then")
+
+    def __repr__(self):
+        return f"({self.m!r} * {self.fn!r})"
 
 
 class MappedMean(Mean):

@@ -36,8 +36,8 @@ def kernel_requires_grad(kernel, _depth=0):
     for val in vars(kernel).values():
         if torch.is_tensor(val) and val.requires_grad:
             return True
-        if isinstance(val, _k.InputMap) and val.requires_grad:       # a learnable shift, the parameters behind a feature map
-            return True
+        if isinstance(val, (_k.InputMap, _k.ScaleFn)) and val.requires_grad:       # a learnable shift, the parameters behind a feature
+            return True                                                            # map or behind the function of `f * fn`
         if isinstance(val, _k.Kernel) and kernel_requires_grad(val, _depth + 1):
             return True
     return False
@@ -61,6 +61,26 @@ def density_requires_grad(kernel, x, noise, y):
     noisy = ((isinstance(noise, Diagonal) and noise.diag().requires_grad)
              or (isinstance(noise, Dense) and noise.mat is not None and noise.mat.requires_grad))
     return bool(noisy or (torch.is_tensor(y) and y.requires_grad) or x_requires_grad(x) or kernel_requires_grad(kernel))
+
+
+def refuse_fn_scaled(what, kernels, x, *others):
+    """Refuse -- before any launch -- ``what`` under a learnable quantity behind a function-scaled kernel (``f * fn``): the one
+    differentiable case there is the log-density of one process (``_scaled_process_logpdf``).  ``kernels``: what the call evaluates;
+    ``x``: an input that primes the functions' probes; ``others``: further tensors whose gradient the call would drop (None: skipped)."""
+    if not torch.is_grad_enabled():
+        return
+    kernels = [k for k in kernels if isinstance(k, _k.Kernel) and _k._contains_fn_scaled(k)]
+    if not kernels:
+        return
+    for k in kernels:
+        _k.prime_scale_fns(k, x)
+    if (any(kernel_requires_grad(k) for k in kernels) or x_requires_grad(x)
+            or any(torch.is_tensor(t) and t.requires_grad for t in others)):
+        raise NotImplementedError(
+            f"{what} under learnable quantities behind a {_k.FN_SCALED} kernel (a process times a function) is not implemented -- "
+            "gradients there cover `f(x, noise).logpdf(y)` of ONE process, unbatched, with respect to variances, scalar length scales, "
+            "RQ's alpha, the noise, y, the mean and the function's parameters --: its value would be cut off from the autograd graph.  "
+            "Wrap the call in torch.no_grad() if that is intended")
 
 
 # ---- pieces the entry points share ------------------------------------------------------------
@@ -154,6 +174,10 @@ def marginals(pm, kernel, x, cache):
     learnable is behind them or when the call is outside the three covered cases: the plain path then runs exactly as before."""
     if not torch.is_grad_enabled():
         return None
+    src = pm if pm is not None else kernel
+    K_z = getattr(src, "K_z", None)
+    refuse_fn_scaled("a posterior mean / marginal variance", (kernel, getattr(pm, "k_zi", None), getattr(K_z, "kernel", None)), x,
+                     getattr(src, "z", None) if torch.is_tensor(getattr(src, "z", None)) else None, *_posterior_tensors(pm, K_z))
     for k in (kernel, getattr(pm, "k_zi", None)):
         if isinstance(k, _k.Kernel) and _k.has_per_batch(k) and kernel_requires_grad(k):
             raise NotImplementedError(f"gradients of posterior means and marginal variances are not implemented with {_k.PER_BATCH}: "
@@ -165,6 +189,21 @@ def marginals(pm, kernel, x, cache):
     if link is None or (pm is not None and kernel is not None and sparse_pair(kernel) is not link):
         return None
     return _sparse_marginals(pm, kernel, link, x, cache)
+
+
+def _posterior_tensors(pm, K_z):
+    """The tensors beside kernel and inputs that a posterior mean / variance depends on: the observations' noise and residual."""
+    out = []
+    noise = getattr(K_z, "noise", None)
+    if isinstance(noise, Diagonal):
+        out.append(noise.diag())
+    elif isinstance(noise, Dense) and noise.mat is not None:
+        out.append(noise.mat)
+    for name in ("y", "r", "rhs"):
+        t = getattr(pm, name, None)
+        if torch.is_tensor(t):
+            out.append(t)
+    return out
 
 
 def _posterior_parts(pm, K_z, k, z, x, cache, own_cross):
@@ -457,6 +496,11 @@ def logpdf(var, r):
             return lp if (r.dim() == 3 or lp.shape[0] != 1) else lp[0]
     if not torch.is_grad_enabled():
         return None
+    if isinstance(var.kernel, _k.Kernel) and _k._contains_fn_scaled(var.kernel):
+        lp = _scaled_process_logpdf(var, r)
+        if lp is not None:
+            return lp[0] if lp.shape[0] == 1 else lp
+        return None               # (nothing learnable behind it: the plain path)
     if r.dim() == 2 and isinstance(var.kernel, _k.MultiOutputKernel):      # several processes observed jointly
         lp = _joint_logpdf(var, r)
         if lp is not None:
@@ -497,6 +541,31 @@ def _process_logpdf(var, r):
         if xin.requires_grad:
             _ag.check_input_dims(xin)
     return _ag.gp_logpdf(mapped, noise_vec, r, noise_mat)
+
+
+def _scaled_process_logpdf(var, r):
+    """One process, unbatched, whose kernel is a sum of groups, each optionally between one function on both sides: ``k(x) = sum_g
+    diag(s_g) k_g(m_g(x)) diag(s_g)``, ``s_g = fn_g(x)`` formed HERE in torch -- the graph carries its gradient into the function's
+    parameters -- and handed to ``autograd._GPLogpdfScaled`` as a tensor.  None when nothing behind the density is learnable; every other
+    call under a learnable quantity is refused, before any launch."""
+    what = "this log-density (inputs with a gradient, a batch, several processes, a posterior, dense noise, learnable input maps)"
+    noise = var.noise
+    noise_t = noise.diag() if isinstance(noise, Diagonal) else getattr(noise, "mat", None) if isinstance(noise, Dense) else None
+    groups = _k._symmetric_scaled_groups(var.kernel) if torch.is_tensor(var.x) else None
+    noise_vec = var.differentiable_noise()
+    covered = (groups is not None and r.dim() == 2 and var.x.dim() == 2 and noise_vec is not NotImplemented and not var.x.requires_grad
+               and (noise_vec is None or noise_vec.dim() == 1) and not _k.has_per_batch(var.kernel)
+               and all(kern.tensor_terms() is not None for kern, *_ in groups))
+    if not covered:
+        refuse_fn_scaled(what, (var.kernel,), var.x, r, noise_t)
+        return None
+    x = var.x
+    mapped = [(kern, x if imap is None else imap(x), None if fx is None else fx(x)) for kern, imap, _, fx, _ in groups]
+    if any(u.requires_grad for _, u, _ in mapped):
+        refuse_fn_scaled(what, (var.kernel,), x, *[u for _, u, _ in mapped])
+    if not (groups_need_grad([(kern, u) for kern, u, _ in mapped], noise_vec, r) or any(s is not None and s.requires_grad for _, _, s in mapped)):
+        return None
+    return _ag.gp_logpdf_scaled(mapped, noise_vec, r)
 
 
 def _joint_logpdf(var, r):
@@ -556,6 +625,8 @@ def elbo(obs, measure):
         return None
     p_x, x, noise_x = obs.fdd.p, obs.fdd._xr, obs.fdd.noise
     p_z, z, noise_z = obs.u.p, obs.u._xr, obs.u.noise
+    refuse_fn_scaled("the pseudo-point bound", (measure.kernels[p_z], measure.kernels[p_x], measure.kernels[p_z, p_x]), x,
+                     z if torch.is_tensor(z) else None, obs.y, noise_x.diag() if isinstance(noise_x, Diagonal) else None)
     if isinstance(x, _k.MultiInput) or isinstance(z, _k.MultiInput) or not isinstance(noise_x, Diagonal):
         return None
     k = measure.kernels[p_z]

@@ -78,8 +78,8 @@ class FDD(Normal):
             k = p.kernel
             if k.input_scaled_view() is not None or isinstance(k, (_k.MultiOutputKernel, _k.DiffKernel)):
                 return KernelDense(k, xr, nz)      # K + noise fused, factorised in place (a derivative kernel: one gpk_kmat_diff launch)
-            if torch.is_tensor(xr) and xr.dim() == 2 and _k._map_groups(k) is not None:
-                return KernelDense(k, xr, nz)      # terms behind different input maps: one launch per group into the same buffer
+            if torch.is_tensor(xr) and xr.dim() == 2 and (_k._map_groups(k) is not None or _k._symmetric_scaled_groups(k) is not None):
+                return KernelDense(k, xr, nz)      # terms behind different input maps (or between functions): one launch per group into the same buffer
             return _k.note_built_from(k(xr) + nz, k, xr, nz)
 
         Normal.__init__(self, lambda: p.mean(xr), var, var_diag=var_diag, mean_var=mean_var,
@@ -100,6 +100,16 @@ class FDD(Normal):
                     f"gradients of a log-density with {_k.PER_BATCH} are implemented for a prior process whose kernel is a sum of "
                     "primitives behind one input map; this one (sums behind different maps, a posterior, several processes) is not: "
                     "wrap the call in torch.no_grad() for the value alone")
+        if torch.is_grad_enabled() and not isinstance(self.p, int) and _k._contains_fn_scaled(self.p.kernel):
+            # a process times a function: ONE differentiable case (learnable._scaled_process_logpdf, reached through the plain call
+            # below); a batch, several processes, a posterior are refused here, before any launch
+            from .. import learnable
+
+            xr = self._xr
+            if posterior or not torch.is_tensor(xr) or xr.dim() != 2 or isinstance(self.p.kernel, _k.MultiOutputKernel):
+                nz = self.noise
+                learnable.refuse_fn_scaled("this log-density (a batch, several processes, a posterior)", (self.p.kernel,), xr, x,
+                                           nz.diag() if isinstance(nz, Diagonal) else getattr(nz, "mat", None))
         if posterior and torch.is_grad_enabled() and self._learnable(x):
             # a posterior density under learnable quantities: the plain path would factorise the posterior covariance,
             # only for its value to be discarded -- go to the chain-rule form (two prior densities) at once

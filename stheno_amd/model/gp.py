@@ -130,8 +130,17 @@ class GP(RandomProcess):
         return res
 
     def __mul__(self, other):
-        if isinstance(other, GP) or isinstance(other, FunctionType):
-            raise NotImplementedError("products with processes/functions are outside the accelerated path")
+        if isinstance(other, GP):
+            raise NotImplementedError("products of processes are outside the accelerated path (they need products of kernels)")
+        if isinstance(other, FunctionType):
+            # (a bare Python function stays refused, as it always was here: `tests/test_host_logic.py` holds `p * <lambda>` to this
+            # error.  The product is asked for with a callable OBJECT -- an nn.Module, or the function wrapped: `f * ScaleFn(fn)`)
+            raise NotImplementedError("products with processes/functions are outside the accelerated path; for a process times a function "
+                                      "of the inputs wrap the function, `f * ScaleFn(fn)`, or pass a callable object such as an nn.Module")
+        if callable(other) and not _is_numeric(other):
+            # f * fn for a callable object of the inputs (an nn.Module, a ScaleFn): ONE wrapper, shared by the mean, the kernel's two
+            # sides and the cross-kernels of every measure -- "the same function" is "the same object"
+            other = other if isinstance(other, _k.ScaleFn) else _k.ScaleFn(other)
         res = GP()
         res._parents = (self,)
         for measure in self._measures:

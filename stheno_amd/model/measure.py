@@ -146,6 +146,12 @@ class Measure:
         return self._update(p_sum, self.means[p] + other, self.kernels[p], lambda j: wself().kernels[pid, j])
 
     def mul(self, p_mul, p, other):
+        if callable(other) and not torch.is_tensor(other):
+            # a process times a function of the inputs (``measure.py:242-251``): mean fn m, kernel fn(x) k(x, y) fn(y), cross-kernel with
+            # any other process fn(x) k_pj(x, y)
+            fn = other if isinstance(other, _k.ScaleFn) else _k.ScaleFn(other)
+            wself, pid = weakref.ref(self), id(p)
+            return self._update(p_mul, self.means[p] * fn, self.kernels[p] * fn, lambda j: _k._fn_scaled(wself().kernels[pid, j], fn, None))
         if torch.is_tensor(other) and other.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("a learnable scale of a process would be detached here: put it on the kernel "
                                       "(`GP(c**2 * EQ())`), where variances are differentiable")

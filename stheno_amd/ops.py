@@ -254,9 +254,10 @@ class HipBackend:
             raise RuntimeError(f"libgpk {what} failed with status {code}")
 
     # -- kernel matrices -----------------------------------------------------
-    def _kmat(self, entry, dims, terms, x, y, lower, diag_add, diag_vec, out, accumulate):
-        """One launch of ``gpk_kmat`` or ``gpk_kmat_diff`` (``entry``): the two take the same arguments, apart from ``dims`` -- what
-        ``gpk_kmat_diff`` has between the term table and the tensors."""
+    def _kmat(self, entry, dims, terms, x, y, lower, diag_add, diag_vec, out, accumulate, scales=None):
+        """One launch of ``gpk_kmat``, ``gpk_kmat_diff`` or ``gpk_kmat_scaled`` (``entry``): they take the same arguments, apart from
+        ``dims`` -- what ``gpk_kmat_diff`` has between the term table and the tensors -- and ``scales`` -- the ``(row_scale, col_scale)`` that
+        ``gpk_kmat_scaled`` has between ``d`` and ``out``."""
         symmetric = y is None
         x3, bshape = _as3(x)
         y3 = x3 if symmetric else _as3(y)[0]
@@ -271,8 +272,20 @@ class HipBackend:
         dv = None
         if diag_vec is not None:
             dv = diag_vec.reshape(B, n).contiguous()
+        sc = ()
+        if scales is not None:
+            # each scale: (..., len) with the inputs' batch shape, or (len,) shared by the batch (stride 0)
+            held = []      # (the contiguous copies live until the launch is enqueued)
+            for v, length in zip(scales, (n, m)):
+                if v is not None:
+                    self._check(v)
+                    if v.dtype != x.dtype or v.dim() < 1 or v.shape[-1] != length or v.numel() not in (length, B * length):
+                        raise ValueError(f"a scale of shape {tuple(v.shape)} and dtype {v.dtype} does not fit {B} x {length} values of {x.dtype}")
+                    v = v.detach().reshape(-1, length).contiguous()
+                    held.append(v)
+                sc += (self._ptr(v), length if v is not None and v.shape[0] > 1 else 0)
         tail = (self._ptr(x3), n, _ld(x3), _bs(x3), self._ptr(y3), m, _ld(y3),
-                _bs(y3), d, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
+                _bs(y3), d, *sc, self._ptr(o3), _ld(o3), _bs(o3), B, int(lower), int(symmetric), float(diag_add),
                 self._ptr(dv), n if dv is not None else 0, int(accumulate), self._stream())
         if terms.batch is not None:
             # one term table per batch entry: the tables stay on the device (gpk_kmat_batch_terms); derivative blocks have no such entry
@@ -300,6 +313,15 @@ class HipBackend:
         """``out[b, i, j] (+)= k(x[b, i], y[b, j])``; ``y is None`` means the symmetric case
         (then ``diag_add`` / ``diag_vec`` go on the diagonal)."""
         return self._kmat("gpk_kmat", (), terms, x, y, lower, diag_add, diag_vec, out, accumulate)
+
+    @_on_operand_device
+    def kmat_scaled(self, terms, x, y, row_scale, col_scale, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        """:meth:`kmat` times ``row_scale[b, i] * col_scale[b, j]`` in the same pass (``gpk_kmat_scaled``); ``diag_add`` / ``diag_vec`` go on
+        the diagonal UNSCALED.  A scale is ``(..., N)`` with the inputs' batch shape or ``(N,)`` shared by the batch, in the inputs' dtype;
+        ``None`` means all ones.  One term table for the whole launch: per-batch hyper-parameters are refused."""
+        if terms.batch is not None:
+            terms.c_arrays()       # (raises: no per-batch term tables under a scale)
+        return self._kmat("gpk_kmat_scaled", (), terms, x, y, lower, diag_add, diag_vec, out, accumulate, scales=(row_scale, col_scale))
 
     @_on_operand_device
     def kmat_diff(self, terms, x, y, dim_x, dim_y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
@@ -912,6 +934,24 @@ class _HostDelta:
         res = self._inner.kmat(rest, x, y, lower=lower, diag_add=diag_add, diag_vec=diag_vec)
         for _, (_, var, scale), eps in delta:
             res = res + self._t(var * self._kappa(x, x if y is None else y, scale, eps), res)
+        return self._deliver(res, out, accumulate)
+
+    def kmat_scaled(self, terms, x, y, row_scale, col_scale, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
+        """``HipBackend.kmat_scaled`` on a backend without the fused launch: the inner ``kmat`` and the two multiplications in torch, the
+        diagonal additions behind them (unscaled)."""
+        if terms.batch is not None:
+            terms.c_arrays()       # (raises, as the HIP backend does)
+        res = _HostDelta.kmat(self, terms, x, y, lower=lower)      # (this class's own: a recording subclass sees ONE call)
+        if row_scale is not None:
+            res = res * row_scale.detach().unsqueeze(-1)
+        if col_scale is not None:
+            res = res * col_scale.detach().unsqueeze(-2)
+        if y is None and (diag_vec is not None or diag_add != 0.0):
+            res = res.clone()
+            dg = torch.diagonal(res, dim1=-2, dim2=-1)
+            dg += diag_add
+            if diag_vec is not None:
+                dg += diag_vec.reshape(dg.shape)
         return self._deliver(res, out, accumulate)
 
     def kmat_diff(self, terms, x, y, dim_x, dim_y, *, lower=False, diag_add=0.0, diag_vec=None, out=None, accumulate=False):
