@@ -63,7 +63,7 @@ extern "C" {
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
  * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms.
  * 108: gpk_kmat_vjp_dense_batch, gpk_kmat_vjp_dense_batch_grid.
- * 109: gpk_kmat_scaled. */
+ * 109: gpk_kmat_scaled.  110: gpk_potrf_vjp. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -543,6 +543,29 @@ int gpk_kmat_vjp_dense_batch(int dtype, const int* kinds, const double* variance
 int gpk_kmat_diff_vjp(int dtype, const int* kinds, const double* variances, const double* inv_ls, const double* shapes, int nterms,
                       int dim_x, int dim_y, const void* x, int64_t n, int64_t ldx, const void* y, int64_t m, int64_t ldy, int d,
                       const void* g, int64_t ldg, void* partial, void* gradx, void* stream);
+
+/* VJP of the Cholesky factorisation A = L L^T (gradients through `B.cholesky`: joint posterior samples `mean + chol(Sigma) xi`,
+ * stheno/random.py:351, under a learnable kernel).
+ *   l: the factor gpk_potrf left (n x n, ld; ONLY its lower triangle is read -- the strict upper triangle holds whatever gpk_potrf
+ *   left there).  lbar: the cotangent of L (n x n, ldlb; only its lower triangle is read).  abar (n x n, lda, written FULL and exactly
+ *   symmetric, abar[i][j] == abar[j][i] bit for bit):
+ *     abar = W^T Psym W,   W = L^{-1},   Psym = 1/2 (P + P^T),   P = Phi(L^T tril(lbar)),   Phi = lower triangle with the diagonal halved
+ *   so that <abar, E> = d/dt sum(lbar * chol(A + t E)) for every symmetric E.  dinv_sb / sb as for gpk_trsm_lower (unbatched).
+ *   ws: gpk_potrf_vjp_ws_elems(n, sb) elements of scratch = three n x ceil16(n) matrices + the sb * n of gpk_trtri_lower (0 for n <= 0 or
+ *   an invalid sb); 16-byte aligned for the GEMM's vector loads.
+ *   Launches, all on `stream`: two clean lower-triangular copies of l and lbar into ws (the GEMM's GPK_GEMM_TRI_K skips whole
+ *   k-chunks, not elements, so its diagonal tiles must read zeros above the diagonal; NaN or Inf in the callers' strict upper
+ *   triangles never reaches the result), lower(L^T lbar) by one GEMM (GPK_GEMM_LOWER | GPK_GEMM_TRI_K), Phi and the half-sum into a
+ *   full symmetric matrix by one tiled transposing kernel, W by gpk_trtri_lower, W^T Psym (GPK_GEMM_TRI_K) and lower(W^T Psym W)
+ *   (GPK_GEMM_LOWER | GPK_GEMM_TRI_K) by two GEMMs, the mirror by gpk_symmetrize (a copy).  About (1/3 + 1/3 + 1 + 1/3) 2 n^3 / 2
+ *   multiply-adds.  No allocation, no host synchronisation, no atomics: a repeated call writes the same bits.  Nothing outside the
+ *   n x n view of abar is written; l, lbar and dinv_sb are not modified.  n is any order (the 128-block inverses are identity-padded).
+ *   Returns -k for argument k, checked in this order: -1 an unknown dtype; then n <= 0 returns 0 (an empty problem); -2 l == NULL;
+ *   -3 n above 2^20; -4 ld < n; -5 dinv_sb == NULL; -6 sb not 128 * 2^k <= 4096; -7 lbar == NULL; -8 ldlb < n; -9 abar == NULL;
+ *   -10 lda < n (or beyond the GEMM's limit on the leading dimension of C); -11 ws == NULL.  GPK_ERR_LAUNCH if a launch failed. */
+int64_t gpk_potrf_vjp_ws_elems(int64_t n, int sb);
+int gpk_potrf_vjp(int dtype, const void* l, int64_t n, int64_t ld, const void* dinv_sb, int sb, const void* lbar, int64_t ldlb,
+                  void* abar, int64_t lda, void* ws, void* stream);
 
 /* Measurement hooks (bench.py's live roofline figure).  Between gpk_prof_start and
  * gpk_prof_stop every MFMA GEMM launch of this process is bracketed by HIP events on its

@@ -26,7 +26,9 @@ shared hyper-parameters: ``_BatchedPosteriorMarginals``, every reduction one ``g
 (one exact conditioning step ACROSS processes: a component of a sum, several observed processes, derivatives -- the blocks are sums of
 groups ``s D^(a, b) k_g(u_g(x), u_g(y))``, ``learnable._block_groups``, and a derivative group's cotangent is reduced by
 ``gpk_kmat_diff_vjp``) and ``_SparsePosteriorMarginals`` (pseudo-point posteriors).  Each runs the plain path as its forward, so the
-values are that path's bits, and derives everything else from the stored factors.
+values are that path's bits, and derives everything else from the stored factors.  The JOINT covariance of the first case
+(``post(xs).var``) is ``_PosteriorCovariance`` at the end of the module, with the differentiable factorisation (``_FactorTimes``, on
+``gpk_potrf_vjp``) and log-determinant (``_LogdetSPD``) that ``Normal.sample`` / ``Normal.entropy`` take for a covariance inside the graph.
 
 This module holds the maths on ``libgpk`` launches and the packing of a kernel into a function's arguments; it imports nothing from
 ``kernels``.  Whether a call is in a covered case (groups, mapped inputs, dimension checks, dispatch, plain path or refusal) is decided in
@@ -41,7 +43,8 @@ import torch
 from . import ops
 from .matrix import LOG_2_PI, Chol, config
 
-__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals", "block_posterior_marginals", "sparse_posterior_marginals"]
+__all__ = ["gp_logpdf", "joint_logpdf", "sparse_elbo", "posterior_marginals", "block_posterior_marginals", "sparse_posterior_marginals",
+           "posterior_covariance", "add_diagonal", "factor_times", "logdet_spd"]
 
 
 # Hyper-parameters travel through the autograd functions as one flat list of scalar tensors: the variances, then the scales and --
@@ -1152,3 +1155,145 @@ def posterior_marginals(groups, r, noise_vec, run):
     layout, params = _pack_groups([kern for kern, _, _ in groups])
     fn = _BatchedPosteriorMarginals if groups[0][1].dim() == 3 else _PosteriorMarginals
     return fn.apply(r, noise_vec, run, layout, *[t for _, x, xs in groups for t in (x, xs)], *params)
+
+
+# ---------------------------------------------------------------------------------------------
+# The JOINT posterior covariance of the same exact posterior, Sigma = k(xs, xs) - V^T V (N* x N*; `post(xs).var`, and through it
+# `.sample()` and `.entropy()`), differentiable w.r.t. everything the marginal variances cover.  The marginal-variance backward with
+# diag(g_s) replaced by a symmetric matrix: with G the cotangent of Sigma, Gs = (G + G^T) / 2, B = L^{-T} V = K^{-1} k(x, xs),
+#     dL/dk(xs, xs) = Gs                          (N* x N*; its input gradient counts for both arguments)
+#     dL/dk(x, xs)  = -2 B Gs = -2 C              (N x N*, ONE N x N* x N* GEMM; d/dxs over its explicit transpose)
+#     dL/dK         = B Gs B^T = C B^T            (N x N, ONE lower-only N x N x N* GEMM; its diagonal: d/dnoise)
+# and the predictive noise sees the diagonal of G (`add_diagonal`).  Every reduction is a launch the marginal path uses:
+# gpk_kmat_vjp_dense on (xs, xs), (x, xs) and (xs, x), gpk_kmat_vjp on the lower triangle of dL/dK (A = 0, g = [-2]: its form
+# 1/2 (A diag(g) A^T - sum(g) S) is then S itself), and gpk_kmat_vjp_dense on (x, x) over the mirrored dL/dK where x needs a gradient.
+# Their number depends on the number of groups, not on N*.  The mean of the same evaluation has a node of its own
+# (`_PosteriorMarginals`): B is formed there only for a loss of the marginal variances, so the two share the factor and V, not B.
+# ---------------------------------------------------------------------------------------------
+class _PosteriorCovariance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, noise_vec, run, layout, *tensors):
+        """``run()`` -> ``(chol, v, cov)``: the plain HIP path (``PosteriorKernel.pairwise`` on detached values, as it is) with the
+        factor and ``v = L^{-1} k(x, xs)`` (N, N*) or its transpose as a ``WhitenedT`` it left behind.  ``layout`` / ``tensors`` as in
+        ``_PosteriorMarginals``: per group ``x`` / ``xs`` behind the group's input map, then the groups' parameters."""
+        chol, v, cov = run()
+        ctx.groups = _split_groups(layout, tensors, 2)
+        ctx.chol, ctx.v = chol, v
+        ctx.has_noise = noise_vec is not None
+        return cov
+
+    @staticmethod
+    def backward(ctx, g_cov):
+        be = ops.get_backend()
+        groups, chol, v = ctx.groups, ctx.chol, ctx.v
+        ng = len(groups)
+        x0, xs0 = groups[0].inputs
+        n, ns = x0.shape[0], xs0.shape[0]
+        dt = x0.dtype
+        need_x = [ctx.needs_input_grad[3 + 2 * i] for i in range(ng)]
+        need_xs = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
+        for grp, nx, nxs in zip(groups, need_x, need_xs):
+            if nx or nxs:
+                check_input_dims(grp.inputs[0])
+        g_cov = g_cov.to(dt)
+        gsym = (0.5 * (g_cov + g_cov.transpose(-1, -2))).contiguous()
+        bm = chol.solve_t_(v.plain() if hasattr(v, "zt") else be.copy(v))                 # B = L^{-T} V  (N, N*)
+        c = be.gemm(bm, gsym, a_kmajor=True, b_kmajor=True)                               # C = B Gs     (N, N*)
+        c_t = c.t().contiguous() if any(need_xs) else None                                # (N*, N), explicit
+        gk = be.gemm(c, bm, a_kmajor=True, b_kmajor=True, lower_only=True)                # C B^T = B Gs B^T, lower triangle (N, N)
+        del bm
+        zero = torch.zeros((n, 1), dtype=dt, device=x0.device)
+        if any(need_x):
+            be.symmetrize_(gk)
+        S, grad_x, grad_xs, diag_g = [None] * ng, [None] * ng, [None] * ng, None
+        for i, grp in enumerate(groups):
+            terms, (x, xs) = grp.terms, grp.inputs
+            S_ss, _, gx_ss = be.kmat_vjp_dense(terms, xs, xs, gsym, want_gradx=need_xs[i])        # through k(xs, xs)
+            S_c, _, gx_c = be.kmat_vjp_dense(terms, x, xs, c, want_gradx=need_x[i])               # through k(x, xs): -2 C
+            S_k, _, dg = be.kmat_vjp(terms, x, gk, zero, [-2.0])                                  # through K: the lower triangle of C B^T
+            S[i] = S_ss - 2.0 * S_c + S_k
+            if i == 0:
+                diag_g = dg                                                                       # (the same from every group)
+            if need_xs[i]:
+                _, _, gx_t = be.kmat_vjp_dense(terms, xs, x, c_t, want_gradx=True)
+                grad_xs[i] = 2.0 * gx_ss - 2.0 * gx_t
+            if need_x[i]:
+                grad_x[i] = _grad_inputs(be, terms, x, gk) - 2.0 * gx_c
+        grads = []
+        for grp, S_g in zip(groups, S):
+            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
+        grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[0]) else None
+        inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
+        return (grad_noise, None, None, *inputs, *grads)
+
+
+def posterior_covariance(groups, noise_vec, run):
+    """The differentiable joint covariance ``k(xs, xs) - V^T V`` (N*, N*) of ``_PosteriorCovariance``; ``groups`` = ``[(k_g, u_g(x),
+    u_g(xs))]``; ``run``: the plain path."""
+    layout, params = _pack_groups([kern for kern, _, _ in groups])
+    return _PosteriorCovariance.apply(noise_vec, run, layout, *[t for _, xin, xsin in groups for t in (xin, xsin)], *params)
+
+
+class _AddDiagonal(torch.autograd.Function):
+    """``mat + diag(d)`` by the launches ``Dense.__add__`` has always made (a copy, ``gpk_add_diag``), recorded: the cotangent goes to the
+    matrix as it is and its diagonal to ``d`` -- a learnable predictive noise under a joint posterior."""
+
+    @staticmethod
+    def forward(ctx, mat, d):
+        be = ops.get_backend()
+        return be.add_diag_(be.copy(mat), 0.0, d)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g if ctx.needs_input_grad[0] else None,
+                torch.diagonal(g, dim1=-2, dim2=-1).clone() if ctx.needs_input_grad[1] else None)
+
+
+def add_diagonal(mat, d):
+    return _AddDiagonal.apply(mat, d)
+
+
+class _FactorTimes(torch.autograd.Function):
+    """``chol(A) xi`` for a covariance ``A`` (n, n) inside the graph -- the factorisation of ``Normal.sample``, differentiable.
+    Forward: the factor the matrix object caches (``gpk_potrf``, as ever) and the one GEMM.  Backward: the cotangent of ``L`` is
+    ``tril(ybar xi^T)`` (one GEMM; ``gpk_potrf_vjp`` reads its lower triangle only), the cotangent of ``A`` is ``gpk_potrf_vjp`` of it."""
+
+    @staticmethod
+    def forward(ctx, a, factor, xi):
+        chol = factor()
+        ctx.chol, ctx.xi = chol, xi
+        return ops.get_backend().gemm(chol.lower(), xi, a_kmajor=True, b_kmajor=False)
+
+    @staticmethod
+    def backward(ctx, ybar):
+        be = ops.get_backend()
+        lbar = be.gemm(ybar.contiguous(), ctx.xi, a_kmajor=True, b_kmajor=True)           # ybar xi^T  (n, n)
+        return ctx.chol.potrf_vjp(lbar), None, None
+
+
+def factor_times(a, factor, xi):
+    """``chol(a) @ xi`` with the gradient to ``a``; ``factor()`` -> the ``Chol`` of ``a`` (plus jitter), ``xi`` (n, num) detached."""
+    return _FactorTimes.apply(a, factor, xi)
+
+
+class _LogdetSPD(torch.autograd.Function):
+    """``log det A`` for a covariance ``A`` (n, n) inside the graph -- ``Normal.entropy``.  Forward: the cached factor's
+    ``gpk_logdet_chol``.  Backward: ``A^{-1} = W^T W`` from ``gpk_trtri_lower`` and the triangular GEMM the log-density's backward
+    uses, mirrored."""
+
+    @staticmethod
+    def forward(ctx, a, factor):
+        chol = factor()
+        ctx.chol = chol
+        return chol.logdet()
+
+    @staticmethod
+    def backward(ctx, g):
+        be = ops.get_backend()
+        w = ctx.chol.inverse_lower()
+        ainv = be.symmetrize_(be.gemm(w, w, a_kmajor=False, b_kmajor=False, lower_only=True, tri_k=True))
+        return ainv * g.to(ainv.dtype), None
+
+
+def logdet_spd(a, factor):
+    return _LogdetSPD.apply(a, factor)

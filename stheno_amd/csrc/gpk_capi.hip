@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 109; }
+int gpk_version(void) { return 110; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -323,6 +323,14 @@ int gpk_kmat_diff_vjp(int dtype, const int* kinds, const double* variances, cons
                       const void* g, int64_t ldg, void* partial, void* gradx, void* stream) {
     D1(dtype, gpk_kmat_diff_vjp_launch<T>(kinds, variances, inv_ls, shapes, nterms, dim_x, dim_y, (const T*)x, n, ldx, (const T*)y, m,
                                           ldy, d, (const T*)g, ldg, (T*)partial, (T*)gradx, (hipStream_t)stream));
+}
+
+int64_t gpk_potrf_vjp_ws_elems(int64_t n, int sb) { return gpk_potrf_vjp_ws_elems_impl(n, sb); }
+
+int gpk_potrf_vjp(int dtype, const void* l, int64_t n, int64_t ld, const void* dinv_sb, int sb, const void* lbar, int64_t ldlb,
+                  void* abar, int64_t lda, void* ws, void* stream) {
+    D1(dtype, gpk_potrf_vjp_launch<T>((const T*)l, n, ld, (const T*)dinv_sb, sb, (const T*)lbar, ldlb, (T*)abar, lda, (T*)ws,
+                                      (hipStream_t)stream));
 }
 
 }  // extern "C"

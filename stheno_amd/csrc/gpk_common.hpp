@@ -328,3 +328,8 @@ int gpk_kmat_diff_vjp_launch(const int* kinds, const double* variances, const do
 template <typename T>
 int gpk_trtri_launch(const T* L, int64_t n, int64_t ld, const T* dinv_sb, int sb, T* W, int64_t ldw, T* tmp,
                      hipStream_t stream);
+// VJP of the Cholesky factorisation (gpk_potrf_vjp in gpk.h; gpk_potrf_vjp.hip): status codes are that entry's argument positions
+int64_t gpk_potrf_vjp_ws_elems_impl(int64_t n, int sb);
+template <typename T>
+int gpk_potrf_vjp_launch(const T* l, int64_t n, int64_t ld, const T* dinv_sb, int sb, const T* lbar, int64_t ldlb, T* abar, int64_t lda,
+                         T* ws, hipStream_t stream);

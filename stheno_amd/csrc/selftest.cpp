@@ -7,6 +7,7 @@
 //     ./gpk_selftest --delta    only the checks of the Delta term kind
 //     ./gpk_selftest --scaled   only the checks of the kernel matrix with row and column factors (gpk_kmat_scaled), both kernels
 //     ./gpk_selftest --diff     only the checks of the derivative blocks of the kernel matrix (gpk_kmat_diff)
+//     ./gpk_selftest --potrf-vjp   only the checks of the VJP of the Cholesky factorisation (gpk_potrf_vjp)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -2668,6 +2669,123 @@ __global__ void xor_lower_kernel(const unsigned* a, int n, long long per, unsign
     if ((threadIdx.x & 63) == 0) atomicXor(out, v);
 }
 
+// The VJP of the Cholesky factorisation (gpk_potrf_vjp)   --potrf-vjp
+// Against an 80-bit host evaluation of the formula of include/gpk.h on the factor as the device left it (so the error is the
+// entry's own): abar = W^T Psym W, W = L^{-1}, Psym = (P + P^T) / 2, P = Phi(L^T tril(lbar)).  NaN is planted in the strict upper
+// triangles of l and lbar (garbage by contract); padded leading dimensions; a second call must write the same bits.
+template <typename T>
+static void test_potrf_vjp() {
+    const double tol = sizeof(T) == 8 ? 1e-9 : 2e-3;
+    for (int n : {1, 127, 129, 300}) {
+        for (int sb : {128, 256}) {
+            if (sb == 256 && n != 300) continue;
+            const int ld = n + 5, ldlb = n + 3, lda = n + 7;
+            std::vector<double> a((size_t)n * (n + 8));
+            { std::normal_distribution<double> d(0.0, 1.0); for (auto& v : a) v = d(rng) / std::sqrt((double)(n + 8)); }
+            std::vector<T> hA((size_t)n * ld, (T)0), hB((size_t)n * ldlb, (T)0);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j <= i; ++j) {
+                    double acc = i == j ? 0.5 : 0.0;
+                    for (int k = 0; k < n + 8; ++k) acc += a[(size_t)i * (n + 8) + k] * a[(size_t)j * (n + 8) + k];
+                    hA[(size_t)i * ld + j] = (T)acc;
+                }
+            { std::normal_distribution<double> d(0.0, 1.0); for (int i = 0; i < n; ++i) for (int j = 0; j <= i; ++j) hB[(size_t)i * ldlb + j] = (T)d(rng); }
+            Dev<T> dA(hA.size()), dB(hB.size()), dinv(gpk_dinv_elems(n)), dsb((size_t)((n + sb - 1) / sb) * sb * sb),
+                tmpm((size_t)((n + sb - 1) / sb) * sb * sb / 4 + 16), out((size_t)n * lda), ws((size_t)gpk_potrf_vjp_ws_elems(n, sb));
+            Dev<int> info(1);
+            info.zero();
+            dA.up(hA);
+            int st = gpk_potrf(DT<T>::v, dA.p, n, ld, 0, 1, dinv.p, info.p, 0, nullptr);
+            st |= gpk_trtri_merge(DT<T>::v, dA.p, n, ld, 0, 1, dinv.p, sb, dsb.p, tmpm.p, nullptr);
+            HIPCHK(hipDeviceSynchronize());
+            std::vector<T> hL = dA.down();
+            const T nan = std::numeric_limits<T>::quiet_NaN();
+            for (int i = 0; i < n; ++i) {
+                for (int j = i + 1; j < ld; ++j) hL[(size_t)i * ld + j] = nan;
+                for (int j = i + 1; j < ldlb; ++j) hB[(size_t)i * ldlb + j] = nan;
+            }
+            dA.up(hL);
+            dB.up(hB);
+            std::vector<T> sentinel(out.n, (T)-7);
+            out.up(sentinel);
+            st |= gpk_potrf_vjp(DT<T>::v, dA.p, n, ld, dsb.p, sb, dB.p, ldlb, out.p, lda, ws.p, nullptr);
+            HIPCHK(hipDeviceSynchronize());
+            const std::vector<T> got = out.down();
+            st |= gpk_potrf_vjp(DT<T>::v, dA.p, n, ld, dsb.p, sb, dB.p, ldlb, out.p, lda, ws.p, nullptr);
+            HIPCHK(hipDeviceSynchronize());
+            const std::vector<T> again = out.down();
+            // the 80-bit reference
+            typedef long double R;
+            std::vector<R> L((size_t)n * n, 0), W((size_t)n * n, 0), P((size_t)n * n, 0), Tm((size_t)n * n, 0), ref((size_t)n * n, 0);
+            for (int i = 0; i < n; ++i) for (int j = 0; j <= i; ++j) L[(size_t)i * n + j] = (R)hL[(size_t)i * ld + j];
+            parallel_for(n, [&](int j) {                       // column j of W = L^{-1} by forward substitution
+                for (int i = j; i < n; ++i) {
+                    R acc = i == j ? 1.0L : 0.0L;
+                    for (int k = j; k < i; ++k) acc -= L[(size_t)i * n + k] * W[(size_t)k * n + j];
+                    W[(size_t)i * n + j] = acc / L[(size_t)i * n + i];
+                }
+            });
+            parallel_for(n, [&](int i) {                       // Psym from the lower triangle of L^T tril(lbar)
+                for (int j = 0; j <= i; ++j) {
+                    R acc = 0;
+                    for (int k = i; k < n; ++k) acc += L[(size_t)k * n + i] * (R)hB[(size_t)k * ldlb + j];
+                    P[(size_t)i * n + j] = 0.5L * acc;
+                }
+            });
+            for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) P[(size_t)i * n + j] = P[(size_t)j * n + i];
+            parallel_for(n, [&](int i) {                       // Tm = Psym W
+                for (int j = 0; j < n; ++j) {
+                    R acc = 0;
+                    for (int k = j; k < n; ++k) acc += P[(size_t)i * n + k] * W[(size_t)k * n + j];
+                    Tm[(size_t)i * n + j] = acc;
+                }
+            });
+            parallel_for(n, [&](int i) {                       // ref = W^T Tm
+                for (int j = 0; j < n; ++j) {
+                    R acc = 0;
+                    for (int k = i; k < n; ++k) acc += W[(size_t)k * n + i] * Tm[(size_t)k * n + j];
+                    ref[(size_t)i * n + j] = acc;
+                }
+            });
+            double num = 0, den = 0;
+            bool sym = true, same = true, kept = true;
+            for (int i = 0; i < n; ++i) {
+                for (int j = 0; j < n; ++j) {
+                    const R r = 0.5L * (ref[(size_t)i * n + j] + ref[(size_t)j * n + i]);
+                    const double g = (double)got[(size_t)i * lda + j];
+                    if (!std::isfinite(g)) num = INFINITY;
+                    num = std::max(num, (double)fabsl((R)g - r));
+                    den = std::max(den, (double)fabsl(r));
+                    sym = sym && memcmp(&got[(size_t)i * lda + j], &got[(size_t)j * lda + i], sizeof(T)) == 0;
+                }
+                for (int j = n; j < lda; ++j) kept = kept && got[(size_t)i * lda + j] == (T)-7;
+            }
+            same = memcmp(got.data(), again.data(), got.size() * sizeof(T)) == 0;
+            char name[160];
+            snprintf(name, sizeof name, "potrf_vjp %s n=%d sb=%d (NaN above the diagonals, padded ld)", DT<T>::name(), n, sb);
+            report(name, st ? INFINITY : num / den, tol);
+            snprintf(name, sizeof name, "potrf_vjp %s n=%d sb=%d symmetric / repeatable / in bounds", DT<T>::name(), n, sb);
+            report(name, (sym && same && kept) ? 0.0 : 1.0, 0.0);
+        }
+    }
+    // argument codes
+    Dev<T> buf(4096);
+    int bad = 0;
+    bad += gpk_potrf_vjp(7, buf.p, 4, 4, buf.p, 128, buf.p, 4, buf.p, 4, buf.p, nullptr) != -1;
+    bad += gpk_potrf_vjp(DT<T>::v, nullptr, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr) != 0;
+    bad += gpk_potrf_vjp(DT<T>::v, nullptr, 4, 4, buf.p, 128, buf.p, 4, buf.p, 4, buf.p, nullptr) != -2;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, ((int64_t)1 << 20) + 1, (int64_t)1 << 21, buf.p, 128, buf.p, (int64_t)1 << 21, buf.p, (int64_t)1 << 21, buf.p, nullptr) != -3;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 3, buf.p, 128, buf.p, 4, buf.p, 4, buf.p, nullptr) != -4;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, nullptr, 128, buf.p, 4, buf.p, 4, buf.p, nullptr) != -5;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, buf.p, 100, buf.p, 4, buf.p, 4, buf.p, nullptr) != -6;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, buf.p, 128, nullptr, 4, buf.p, 4, buf.p, nullptr) != -7;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, buf.p, 128, buf.p, 3, buf.p, 4, buf.p, nullptr) != -8;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, buf.p, 128, buf.p, 4, nullptr, 4, buf.p, nullptr) != -9;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, buf.p, 128, buf.p, 4, buf.p, 3, buf.p, nullptr) != -10;
+    bad += gpk_potrf_vjp(DT<T>::v, buf.p, 4, 4, buf.p, 128, buf.p, 4, buf.p, 4, nullptr, nullptr) != -11;
+    report(std::string("potrf_vjp ") + DT<T>::name() + " argument codes", bad, 0.0);
+}
+
 int main(int argc, char** argv) {
     bool do_perf = false, only_perf = false;
     for (int i = 1; i + 2 < argc; ++i)     // --set KEY VALUE: tuning knobs (gpk_debug_set)
@@ -2835,6 +2953,11 @@ int main(int argc, char** argv) {
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
+        if (!strcmp(argv[i], "--potrf-vjp")) {                 // only the checks of the Cholesky VJP (gpk_potrf_vjp)
+            test_potrf_vjp<double>(); test_potrf_vjp<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
         if (!strcmp(argv[i], "--potrf")) {                     // only the factorisation checks (plain + look-ahead)
             test_potrf<double>(); test_potrf<float>();
             test_lookahead<double>(); test_lookahead<float>();
@@ -2909,6 +3032,7 @@ int main(int argc, char** argv) {
         test_delta<double>(); test_delta<float>();
         test_diff<double>(); test_diff<float>();
         test_scaled<double>(); test_scaled<float>();
+        test_potrf_vjp<double>(); test_potrf_vjp<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

@@ -2068,6 +2068,11 @@ class PosteriorKernel(Kernel):
     def pairwise(self, x, y=None, *, lower=False, diag_add=0.0, diag_vec=None, cache=None):
         x = uprank(x)
         sym = y is None
+        if sym and torch.is_grad_enabled():
+            from . import learnable
+            got = learnable.covariance(self, x, cache, lower=lower, diag_add=diag_add, diag_vec=diag_vec)      # (the joint covariance under learnable quantities)
+            if got is not None:
+                return got
         y = x if sym else uprank(y)
         out = self.k_ij.pairwise(x, None if sym else y, cache=cache) if _accepts_cache(self.k_ij) else \
             self.k_ij.pairwise(x, None if sym else y)

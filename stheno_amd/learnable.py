@@ -5,7 +5,9 @@ dimensions, and then dispatches, leaves the call to the plain path, or refuses l
 mean / marginal variances: exact, across processes, pseudo-point), ``logpdf`` (one process, a batch, several processes jointly, the
 refusal) and ``elbo`` (the pseudo-point bound; ``requested``: its predicate) -- each return the differentiable result, or None for "run
 the plain path", or raise where a value would come out cut off from the graph.  The hooks in ``kernels.py``, ``random.py`` and
-``model/`` import this module where they call it: it imports ``kernels`` and ``autograd``, neither of which imports the other."""
+``model/`` import this module where they call it: it imports ``kernels`` and ``autograd``, neither of which imports the other.
+``covariance`` (the joint posterior covariance of the exact one-process case; ``graph_matrix``: what ``Normal.sample`` / ``.entropy``
+ask) follows the same rule."""
 import functools
 
 import numpy as np
@@ -481,6 +483,78 @@ def _sparse_marginals(pm, kernel, link, x, cache):
     mu, s = _ag.sparse_posterior_marginals(kern, xm, zm, xsm, r, noise_vec, obs.method, run)
     kt = kdiag_terms(kern.tensor_terms(), xsm) if pk is not None else None
     return _columns(pm, x, mu, s, (lambda: k.elwise(xd)) if pk is not None else None, kt)
+
+
+# ---- the joint posterior covariance ------------------------------------------------------------
+def _admit_covariance(pk, x):
+    """The admitted case of the differentiable joint covariance, or None: an EXACT posterior of one process predicted from its own
+    observations, unbatched, scalar or per-point noise, a kernel that is a sum of groups of primitives behind input maps -- the case
+    ``_exact_marginals`` handles directly -- with something learnable behind it.  Returns ``(groups, noise_vec)``.  Nothing is launched
+    here: every other call is the plain path's, exactly as before."""
+    if not (isinstance(pk, _k.PosteriorKernel) and pk.exact):
+        return None
+    K_z, k, z = pk.K_z, pk.k_zi, pk.z
+    if not (pk.k_zj is k and pk.k_ij is k and isinstance(K_z, KernelDense) and K_z.kernel is k and K_z.x is z):
+        return None
+    if not (torch.is_tensor(x) and torch.is_tensor(z) and x.dim() == 2 and z.dim() == 2 and x.shape[-1] == z.shape[-1]
+            and x.dtype == z.dtype and x.device == z.device):
+        return None
+    noise_vec = _diagonal_noise(K_z)
+    if noise_vec is NotImplemented:
+        return None
+    groups = _k._symmetric_groups(k)
+    if groups is None or not all(kern.tensor_terms() for kern, _, _ in groups):
+        return None
+    if not (kernel_requires_grad(k) or x.requires_grad or z.requires_grad or (noise_vec is not None and noise_vec.requires_grad)):
+        return None
+    return groups, noise_vec
+
+
+def covariance(pk, x, cache, **kw):
+    """The joint posterior covariance ``pk.pairwise(x)`` (N*, N*) under learnable quantities, through ``autograd._PosteriorCovariance``:
+    the plain path's bits with a gradient to variances, scales, shapes, map parameters, the observation noise, ``x`` and the observed
+    inputs.  ``kw``: what ``pairwise`` was called with (``lower``, ``diag_add``, ``diag_vec``: constants, added by the plain path
+    itself).  None when grad is off or the call is outside the admitted case (``_admit_covariance``).  A function-scaled kernel and
+    per-batch hyper-parameters under a gradient are refused as the marginals refuse them."""
+    if not torch.is_grad_enabled():
+        return None
+    K_z = getattr(pk, "K_z", None)
+    z = getattr(pk, "z", None)
+    refuse_fn_scaled("a posterior covariance", (pk, getattr(pk, "k_zi", None), getattr(K_z, "kernel", None)), x,
+                     z if torch.is_tensor(z) else None, *_posterior_tensors(None, K_z))
+    if _k.has_per_batch(pk) and kernel_requires_grad(pk):
+        raise NotImplementedError(f"gradients of posterior covariances are not implemented with {_k.PER_BATCH}: this call would return "
+                                  "values cut off from the autograd graph -- wrap it in torch.no_grad() if that is intended")
+    got = _admit_covariance(pk, x)
+    if got is None:
+        return None
+    groups, noise_vec = got
+    k = pk.k_zi
+    mapped = [(kern, z if imap is None else imap(z), x if imap is None else imap(x)) for kern, imap, _ in groups]
+    for _, zin, xin in mapped:
+        if zin.requires_grad or xin.requires_grad:
+            _ag.check_input_dims(xin)
+    xd = x.detach()
+    cache = {} if cache is None else cache
+
+    def run():
+        cov = pk.pairwise(xd, None, cache=cache, **kw)          # (grad is off in here: the plain path, as it is)
+        return K_z.chol(), _k._whiten(cache, K_z, k, z, xd, pk.own_cross), cov
+
+    return _ag.posterior_covariance(mapped, noise_vec, run)
+
+
+def graph_matrix(var):
+    """The matrix of a variance (``matrix.Dense``) as a tensor inside the autograd graph, or None when it carries none: what
+    ``Normal.sample`` / ``Normal.entropy`` ask before they take their differentiable form.  A lazily materialised posterior
+    covariance is materialised here only in the admitted case of :func:`covariance`; nothing else is touched."""
+    if not torch.is_grad_enabled() or not isinstance(var, Dense):
+        return None
+    mat = var._mat
+    if mat is None and isinstance(var, KernelDense) and var._chol is None and isinstance(var.noise, (type(None), Zero)) \
+            and _admit_covariance(var.kernel, _k.uprank(var.x)) is not None:
+        mat = var.mat
+    return mat if (torch.is_tensor(mat) and mat.dim() == 2 and mat.requires_grad) else None
 
 
 # ---- the log-density ------------------------------------------------------------

@@ -442,6 +442,15 @@ class Chol:
         sb, dsb = self._blocks(b.shape[-1])
         return ops.get_backend().tri_solve_t_(self.l, dsb, sb, b)
 
+    def potrf_vjp(self, lbar):
+        """The cotangent of ``A = L L^T`` from the cotangent ``lbar`` (n, n; its lower triangle is read) of this factor, full and exactly
+        symmetric (``gpk_potrf_vjp``; unbatched) -- the backward of a sample ``mean + L xi``.  The merged inverses are those of
+        :meth:`_blocks`."""
+        if self.l.dim() != 2:
+            raise NotImplementedError("potrf_vjp is implemented for unbatched factors")
+        sb, dsb = self._blocks(self.n)
+        return ops.get_backend().potrf_vjp(self.l, dsb, sb, lbar)
+
     def solve_t(self, b):
         """``L^{-T} b`` as a new tensor (see :meth:`solve_t_`)."""
         lb, bb = tuple(self.l.shape[:-2]), tuple(b.shape[:-2])
@@ -663,7 +672,7 @@ class Dense(AbstractMatrix):
         """``chol(self + epsilon * I)``, computed once (a copy is factorised)."""
         if self._chol is None:
             be = ops.get_backend()
-            a = be.copy(self.mat)
+            a = be.copy(self.mat.detach())           # (values only: a covariance that carries a graph is factorised as any other)
             if config.epsilon:
                 be.add_diag_(a, config.epsilon)
             self._chol = Chol.factor_(a)
@@ -682,6 +691,10 @@ class Dense(AbstractMatrix):
         if isinstance(other, Zero) or (isinstance(other, (int, float)) and other == 0):
             return self
         if isinstance(other, Diagonal):
+            if torch.is_grad_enabled() and self.mat.dim() == 2 and self.mat.requires_grad:
+                # a covariance inside the autograd graph (a joint posterior under learnable quantities): the same launches, recorded
+                from .autograd import add_diagonal
+                return Dense(add_diagonal(self.mat, other.diag()))
             return Dense(be.add_diag_(be.copy(self.mat), 0.0, other.diag()))
         if isinstance(other, Dense):
             return Dense(self.mat + other.mat)

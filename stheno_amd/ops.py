@@ -520,6 +520,30 @@ class HipBackend:
         return w
 
     @_on_operand_device
+    def potrf_vjp(self, l, dinv_sb, sb, lbar):
+        """The vector-Jacobian product of the Cholesky factorisation (``gpk_potrf_vjp``): ``l`` (n, n) the factor ``potrf_`` left (only its
+        lower triangle is read), ``dinv_sb`` / ``sb`` its merged inverses as for :meth:`tri_solve_`, ``lbar`` (n, n) the cotangent of
+        ``L`` (only its lower triangle is read).  Returns the cotangent of ``A = L L^T`` as a full, exactly symmetric (n, n) matrix."""
+        if l.dim() != 2 or lbar.dim() != 2 or l.shape[0] != l.shape[1] or tuple(lbar.shape) != tuple(l.shape):
+            raise ValueError("potrf_vjp takes one (n, n) factor and an (n, n) cotangent")
+        if lbar.dtype != l.dtype:
+            raise TypeError("potrf_vjp: the cotangent must have the factor's dtype")
+        n = l.shape[0]
+        if (n > 1 and l.stride(1) != 1) or (n > 1 and lbar.stride(1) != 1):
+            raise ValueError("potrf_vjp: unit inner strides")
+        self._check(l, dinv_sb, lbar)
+        abar = _alloc((), n, n, l.dtype, l.device)
+        if n == 0:
+            return abar
+        ws = torch.empty((int(self.lib.gpk_potrf_vjp_ws_elems(n, sb)),), dtype=l.dtype, device=l.device)
+        ld = lambda t: _ld(t.unsqueeze(0))      # noqa: E731
+        code = self.lib.gpk_potrf_vjp(_dtype_id(l), self._ptr(l), n, ld(l), self._ptr(dinv_sb), sb, self._ptr(lbar), ld(lbar),
+                                      self._ptr(abar), ld(abar), self._ptr(ws), self._stream())
+        self._st(code, "gpk_potrf_vjp")
+        # (`ws` is released here: the caching allocator hands it to later work of THIS stream only)
+        return abar
+
+    @_on_operand_device
     def gemm(self, a, b, *, a_kmajor=True, b_kmajor=True, alpha=1.0, beta=0.0, out=None, lower_only=False,
              tri_k=False, tri_k_lower=False, tri_k_lower_b=False, panel_solve=False):
         """``out[m, n] = alpha * sum_k a(m, k) b(n, k) + beta * out``.
@@ -870,7 +894,7 @@ class HipBackend:
 class _HostDelta:
     """Around a backend that is not the HIP one (the checker backends of ``tests/``, built on an oracle that predates the ``"delta"``
     kind): ``"delta"`` terms are evaluated here, in NumPy, and every other term is handed on unchanged; so are the derivative blocks of
-    ``kmat_diff``, which that oracle does not know either.  ``HipBackend`` is never wrapped: there both are launches of the fused HIP
+    ``kmat_diff`` and the Cholesky VJP ``potrf_vjp``, which that oracle does not know either.  ``HipBackend`` is never wrapped: there both are launches of the fused HIP
     kernels."""
 
     def __init__(self, inner):
@@ -1105,6 +1129,19 @@ class _HostDelta:
             gradx = ((G * cD)[:, :, None] * df).sum(1)
             gradx[:, sel] += (G * cS).sum(1)
         return self._t(S, x), (self._t(gradx, x) if want_gradx else None)
+
+    def potrf_vjp(self, l, dinv_sb, sb, lbar):
+        """``HipBackend.potrf_vjp`` in NumPy (fp64, rounded to the factor's dtype), the formula of ``include/gpk.h`` (gpk_potrf_vjp):
+        ``abar = W^T Psym W``, ``W = L^{-1}``, ``Psym = (P + P^T) / 2``, ``P = Phi(L^T tril(lbar))``; the strict upper triangles of ``l``
+        and ``lbar`` are not read."""
+        import numpy as np
+
+        L = np.tril(l.detach().cpu().numpy().astype(np.float64))
+        P = np.tril(L.T @ np.tril(lbar.detach().cpu().numpy().astype(np.float64)))
+        P[np.diag_indices_from(P)] *= 0.5
+        W = np.linalg.inv(L)
+        abar = W.T @ (0.5 * (P + P.T)) @ W
+        return self._t(0.5 * (abar + abar.T), l)
 
     def kdiag(self, terms, x):
         if terms.batch is not None:

@@ -256,7 +256,20 @@ class Normal(RandomVector):
         return (logpdfs[..., 0] if logpdfs.shape[-1] == 1 else logpdfs), False
 
     def entropy(self):
-        return (self.var.logdet() + self.dim * (LOG_2_PI + 1)) / 2
+        var = self.var
+        mat = self._graph_matrix(var)
+        if mat is not None:          # the covariance carries a graph (a joint posterior under learnable quantities): its gradient too
+            from .autograd import logdet_spd
+            return (logdet_spd(mat, var.chol) + self.dim * (LOG_2_PI + 1)) / 2
+        return (var.logdet() + self.dim * (LOG_2_PI + 1)) / 2
+
+    @staticmethod
+    def _graph_matrix(var):
+        """The variance's matrix if it is inside the autograd graph (``learnable.graph_matrix``), else None: the plain path."""
+        if not torch.is_grad_enabled():
+            return None
+        from . import learnable
+        return learnable.graph_matrix(var)
 
     @property
     def m2(self):
@@ -301,13 +314,23 @@ class Normal(RandomVector):
                 xi = torch.randn(d.shape + (num,), dtype=d.dtype, device=d.device, generator=generator)
             out = torch.sqrt(d)[..., None] * xi
         else:
+            graph = self._graph_matrix(var) is not None
             if noise is not None:
-                var = var + Diagonal(torch.full(tuple(var.shape[:-1]), float(noise), dtype=var.dtype, device=var.device))
-            chol = var.chol() if isinstance(var, Dense) else to_matrix(var.dense()).chol()
-            l = chol.lower()
+                if graph and torch.is_tensor(noise) and noise.requires_grad:
+                    d = noise.to(dtype=var.dtype, device=var.device) * torch.ones(tuple(var.shape[:-1]), dtype=var.dtype, device=var.device)
+                else:
+                    d = torch.full(tuple(var.shape[:-1]), float(noise), dtype=var.dtype, device=var.device)
+                var = var + Diagonal(d)
             if xi is None:
                 xi = torch.randn(tuple(var.shape[:-1]) + (num,), dtype=var.dtype, device=var.device, generator=generator)
-            out = ops.get_backend().gemm(l, xi.to(var.dtype), a_kmajor=True, b_kmajor=False)
+            mat = self._graph_matrix(var) if graph else None
+            if mat is not None:
+                # the covariance carries a graph: the same factorisation and product, recorded (the reparameterised sample)
+                from .autograd import factor_times
+                out = factor_times(mat, var.chol, xi.detach().to(var.dtype).contiguous())
+            else:
+                chol = var.chol() if isinstance(var, Dense) else to_matrix(var.dense()).chol()
+                out = ops.get_backend().gemm(chol.lower(), xi.to(var.dtype), a_kmajor=True, b_kmajor=False)
         if not self.mean_is_zero:
             out = out + self._mean_t
         return out
