@@ -63,7 +63,7 @@ extern "C" {
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
  * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms.
  * 108: gpk_kmat_vjp_dense_batch, gpk_kmat_vjp_dense_batch_grid.
- * 109: gpk_kmat_scaled.  110: gpk_potrf_vjp. */
+ * 109: gpk_kmat_scaled.  110: gpk_potrf_vjp.  111: gpk_nuclear_norm. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -566,6 +566,34 @@ int gpk_kmat_diff_vjp(int dtype, const int* kinds, const double* variances, cons
 int64_t gpk_potrf_vjp_ws_elems(int64_t n, int sb);
 int gpk_potrf_vjp(int dtype, const void* l, int64_t n, int64_t ld, const void* dinv_sb, int sb, const void* lbar, int64_t ldlb,
                   void* abar, int64_t lda, void* ws, void* stream);
+
+/* Nuclear norm (sum of the singular values) of a batch of square matrices:  out[b] = |M_b|_* = tr(U_b^T M_b),  U the orthogonal
+ * polar factor of M, taken as the limit of the Newton-Schulz iteration
+ *     X_0 = M / |M|_F,      X <- X (3/2 I - 1/2 X^T X)                      (`iters` steps, two GEMMs each: 3 n^3 flops per step)
+ * With V1 = L1 L1^T, V2 = L2 L2^T and M = L2^T L1 it is tr (V1^(1/2) V2 V1^(1/2))^(1/2), the cross term of the 2-Wasserstein distance
+ * between two normal distributions -- V1^(1/2) V2 V1^(1/2), V2 V1 and M^T M share their non-zero eigenvalues.  Replaces the two dense
+ * eigendecompositions `B.root(B.matmul(B.root(V1), V2, B.root(V1)))` of `Normal.w2`: stheno/random.py:313-329.
+ *   m: `batch` matrices of n x n, row stride ld >= n, batch stride sm >= 0 (0 shares one matrix); READ ONLY, and only inside its n
+ *   columns: the padding of a row may hold NaN.  out: batch values.  ws: gpk_nuclear_norm_ws_elems(n, batch) elements of scratch =
+ *   batch * (3 n ceil16(n) + min(ceil(n / 32), 512) + 1): three n x ceil16(n) matrices per entry (X, X', S), the per-workgroup partial
+ *   sums of the reductions and the norm (0 for n <= 0, batch <= 0 or a size the entry refuses); 16-byte aligned for the GEMM's vector
+ *   loads; its contents on entry do not matter (NaN included).
+ *   Launches, all on `stream`: the Frobenius norm of every entry as a two-stage reduction (per-workgroup partial sums over 32-row
+ *   bands, accumulated in fp64 in both dtypes, then one finishing workgroup per entry; fixed order); X_0 = M / |M|_F with the norm read
+ *   from device memory (a zero matrix gives X_0 = 0 and out = 0, never NaN); per step S = lower(X^T X) by one GEMM (GPK_GEMM_LOWER),
+ *   the full symmetric T = 3/2 I - 1/2 S from the lower triangle of S by one tiled transposing kernel, X' = X T by one GEMM into the
+ *   second X buffer; at the end out[b] = sum_ij X_ij M_ij by the same two-stage reduction, reading the caller's m with its strides.
+ *   The batch is the third grid dimension of the kernels and the batch of the GEMMs: one launch sequence for all entries, which
+ *   depends on (n, batch, iters) alone.  No allocation, no host read, no atomics: a repeated call writes the same bits.
+ *   Step count: a singular value that has not reached 1 after k steps was below about 1.5^-(k - 8) |M|_F to begin with and contributes
+ *   at most its own size to the error; 60 steps (fp64) / 40 (fp32) leave that below the rounding of the sum.
+ *   There is no convergence read.  Entries far outside 1e-150 .. 1e150 in magnitude overflow or underflow the sum of squares.
+ *   Returns -k for argument k, checked in this order: -1 an unknown dtype; then n <= 0 or batch <= 0 returns 0 (an empty problem,
+ *   nothing launched); -2 m == NULL; -3 n above 2^20 (the 32-tiles of the kernels are a grid dimension); -4 ld < n; -5 sm < 0;
+ *   -6 batch above 65535 (a grid dimension); -7 iters < 1; -8 out == NULL; -9 ws == NULL.  GPK_ERR_LAUNCH if a launch failed. */
+int64_t gpk_nuclear_norm_ws_elems(int64_t n, int64_t batch);
+int gpk_nuclear_norm(int dtype, const void* m, int64_t n, int64_t ld, int64_t sm, int64_t batch, int iters, void* out, void* ws,
+                     void* stream);
 
 /* Measurement hooks (bench.py's live roofline figure).  Between gpk_prof_start and
  * gpk_prof_stop every MFMA GEMM launch of this process is bracketed by HIP events on its

@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 110; }
+int gpk_version(void) { return 111; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -331,6 +331,13 @@ int gpk_potrf_vjp(int dtype, const void* l, int64_t n, int64_t ld, const void* d
                   void* abar, int64_t lda, void* ws, void* stream) {
     D1(dtype, gpk_potrf_vjp_launch<T>((const T*)l, n, ld, (const T*)dinv_sb, sb, (const T*)lbar, ldlb, (T*)abar, lda, (T*)ws,
                                       (hipStream_t)stream));
+}
+
+int64_t gpk_nuclear_norm_ws_elems(int64_t n, int64_t batch) { return gpk_nuclear_norm_ws_elems_impl(n, batch); }
+
+int gpk_nuclear_norm(int dtype, const void* m, int64_t n, int64_t ld, int64_t sm, int64_t batch, int iters, void* out, void* ws,
+                     void* stream) {
+    D1(dtype, gpk_nuclear_norm_launch<T>((const T*)m, n, ld, sm, batch, iters, (T*)out, (T*)ws, (hipStream_t)stream));
 }
 
 }  // extern "C"

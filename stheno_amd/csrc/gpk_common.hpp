@@ -333,3 +333,8 @@ int64_t gpk_potrf_vjp_ws_elems_impl(int64_t n, int sb);
 template <typename T>
 int gpk_potrf_vjp_launch(const T* l, int64_t n, int64_t ld, const T* dinv_sb, int sb, const T* lbar, int64_t ldlb, T* abar, int64_t lda,
                          T* ws, hipStream_t stream);
+// nuclear norm by the Newton-Schulz polar iteration (gpk_nuclear_norm in gpk.h; gpk_nuclear.hip): status codes are that entry's
+// argument positions
+int64_t gpk_nuclear_norm_ws_elems_impl(int64_t n, int64_t batch);
+template <typename T>
+int gpk_nuclear_norm_launch(const T* m, int64_t n, int64_t ld, int64_t sm, int64_t batch, int iters, T* out, T* ws, hipStream_t stream);

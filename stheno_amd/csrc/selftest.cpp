@@ -8,6 +8,7 @@
 //     ./gpk_selftest --scaled   only the checks of the kernel matrix with row and column factors (gpk_kmat_scaled), both kernels
 //     ./gpk_selftest --diff     only the checks of the derivative blocks of the kernel matrix (gpk_kmat_diff)
 //     ./gpk_selftest --potrf-vjp   only the checks of the VJP of the Cholesky factorisation (gpk_potrf_vjp)
+//     ./gpk_selftest --nuclear-norm   only the checks of the nuclear norm by the polar iteration (gpk_nuclear_norm)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -2786,6 +2787,114 @@ static void test_potrf_vjp() {
     report(std::string("potrf_vjp ") + DT<T>::name() + " argument codes", bad, 0.0);
 }
 
+// The nuclear norm by the Newton-Schulz polar iteration (gpk_nuclear_norm)   --nuclear-norm
+// Against a host evaluation of the singular values: one-sided Jacobi (Hestenes) rotations in 80-bit arithmetic on the matrix as the
+// device reads it, the sum of the column norms at convergence.  Batches of two with a padded leading dimension and a batch stride
+// beyond n * ld, NaN planted in all padding and in the whole workspace; a second call must write the same bits, the input is read only.
+static double host_nuclear_norm(std::vector<long double> a, int n) {      // a: n x n row-major, used up
+    typedef long double R;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        R off = 0;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                R app = 0, aqq = 0, apq = 0;
+                for (int i = 0; i < n; ++i) {
+                    const R x = a[(size_t)i * n + p], y = a[(size_t)i * n + q];
+                    app += x * x; aqq += y * y; apq += x * y;
+                }
+                if (apq == 0 || fabsl(apq) <= 1e-19L * sqrtl(app * aqq)) continue;
+                off = std::max(off, fabsl(apq) / sqrtl(app * aqq));
+                const R zeta = (aqq - app) / (2 * apq);
+                const R t = (zeta >= 0 ? 1.0L : -1.0L) / (fabsl(zeta) + sqrtl(1 + zeta * zeta));
+                const R c = 1 / sqrtl(1 + t * t), s = c * t;
+                for (int i = 0; i < n; ++i) {
+                    const R x = a[(size_t)i * n + p], y = a[(size_t)i * n + q];
+                    a[(size_t)i * n + p] = c * x - s * y;
+                    a[(size_t)i * n + q] = s * x + c * y;
+                }
+            }
+        if (off < 1e-17L) break;
+    }
+    R sum = 0;
+    for (int j = 0; j < n; ++j) {
+        R ss = 0;
+        for (int i = 0; i < n; ++i) ss += a[(size_t)i * n + j] * a[(size_t)i * n + j];
+        sum += sqrtl(ss);
+    }
+    return (double)sum;
+}
+
+template <typename T>
+static void test_nuclear_norm() {
+    const double tol = sizeof(T) == 8 ? 1e-12 : 1e-5;
+    const int iters = sizeof(T) == 8 ? 60 : 40;
+    const T nan = std::numeric_limits<T>::quiet_NaN();
+    for (int n : {1, 33, 129, 200}) {
+        const int batch = 2, ld = n + 5;
+        const size_t sm = (size_t)n * ld + 11;
+        std::vector<T> hM(sm * batch, nan);
+        std::normal_distribution<double> d(0.0, 1.0);
+        for (int b = 0; b < batch; ++b)
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) hM[b * sm + (size_t)i * ld + j] = (T)((b ? 3.0 : 0.25) * d(rng));
+        const size_t wse = (size_t)gpk_nuclear_norm_ws_elems(n, batch);
+        Dev<T> dM(hM.size()), out(batch + 2), ws(wse);
+        dM.up(hM);
+        ws.up(std::vector<T>(wse, nan));
+        out.up(std::vector<T>(batch + 2, (T)-7));
+        int st = gpk_nuclear_norm(DT<T>::v, dM.p, n, ld, (int64_t)sm, batch, iters, out.p, ws.p, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        const std::vector<T> got = out.down();
+        st |= gpk_nuclear_norm(DT<T>::v, dM.p, n, ld, (int64_t)sm, batch, iters, out.p, ws.p, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        const std::vector<T> again = out.down(), after = dM.down();
+        std::vector<double> ref(batch);
+        parallel_for(batch, [&](int b) {
+            std::vector<long double> a((size_t)n * n);
+            for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) a[(size_t)i * n + j] = (long double)hM[b * sm + (size_t)i * ld + j];
+            ref[b] = host_nuclear_norm(a, n);
+        });
+        double err = 0;
+        for (int b = 0; b < batch; ++b) err = std::max(err, std::isfinite((double)got[b]) ? std::fabs((double)got[b] - ref[b]) / ref[b] : INFINITY);
+        char name[160];
+        snprintf(name, sizeof name, "nuclear_norm %s n=%d batch=2 (NaN in padding and workspace)", DT<T>::name(), n);
+        report(name, st ? INFINITY : err, tol);
+        const bool ok = memcmp(got.data(), again.data(), got.size() * sizeof(T)) == 0 && got[batch] == (T)-7 && got[batch + 1] == (T)-7 &&
+                        memcmp(after.data(), hM.data(), hM.size() * sizeof(T)) == 0;
+        snprintf(name, sizeof name, "nuclear_norm %s n=%d repeatable / in bounds / input kept", DT<T>::name(), n);
+        report(name, ok ? 0.0 : 1.0, 0.0);
+    }
+    {   // exact cases: the zero matrix gives 0 (no 0 / 0), the identity gives n
+        const int n = 40;
+        std::vector<T> hM((size_t)2 * n * n, (T)0);
+        for (int i = 0; i < n; ++i) hM[(size_t)n * n + (size_t)i * n + i] = (T)1;
+        Dev<T> dM(hM.size()), out(2), ws((size_t)gpk_nuclear_norm_ws_elems(n, 2));
+        dM.up(hM);
+        const int st = gpk_nuclear_norm(DT<T>::v, dM.p, n, n, (int64_t)n * n, 2, iters, out.p, ws.p, nullptr);
+        HIPCHK(hipDeviceSynchronize());
+        const std::vector<T> got = out.down();
+        report(std::string("nuclear_norm ") + DT<T>::name() + " zero matrix = 0", st ? INFINITY : std::fabs((double)got[0]), 0.0);
+        report(std::string("nuclear_norm ") + DT<T>::name() + " identity = n", st ? INFINITY : std::fabs((double)got[1] - n) / n, tol);
+    }
+    // workspace size and argument codes
+    Dev<T> buf(4096);
+    int bad = 0;
+    bad += gpk_nuclear_norm_ws_elems(200, 3) != 3 * (3 * 200 * 208 + 7 + 1);
+    bad += gpk_nuclear_norm_ws_elems(0, 3) != 0 || gpk_nuclear_norm_ws_elems(-1, 1) != 0 || gpk_nuclear_norm_ws_elems(5, 0) != 0;
+    bad += gpk_nuclear_norm(7, buf.p, 4, 4, 16, 1, 5, buf.p, buf.p, nullptr) != -1;
+    bad += gpk_nuclear_norm(DT<T>::v, nullptr, 0, 0, 0, 1, 0, nullptr, nullptr, nullptr) != 0;
+    bad += gpk_nuclear_norm(DT<T>::v, nullptr, 4, 4, 16, 0, 0, nullptr, nullptr, nullptr) != 0;
+    bad += gpk_nuclear_norm(DT<T>::v, nullptr, 4, 4, 16, 1, 5, buf.p, buf.p, nullptr) != -2;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, ((int64_t)1 << 20) + 1, (int64_t)1 << 21, 0, 1, 5, buf.p, buf.p, nullptr) != -3;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, 4, 3, 16, 1, 5, buf.p, buf.p, nullptr) != -4;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, 4, 4, -1, 2, 5, buf.p, buf.p, nullptr) != -5;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, 4, 4, 0, 65536, 5, buf.p, buf.p, nullptr) != -6;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, 4, 4, 16, 1, 0, buf.p, buf.p, nullptr) != -7;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, 4, 4, 16, 1, 5, nullptr, buf.p, nullptr) != -8;
+    bad += gpk_nuclear_norm(DT<T>::v, buf.p, 4, 4, 16, 1, 5, buf.p, nullptr, nullptr) != -9;
+    report(std::string("nuclear_norm ") + DT<T>::name() + " workspace size and argument codes", bad, 0.0);
+}
+
 int main(int argc, char** argv) {
     bool do_perf = false, only_perf = false;
     for (int i = 1; i + 2 < argc; ++i)     // --set KEY VALUE: tuning knobs (gpk_debug_set)
@@ -2958,6 +3067,11 @@ int main(int argc, char** argv) {
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
+        if (!strcmp(argv[i], "--nuclear-norm")) {              // only the checks of the nuclear norm (gpk_nuclear_norm)
+            test_nuclear_norm<double>(); test_nuclear_norm<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
         if (!strcmp(argv[i], "--potrf")) {                     // only the factorisation checks (plain + look-ahead)
             test_potrf<double>(); test_potrf<float>();
             test_lookahead<double>(); test_lookahead<float>();
@@ -3033,6 +3147,7 @@ int main(int argc, char** argv) {
         test_diff<double>(); test_diff<float>();
         test_scaled<double>(); test_scaled<float>();
         test_potrf_vjp<double>(); test_potrf_vjp<float>();
+        test_nuclear_norm<double>(); test_nuclear_norm<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

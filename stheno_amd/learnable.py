@@ -65,6 +65,63 @@ def density_requires_grad(kernel, x, noise, y):
     return bool(noisy or (torch.is_tensor(y) and y.requires_grad) or x_requires_grad(x) or kernel_requires_grad(kernel))
 
 
+def _matrix_requires_grad(v):
+    """Does a structured matrix carry a gradient -- in what it holds already, or, for a kernel matrix that is not built yet, behind it?"""
+    if isinstance(v, Diagonal):
+        return bool(v.diag().requires_grad)
+    if isinstance(v, KernelDense):
+        if v._mat is not None and v._mat.requires_grad:
+            return True
+        return density_requires_grad(v.kernel, v.x, v.noise, None)
+    if isinstance(v, Dense):
+        return bool(v._mat is not None and v._mat.requires_grad)
+    return bool(torch.is_tensor(v) and v.requires_grad)
+
+
+def mean_requires_grad(mean, _depth=0):
+    """Does anything reachable from a mean carry a gradient: a tensor among its attributes (a scale, the observations and inputs of a
+    posterior mean), a learnable map or function (a module's parameters included), a kernel, a kernel matrix, another mean?"""
+    if _depth > 16 or mean is None:
+        return False
+    if isinstance(mean, _k.MultiOutputMean):
+        measure = mean._measure()
+        return measure is not None and any(mean_requires_grad(measure.means[p], _depth + 1) for p in mean.pids)
+    for val in vars(mean).values():
+        if torch.is_tensor(val):
+            if val.requires_grad:
+                return True
+        elif isinstance(val, (_k.InputMap, _k.ScaleFn)):
+            if val.requires_grad:
+                return True
+        elif isinstance(val, _k.Kernel):
+            if kernel_requires_grad(val):
+                return True
+        elif isinstance(val, _k.Mean):
+            if mean_requires_grad(val, _depth + 1):
+                return True
+        elif isinstance(val, (Dense, Diagonal)):
+            if _matrix_requires_grad(val):
+                return True
+        elif isinstance(val, torch.nn.Module):
+            if any(p.requires_grad for p in val.parameters()):
+                return True
+    return False
+
+
+def normal_requires_grad(dist):
+    """Does the mean or the variance of a ``Normal`` carry a graph?  Asked of what exists already (tensors, structured matrices) and, for
+    a finite-dimensional distribution of a process whose quantities are still lazy, of the process's mean and kernel, the inputs and
+    the noise -- nothing is computed by asking.  What ``Normal.w2`` asks before it refuses."""
+    if not torch.is_grad_enabled():
+        return False
+    if any(_matrix_requires_grad(q.value) for q in (dist._m, dist._v, dist._d) if q.known):
+        return True
+    p = getattr(dist, "p", None)
+    if p is None or isinstance(p, int):
+        return False
+    return bool(density_requires_grad(p.kernel, dist._xr, dist.noise, None) or mean_requires_grad(p.mean))
+
+
 def refuse_fn_scaled(what, kernels, x, *others):
     """Refuse -- before any launch -- ``what`` under a learnable quantity behind a function-scaled kernel (``f * fn``): the one
     differentiable case there is the log-density of one process (``_scaled_process_logpdf``).  ``kernels``: what the call evaluates;
