@@ -63,7 +63,7 @@ extern "C" {
 /* 104: the four entries that take a term table take `shapes` behind `inv_ls`; their `_s` twins of versions 102-103 are retired in version 104.
  * 105: gpk_kmat_diff.  106: gpk_kmat_diff_vjp.  107: gpk_kmat_batch_terms, gpk_kdiag_batch_terms.
  * 108: gpk_kmat_vjp_dense_batch, gpk_kmat_vjp_dense_batch_grid.
- * 109: gpk_kmat_scaled.  110: gpk_potrf_vjp.  111: gpk_nuclear_norm. */
+ * 109: gpk_kmat_scaled.  110: gpk_potrf_vjp.  111: gpk_nuclear_norm.  112: gpk_potrf_border. */
 int gpk_version(void);
 
 /* Optional: create the per-device helper stream of gpk_potrf_la now (current device) instead of at its first
@@ -594,6 +594,35 @@ int gpk_potrf_vjp(int dtype, const void* l, int64_t n, int64_t ld, const void* d
 int64_t gpk_nuclear_norm_ws_elems(int64_t n, int64_t batch);
 int gpk_nuclear_norm(int dtype, const void* m, int64_t n, int64_t ld, int64_t sm, int64_t batch, int iters, void* out, void* ws,
                      void* stream);
+
+/* BORDERED Cholesky: grow the factor of an n x n matrix by q new rows and columns without refactorising (a data set that grows by a
+ * few points per step: sequential conditioning, Bayesian optimisation).  With K11 = L11 L11^T factored and the bordered matrix
+ * [[K11, K12], [K12^T, K22]]:   L21 = (L11^{-1} K12)^T,   L22 = chol(K22 - L21 L21^T),   w2 = L22^{-1} (r2 - L21 w1).
+ * The O(n^2 q) part, V = L11^{-1} K12, is the caller's (gpk_trsm_lower_to / gpk_trsv_lower); this entry is the O(n q^2 + q^3) rest.
+ * On entry:  a (leading dimension ld >= n + q): rows [0, n) hold L11 (strict upper triangle unspecified, as after gpk_potrf);
+ *   a[n + i][n + j], j <= i < q, holds the lower triangle of K22 WITH its diagonal additions (noise, jitter);
+ *   v: V, n x q, unit inner stride, leading dimension ldv >= q;
+ *   dinv: ceil((n + q) / 128) blocks of 128 x 128, the first ceil(n / 128) as gpk_potrf left them for L11;
+ *   w1 (n values: L11^{-1} r1) and r2 (q values): both given or both NULL;
+ *   ws: gpk_potrf_border_ws_elems(n, q) elements of scratch (0 for an n or q the entry refuses); info: one int (need not be zeroed).
+ * On return: a[n + i][0 .. n) = row i of V^T (L21); a[n + i][n .. n + i] = L22 (entries right of the diagonal in the new rows are
+ *   unspecified); rows < n of `a` are not written.  dinv blocks g >= n / 128 (integer division) hold the inverse of the 128 x 128
+ *   diagonal block of the GROWN factor -- the block L11 filled only partly (n % 128 != 0) is REWRITTEN -- padded as gpk_potrf pads
+ *   a partial last block: the block is taken as diag(L_gg, I), so its inverse has the identity behind row n + q and zeros above the
+ *   diagonal.  Blocks below n / 128 are not written.  r2 is overwritten by w2.  info[0] = 0, or n + j when the leading minor of order
+ *   n + j of the bordered matrix is not positive definite (gpk_potrf's convention; the new rows, dinv and r2 are then unspecified).
+ * Four launches on `stream` (gpk_border.hip): V^T + partial Gram matrices of at most 64 row chunks of V + partial V^T w1 in one pass
+ * over V; the partials added in chunk order, one thread per element; ONE workgroup that forms S = K22 - sum and factorises it in LDS
+ * with the block routine of gpk_potrf, w2 by forward substitution; one workgroup per touched 128-block (at most two) that inverts the
+ * block of the grown factor by substitution (X L = I row by row).  No atomics, fixed summation order: a repeated call writes the same bits.  No
+ * allocation, no host synchronisation.
+ * Returns -k for argument k, all checked before anything is launched: -1 an unknown dtype; -2 a == NULL; -3 n < 1 (or above 2^30);
+ * -4 q outside 1 .. GPK_BORDER_MAX; -5 ld < n + q; -6 v == NULL; -7 ldv < q; -8 dinv == NULL; -9 r2 given without w1; -10 w1 given
+ * without r2; -11 info == NULL; -12 ws == NULL.  GPK_ERR_LAUNCH if a launch failed. */
+#define GPK_BORDER_MAX 128
+int64_t gpk_potrf_border_ws_elems(int64_t n, int q);
+int gpk_potrf_border(int dtype, void* a, int64_t n, int q, int64_t ld, const void* v, int64_t ldv, void* dinv, const void* w1, void* r2,
+                     int* info, void* ws, void* stream);
 
 /* Measurement hooks (bench.py's live roofline figure).  Between gpk_prof_start and
  * gpk_prof_stop every MFMA GEMM launch of this process is bracketed by HIP events on its

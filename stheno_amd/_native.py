@@ -136,6 +136,8 @@ SIGNATURES = {
     "gpk_potrf_vjp": (_c_int, [_c_int, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_int, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     "gpk_nuclear_norm_ws_elems": (_c_i64, [_c_i64, _c_i64]),
     "gpk_nuclear_norm": (_c_int, [_c_int, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
+    "gpk_potrf_border_ws_elems": (_c_i64, [_c_i64, _c_int]),
+    "gpk_potrf_border": (_c_int, [_c_int, _c_ptr, _c_i64, _c_int, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     "gpk_kmat_vjp_blocks": (_c_i64, [_c_i64]),
     "gpk_kmat_vjp": (
         _c_int,

@@ -38,7 +38,7 @@ static int potrf_rows_any(T* a, int64_t n, int64_t rows, int64_t ld, T* dinv, T*
 
 extern "C" {
 
-int gpk_version(void) { return 111; }
+int gpk_version(void) { return 112; }
 
 int64_t gpk_colreduce_chunks(int64_t rows) { return gpk_colreduce_nchunks_impl(rows); }
 
@@ -338,6 +338,14 @@ int64_t gpk_nuclear_norm_ws_elems(int64_t n, int64_t batch) { return gpk_nuclear
 int gpk_nuclear_norm(int dtype, const void* m, int64_t n, int64_t ld, int64_t sm, int64_t batch, int iters, void* out, void* ws,
                      void* stream) {
     D1(dtype, gpk_nuclear_norm_launch<T>((const T*)m, n, ld, sm, batch, iters, (T*)out, (T*)ws, (hipStream_t)stream));
+}
+
+int64_t gpk_potrf_border_ws_elems(int64_t n, int q) { return gpk_potrf_border_ws_elems_impl(n, q); }
+
+int gpk_potrf_border(int dtype, void* a, int64_t n, int q, int64_t ld, const void* v, int64_t ldv, void* dinv, const void* w1, void* r2,
+                     int* info, void* ws, void* stream) {
+    D1(dtype, gpk_potrf_border_launch<T>((T*)a, n, q, ld, (const T*)v, ldv, (T*)dinv, (const T*)w1, (T*)r2, info, (T*)ws,
+                                         (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -338,3 +338,15 @@ int gpk_potrf_vjp_launch(const T* l, int64_t n, int64_t ld, const T* dinv_sb, in
 int64_t gpk_nuclear_norm_ws_elems_impl(int64_t n, int64_t batch);
 template <typename T>
 int gpk_nuclear_norm_launch(const T* m, int64_t n, int64_t ld, int64_t sm, int64_t batch, int iters, T* out, T* ws, hipStream_t stream);
+// bordered Cholesky: q new rows under a factor of order n (gpk_potrf_border in gpk.h; gpk_border.hip): status codes are that entry's
+// argument positions
+int64_t gpk_potrf_border_ws_elems_impl(int64_t n, int q);
+template <typename T>
+int gpk_potrf_border_launch(T* a, int64_t n, int q, int64_t ld, const T* v, int64_t ldv, T* dinv, const T* w1, T* r2, int* info, T* ws,
+                            hipStream_t stream);
+// its middle launch, one workgroup on the in-LDS block factorisation of gpk_potrf.hip (diag3_block): S = K22 - (the `nparts` partial
+// Gram matrices, q x q each, added in order), factorised in LDS into a22 (= element (n, n) of the matrix); r2 (nullable, with `dots`:
+// nparts x q partial V^T w1) becomes L22^{-1} (r2 - sum of the partials) by substitution; info[0] = 0 or info_off + the failing order
+template <typename T>
+int gpk_border_factor_launch(T* a22, int64_t ld, int q, const T* gram, const T* dots, int nparts, T* r2, int* info, int info_off,
+                             hipStream_t stream);

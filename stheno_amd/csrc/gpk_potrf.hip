@@ -650,6 +650,74 @@ __global__ __launch_bounds__(D3_THREADS, WPE) void potrf_diag3_kernel(DiagArgs<T
 }
 
 // ---------------------------------------------------------------------------
+// border_factor_kernel -- the middle launch of gpk_potrf_border (gpk_border.hip): ONE workgroup builds the Schur complement of the q
+// new rows in LDS, S = K22 - sum_p G_p (the partial Gram matrices of V = L11^{-1} K12 per row chunk, added in the order p = 0, 1, ...:
+// the same bits on every call), and hands it to diag3_block as a block that is already there (LOAD = false; identity-padded to 128;
+// no inverse: the 128-blocks of the GROWN factor are inverted where they lie, border_inverse_kernel).  diag3_block writes L22 over
+// K22 and reports a non-positive pivot as info_off + its order.  The whitened residual of the new rows, w2 = L22^{-1} (r2 - sum_p
+// d_p) with d_p the partial V^T w1, is one wave's forward substitution against the factor in LDS (divisions by the pivots, not the
+// reciprocal pivots: this is the value the posterior mean is made of).
+// ---------------------------------------------------------------------------
+template <typename T>
+struct BorderArgs {
+    T* a22;            // element (n, n) of the matrix: K22 (lower triangle) on entry, L22 on return
+    int64_t ld;
+    int q;
+    const T* gram;     // [nparts][q][q], lower triangles
+    const T* dots;     // [nparts][q], nullable with r2
+    int nparts;
+    T* r2;
+    int* info;
+    int info_off;
+};
+
+template <typename T>
+__global__ __launch_bounds__(D3_THREADS, 2) void border_factor_kernel(BorderArgs<T> p) {
+    __shared__ __attribute__((aligned(16))) T S[D3_LDS_ELEMS];
+    const int tid = threadIdx.x, q = p.q;
+    if (tid == 0) *p.info = 0;
+    const int64_t qq = (int64_t)q * q;
+    for (int idx = tid; idx < GPK_DB * GPK_DB; idx += D3_THREADS) {
+        const int r = idx >> 7, c = idx & 127;
+        T v = (r == c) ? T(1) : T(0);
+        if (r < q && c <= r) {
+            const T* g = p.gram + (int64_t)r * q + c;
+            T s = T(0);
+            for (int k = 0; k < p.nparts; ++k) s += g[k * qq];
+            v = p.a22[(int64_t)r * p.ld + c] - s;
+        }
+        S[r * LDP + c] = v;
+    }
+    T t = T(0);
+    if (p.r2 != nullptr && tid < q) {
+        T s = T(0);
+        for (int k = 0; k < p.nparts; ++k) s += p.dots[(int64_t)k * q + tid];
+        t = p.r2[tid] - s;
+    }
+    __syncthreads();
+    diag3_block<T, false>(S, S + GPK_DB * LDP, p.a22, p.ld, q, (T*)nullptr, p.info, p.info_off, 0, nullptr);
+    if (p.r2 == nullptr) return;
+    __syncthreads();                                  // every wave is done with the block: the reciprocal pivots' slot is free
+    T* tv = S + GPK_DB * LDP;
+    if (tid < GPK_DB) tv[tid] = t;
+    __syncthreads();
+    if (tid < 64) {
+        const int r0 = tid, r1 = tid + 64;
+        T t0 = tv[r0], t1 = tv[r1];
+        for (int j = 0; j < q; ++j) {
+            T tj = __shfl(j < 64 ? t0 : t1, j & 63, 64);
+            tj = tj / S[j * LDP + j];
+            if (r0 == j) t0 = tj;
+            if (r1 == j) t1 = tj;
+            if (r0 > j && r0 < q) t0 -= S[r0 * LDP + j] * tj;
+            if (r1 > j && r1 < q) t1 -= S[r1 * LDP + j] * tj;
+        }
+        if (r0 < q) p.r2[r0] = t0;
+        if (r1 < q) p.r2[r1] = t1;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // potrf_pipe_kernel -- a whole panel of the factorisation (its diagonal blocks, the solves below them, the rank-128 updates
 // inside the panel) in ONE launch, as a pipeline between workgroups (task list and dependency rules: gpk_potrf_pipe.hpp).
 //
@@ -1936,6 +2004,17 @@ int gpk_potrf_rows_launch(T* A, int64_t n, int64_t rows, int64_t ld, T* dinv, in
 }
 template int gpk_potrf_rows_launch<double>(double*, int64_t, int64_t, int64_t, double*, int*, hipStream_t);
 template int gpk_potrf_rows_launch<float>(float*, int64_t, int64_t, int64_t, float*, int*, hipStream_t);
+
+template <typename T>
+int gpk_border_factor_launch(T* a22, int64_t ld, int q, const T* gram, const T* dots, int nparts, T* r2, int* info, int info_off,
+                             hipStream_t stream) {
+    BorderArgs<T> b{a22, ld, q, gram, dots, nparts, r2, info, info_off};
+    hipLaunchKernelGGL((border_factor_kernel<T>), dim3(1), dim3(D3_THREADS), 0, stream, b);
+    GPK_CHECK_LAUNCH();
+    return GPK_OK;
+}
+template int gpk_border_factor_launch<double>(double*, int64_t, int, const double*, const double*, int, double*, int*, int, hipStream_t);
+template int gpk_border_factor_launch<float>(float*, int64_t, int, const float*, const float*, int, float*, int*, int, hipStream_t);
 
 template int gpk_potrf_launch<double>(double*, int64_t, int64_t, int64_t, int64_t, double*, int*,
                                       int, hipStream_t);

@@ -9,6 +9,7 @@
 //     ./gpk_selftest --diff     only the checks of the derivative blocks of the kernel matrix (gpk_kmat_diff)
 //     ./gpk_selftest --potrf-vjp   only the checks of the VJP of the Cholesky factorisation (gpk_potrf_vjp)
 //     ./gpk_selftest --nuclear-norm   only the checks of the nuclear norm by the polar iteration (gpk_nuclear_norm)
+//     ./gpk_selftest --append   only the checks of the bordered Cholesky factorisation (gpk_potrf_border)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -2895,6 +2896,177 @@ static void test_nuclear_norm() {
     report(std::string("nuclear_norm ") + DT<T>::name() + " workspace size and argument codes", bad, 0.0);
 }
 
+// ----------------------------------------------------------------------------
+// The bordered Cholesky factorisation (gpk_potrf_border)   --append
+// The entry takes V = L11^{-1} K12 from its caller, so the contract is checked on operands made up here -- a random well-conditioned
+// lower-triangular L11, a random V and K22 = V^T V + M M^T + I -- against 80-bit host loops, in units of eps and with the bounds any
+// order of summation guarantees (Higham's gamma_k, k = the number of terms of the longest sum):
+//   L21 is V^T bit for bit;   |K22 - V^T V - L22 L22^T| <= (n + q + 1) eps (|K22| + |V|^T |V| + |L22| |L22|^T);
+//   |w2 - L22^{-1} (r2 - V^T w1)| <= (n + q + 1) eps |L22^{-1}| (|r2| + |V|^T |w1|), L22 as the device left it;
+//   |D_g L_gg - I| <= 129 eps |D_g| |L_gg| for the touched 128-blocks of the grown factor, identity-padded;
+//   nothing else is written (sentinels in the old rows, the padding columns, the rows behind the factor, the lower dinv blocks);
+//   a second call writes the same bits;   info = n + j for a K22 whose j-th new pivot is not positive;   the argument codes.
+// Shapes: those of tests/test_potrf_border_gpu.py, one with a padded leading dimension, one in a capacity buffer.
+template <typename T>
+static void test_append() {
+    typedef long double R;
+    const double eps = std::numeric_limits<T>::epsilon();
+    const T sentinel = (T)777;
+    struct Shape { int n, q, extra_ld, extra_rows; };
+    const Shape shapes[] = {{1, 1, 0, 0}, {127, 1, 0, 0}, {128, 1, 0, 0}, {130, 126, 0, 0}, {130, 127, 0, 0}, {130, 127, 16, 0}, {200, 128, 0, 0},
+                            {200, 128, 184, 184}, {384, 64, 0, 0}, {1000, 5, 0, 0}, {1000, 9, 0, 0}, {4133, 16, 0, 0}};
+    for (const Shape& sh : shapes) {
+        const int n = sh.n, q = sh.q, m = n + q, ld = m + sh.extra_ld, rows = m + sh.extra_rows;
+        const int nblk = (m + 127) / 128, keep = n / 128;
+        std::normal_distribution<double> d(0.0, 1.0);
+        std::vector<T> hA((size_t)rows * ld, sentinel), hV((size_t)n * q), hM((size_t)q * q), hw1(n), hr2(q);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j <= i; ++j) hA[(size_t)i * ld + j] = (T)(i == j ? 1.0 + std::fabs(d(rng)) : 0.5 * d(rng) / std::sqrt((double)n));
+        for (auto& x : hV) x = (T)(d(rng) / std::sqrt((double)n));
+        for (auto& x : hM) x = (T)(d(rng) / std::sqrt((double)q));
+        for (auto& x : hw1) x = (T)d(rng);
+        for (auto& x : hr2) x = (T)d(rng);
+        std::vector<R> gram((size_t)q * q), agram((size_t)q * q);           // V^T V and |V|^T |V|, lower triangles
+        parallel_for(q, [&](int i) {
+            for (int j = 0; j <= i; ++j) {
+                R s = 0, a = 0;
+                for (int k = 0; k < n; ++k) { const R p = (R)hV[(size_t)k * q + i] * (R)hV[(size_t)k * q + j]; s += p; a += fabsl(p); }
+                gram[(size_t)i * q + j] = s; agram[(size_t)i * q + j] = a;
+            }
+        });
+        for (int i = 0; i < q; ++i)
+            for (int j = 0; j <= i; ++j) {
+                R s = gram[(size_t)i * q + j] + (i == j ? 1 : 0);
+                for (int k = 0; k < q; ++k) s += (R)hM[(size_t)i * q + k] * (R)hM[(size_t)j * q + k];
+                hA[(size_t)(n + i) * ld + n + j] = (T)s;
+            }
+        const size_t wse = (size_t)gpk_potrf_border_ws_elems(n, q);
+        Dev<T> dA(hA.size()), dV(hV.size()), dinv((size_t)nblk * 128 * 128), w1(n), r2(q), ws(wse);
+        Dev<int> info(1);
+        const std::vector<T> hD((size_t)nblk * 128 * 128, sentinel);
+        auto run = [&](const std::vector<T>& a0, bool rhs, std::vector<T>& a1, std::vector<T>& d1, std::vector<T>& w2) -> int {
+            dA.up(a0); dV.up(hV); dinv.up(hD); w1.up(hw1); r2.up(hr2);
+            ws.up(std::vector<T>(wse, std::numeric_limits<T>::quiet_NaN()));
+            std::vector<int> one(1, -5);
+            HIPCHK(hipMemcpy(info.p, one.data(), sizeof(int), hipMemcpyHostToDevice));
+            const int st = gpk_potrf_border(DT<T>::v, dA.p, n, q, ld, dV.p, q, dinv.p, rhs ? w1.p : nullptr, rhs ? r2.p : nullptr, info.p, ws.p, nullptr);
+            HIPCHK(hipDeviceSynchronize());
+            a1 = dA.down(); d1 = dinv.down(); w2 = r2.down();
+            HIPCHK(hipMemcpy(one.data(), info.p, sizeof(int), hipMemcpyDeviceToHost));
+            return st ? -1000 + st : one[0];
+        };
+        std::vector<T> a1, d1, w2, a2, d2, w2b;
+        const int inf = run(hA, true, a1, d1, w2);
+        const int inf2 = run(hA, true, a2, d2, w2b);
+        char name[200], tag[80];
+        snprintf(tag, sizeof tag, "%s n=%d q=%d ld=%d rows=%d", DT<T>::name(), n, q, ld, rows);
+        // untouched memory, L21 = V^T, repeatability
+        bool same = inf == 0 && inf2 == 0;
+        for (int i = 0; i < rows && same; ++i)
+            for (int j = 0; j < ld; ++j) {
+                const size_t at = (size_t)i * ld + j;
+                const bool written = i >= n && i < m && j < m;      // (right of the diagonal the new rows are unspecified)
+                if (!written && memcmp(&a1[at], &hA[at], sizeof(T)) != 0) { same = false; break; }
+                if (i >= n && i < m && j < n && memcmp(&a1[at], &hV[(size_t)j * q + (i - n)], sizeof(T)) != 0) { same = false; break; }
+            }
+        for (size_t at = 0; at < (size_t)keep * 128 * 128 && same; ++at) same = d1[at] == sentinel;
+        same = same && memcmp(a1.data(), a2.data(), a1.size() * sizeof(T)) == 0 && memcmp(d1.data(), d2.data(), d1.size() * sizeof(T)) == 0 &&
+               memcmp(w2.data(), w2b.data(), w2.size() * sizeof(T)) == 0;
+        snprintf(name, sizeof name, "append %s untouched / L21 = V^T / repeatable", tag);
+        report(name, same ? 0.0 : 1.0, 0.0);
+        // L22
+        auto L = [&](int i, int j) -> R { return j <= i ? (R)a1[(size_t)(n + i) * ld + n + j] : (R)0; };
+        double worst = 0;
+        for (int i = 0; i < q; ++i)
+            for (int j = 0; j <= i; ++j) {
+                R s = 0, a = 0;
+                for (int k = 0; k <= j; ++k) { s += L(i, k) * L(j, k); a += fabsl(L(i, k) * L(j, k)); }
+                const R k22 = (R)hA[(size_t)(n + i) * ld + n + j];
+                const R res = fabsl(k22 - gram[(size_t)i * q + j] - s), scale = fabsl(k22) + agram[(size_t)i * q + j] + a;
+                worst = std::max(worst, std::isfinite((double)res) ? (double)(res / (eps * scale)) : INFINITY);
+            }
+        snprintf(name, sizeof name, "append %s |K22 - V^T V - L22 L22^T| (units of eps)", tag);
+        report(name, worst, n + q + 1);
+        // w2 against substitution in 80 bits with the device's L22; the tolerance needs |L22^{-1}|
+        {
+            std::vector<R> inv((size_t)q * q, 0), t(q), at(q);
+            for (int c = 0; c < q; ++c)
+                for (int i = c; i < q; ++i) {
+                    R s = i == c ? 1 : 0;
+                    for (int k = c; k < i; ++k) s -= L(i, k) * inv[(size_t)k * q + c];
+                    inv[(size_t)i * q + c] = s / L(i, i);
+                }
+            for (int i = 0; i < q; ++i) {
+                R s = hr2[i], a = fabsl((R)hr2[i]);
+                for (int k = 0; k < n; ++k) { const R p = (R)hV[(size_t)k * q + i] * (R)hw1[k]; s -= p; a += fabsl(p); }
+                t[i] = s; at[i] = a;
+            }
+            worst = 0;
+            for (int i = 0; i < q; ++i) {
+                R want = 0, tol = 0;
+                for (int k = 0; k <= i; ++k) { want += inv[(size_t)i * q + k] * t[k]; tol += fabsl(inv[(size_t)i * q + k]) * at[k]; }
+                const R err = fabsl((R)w2[i] - want);
+                worst = std::max(worst, std::isfinite((double)err) ? (double)(err / (eps * tol)) : INFINITY);
+            }
+            snprintf(name, sizeof name, "append %s w2 = L22^{-1} (r2 - V^T w1) (units of eps)", tag);
+            report(name, worst, n + q + 1);
+        }
+        // the touched diagonal-block inverses of the grown factor
+        worst = 0;
+        bool shape_ok = true;
+        for (int g = keep; g < nblk; ++g) {
+            const int nv = std::min(128, m - 128 * g);
+            auto Lg = [&](int i, int j) -> R { return (i < nv && j <= i) ? (R)a1[(size_t)(128 * g + i) * ld + 128 * g + j] : (R)(i == j ? 1 : 0); };
+            const T* D = d1.data() + (size_t)g * 128 * 128;
+            for (int i = 0; i < 128; ++i)
+                for (int j = 0; j < 128; ++j) {
+                    if (j > i) { shape_ok = shape_ok && D[i * 128 + j] == (T)0; continue; }
+                    if (i >= nv) { shape_ok = shape_ok && D[i * 128 + j] == (T)(i == j ? 1 : 0); continue; }
+                    R s = 0, a = 0;
+                    for (int k = j; k <= i; ++k) { s += (R)D[i * 128 + k] * Lg(k, j); a += fabsl((R)D[i * 128 + k] * Lg(k, j)); }
+                    const R res = fabsl(s - (i == j ? 1 : 0));
+                    worst = std::max(worst, std::isfinite((double)res) ? (double)(res / (eps * a)) : INFINITY);
+                }
+        }
+        snprintf(name, sizeof name, "append %s |D L - I| of the touched 128-blocks (units of eps)", tag);
+        report(name, shape_ok ? worst : INFINITY, 129);
+        // without a residual: the same factor;   a non-positive pivot: info = n + its order
+        std::vector<T> a3, d3, w3;
+        const int inf3 = run(hA, false, a3, d3, w3);
+        bool ok = inf3 == 0 && memcmp(a1.data(), a3.data(), a1.size() * sizeof(T)) == 0 && memcmp(d1.data(), d3.data(), d1.size() * sizeof(T)) == 0 &&
+                  memcmp(w3.data(), hr2.data(), w3.size() * sizeof(T)) == 0;
+        const int jbad = q / 2;
+        std::vector<T> hB = hA;
+        hB[(size_t)(n + jbad) * ld + n + jbad] = (T)(gram[(size_t)jbad * q + jbad] * 0.5L);      // below V^T V alone: the pivot is negative
+        const int inf4 = run(hB, false, a3, d3, w3);
+        ok = ok && inf4 == n + jbad + 1;
+        for (int i = 0; i < n && ok; ++i) ok = memcmp(&a3[(size_t)i * ld], &hA[(size_t)i * ld], (size_t)ld * sizeof(T)) == 0;
+        snprintf(name, sizeof name, "append %s no residual: same factor / info = n + j (got %d, want %d)", tag, inf4, n + jbad + 1);
+        report(name, ok ? 0.0 : 1.0, 0.0);
+    }
+    // workspace size and argument codes (nothing is launched)
+    Dev<T> buf(4096);
+    Dev<int> info(1);
+    int bad = 0;
+    bad += gpk_version() < 112;
+    bad += gpk_potrf_border_ws_elems(1000, 9) <= 0 || gpk_potrf_border_ws_elems(0, 9) != 0 || gpk_potrf_border_ws_elems(10, 0) != 0 ||
+           gpk_potrf_border_ws_elems(10, GPK_BORDER_MAX + 1) != 0;
+    bad += gpk_potrf_border(7, buf.p, 20, 4, 24, buf.p, 4, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -1;
+    bad += gpk_potrf_border(DT<T>::v, nullptr, 20, 4, 24, buf.p, 4, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -2;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 0, 4, 24, buf.p, 4, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -3;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 0, 24, buf.p, 4, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -4;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 129, 200, buf.p, 129, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -4;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 23, buf.p, 4, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -5;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, nullptr, 4, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -6;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, buf.p, 3, buf.p, buf.p, buf.p, info.p, buf.p, nullptr) != -7;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, buf.p, 4, nullptr, buf.p, buf.p, info.p, buf.p, nullptr) != -8;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, buf.p, 4, buf.p, nullptr, buf.p, info.p, buf.p, nullptr) != -9;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, buf.p, 4, buf.p, buf.p, nullptr, info.p, buf.p, nullptr) != -10;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, buf.p, 4, buf.p, buf.p, buf.p, nullptr, buf.p, nullptr) != -11;
+    bad += gpk_potrf_border(DT<T>::v, buf.p, 20, 4, 24, buf.p, 4, buf.p, buf.p, buf.p, info.p, nullptr, nullptr) != -12;
+    report(std::string("append ") + DT<T>::name() + " version, workspace size and argument codes", bad, 0.0);
+}
+
 int main(int argc, char** argv) {
     bool do_perf = false, only_perf = false;
     for (int i = 1; i + 2 < argc; ++i)     // --set KEY VALUE: tuning knobs (gpk_debug_set)
@@ -3072,6 +3244,11 @@ int main(int argc, char** argv) {
             printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
             return g_fail ? 1 : 0;
         }
+        if (!strcmp(argv[i], "--append")) {                    // only the checks of the bordered factorisation (gpk_potrf_border)
+            test_append<double>(); test_append<float>();
+            printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
+            return g_fail ? 1 : 0;
+        }
         if (!strcmp(argv[i], "--potrf")) {                     // only the factorisation checks (plain + look-ahead)
             test_potrf<double>(); test_potrf<float>();
             test_lookahead<double>(); test_lookahead<float>();
@@ -3148,6 +3325,7 @@ int main(int argc, char** argv) {
         test_scaled<double>(); test_scaled<float>();
         test_potrf_vjp<double>(); test_potrf_vjp<float>();
         test_nuclear_norm<double>(); test_nuclear_norm<float>();
+        test_append<double>(); test_append<float>();
         printf("SUMMARY pass=%d fail=%d\n", g_pass, g_fail);
     }
     if (do_perf) { perf<double>(); perf<float>(); }

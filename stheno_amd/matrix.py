@@ -84,6 +84,22 @@ class _Config:
     #: True / False: always / never (factors of kernel matrices; a ``Dense`` handed in by the user is never refined).
     refine_solves = "auto"
     refine_kappa = {torch.float64: 1e9}
+    #: A factor that grows (:meth:`Chol.append`) lives in a square capacity buffer whose order is a multiple of 128.  When a buffer is
+    #: allocated -- the first append to a factor, an append that does not fit, a branch -- its order is
+    #: ``ceil128(n + q + max(append_min_rows, append_growth * n))``: room for ``append_growth * n`` further rows, so a run of T appends
+    #: of a few points each copies the factor once every ``append_growth * n / q`` steps (geometric growth: O(log T) copies of O(n^2)
+    #: each against T solves of O(n^2 q), a constant number for any run that less than doubles its data) while the buffer holds at most
+    #: ``(1 + append_growth)^2`` = 1.56 times the factor's elements.  A larger fraction buys fewer copies with memory that the
+    #: N = 16384 fp64 factor (2.1 GB) does not have to spare twice.
+    append_growth = 0.25
+    append_min_rows = 256
+    #: ``Observations.append`` refactorises from scratch (the lazy, differentiable plain ``Observations``) instead of growing the factor
+    #: when one append brings more than this fraction of the current ``n``: the measured crossover of scripts/time_append.py
+    #: (profiles/README.md, "Factor append": at n = 16385 and q = 1024, q / n = 1 / 16, the append + prediction takes 39.2 ms against
+    #: 41.4 ms from scratch in fp64 and 26.3 against 22.8 ms in fp32 -- the first row of the table at which either dtype loses; at
+    #: q = 128 it takes 13.8 against 36.2 and 8.6 against 19.9).
+    #: ``None``: never fall back for size.
+    append_refactor_fraction = 1.0 / 16.0
 
 
 config = _Config()
@@ -187,6 +203,16 @@ def _solve_block(n, nrhs, fp64=True):
 
 #: rows of the right-hand side's strip under the matrix (``gpk.h``: GPK_ROWS_RHS_STRIP)
 RHS_STRIP = 64
+#: most rows one call of ``gpk_potrf_border`` appends (``gpk.h``: GPK_BORDER_MAX)
+BORDER_MAX = 128
+
+
+class _GrowBuffer:
+    """The square capacity buffer a growing factor lives in (:meth:`Chol.append`) and how many of its rows hold the factor: shared by
+    the factors that are views of it; only the one whose order is ``filled`` may write behind its last row."""
+
+    def __init__(self, buf, filled):
+        self.buf, self.filled = buf, filled
 
 
 class Chol:
@@ -209,6 +235,8 @@ class Chol:
         self.refine = False           # one refinement step behind every solve (config.refine_solves; set by the matrix that owns the factor)
         self.refined = 0              # (how many solves took it; the tests ask)
         self._residuals = {}
+        self._grow = None             # the capacity buffer this factor is a view of, once it has been appended to (or came from an append)
+        self.appended_residual = None
 
     @classmethod
     def factor_(cls, a, rhs=None):
@@ -283,6 +311,94 @@ class Chol:
         if rhs_row:
             return c, buf[n:-RHS_STRIP, :n_true], buf[-RHS_STRIP, :n_true].unsqueeze(-1)
         return c, buf[n:, :n_true]
+
+    def _remembered(self, source=None):
+        """The whitened residual filed with this factor (under ``source``, if given) that is still valid, as (n, 1); else ``None``."""
+        for src, ver, w in self._residuals.values():
+            if (source is None or src is source) and ver is not None and _version_of(src) == ver and tuple(w.shape) == (self.n, 1):
+                return w
+        return None
+
+    def _room_for(self, q, q_left):
+        """The capacity buffer the next ``q`` rows go into (``q_left >= q``: what this append still brings): the factor's own while it
+        is the buffer's latest state and the rows fit, else a new one with the factor copied in (``config.append_growth``) -- the first
+        append, growth, or a BRANCH: a second continuation of a factor somebody has already appended to must not write into the rows
+        the first continuation owns."""
+        g, n = self._grow, self.n
+        if g is not None and g.filled == n and n + q <= g.buf.shape[0]:
+            return g
+        cap = -(-(n + q_left + max(int(config.append_min_rows), int(config.append_growth * n))) // 128) * 128
+        buf = torch.empty((cap, cap), dtype=self.l.dtype, device=self.l.device)
+        be = ops.get_backend()
+        if getattr(be, "name", "") == "hip":
+            be.copy(self.l, out=buf[:n, :n])          # (gpk_copy2d; the square: the lower triangle and whatever lies above it)
+        else:
+            buf[:n, :n].copy_(self.l)
+        return _GrowBuffer(buf, n)
+
+    def append(self, k12, k22_lower, r2=None, source=None):
+        """The factor of the BORDERED matrix ``[[A, k12], [k12^T, K22]]`` as a new :class:`Chol` of order ``n + q``, grown from this one
+        instead of refactorised: ``k12`` (n, q), ``k22_lower`` (q, q; its lower triangle is read, diagonal additions in).  Unbatched;
+        any ``q``, in chunks of at most 128 (``gpk.h``: GPK_BORDER_MAX); per chunk ``V = self.solve(k12 chunk)`` on the existing solve,
+        then ``gpk_potrf_border``: O(n^2 q) instead of (n + q)^3 / 3.
+        The new factor is the ``[:n+q, :n+q]`` view of a capacity buffer (:meth:`_room_for`) that later appends write in place; this
+        factor keeps its ``[:n, :n]`` view of it and stays valid.  The new factor has its own ``dinv`` (the block this one filled only
+        partly is rewritten), merged inverses are rebuilt on demand; ``refine`` is inherited, ``lookahead_*`` / ``rows_under`` are not.
+        ``r2`` (q values, the new rows of the residual ``y - m(x)``): if this factor remembers the whitened residual of its own rows
+        (under ``source``, when given), the new factor's is ``cat(w1, w2)``, handed back as ``appended_residual`` ((n + q, 1); else
+        ``None``) for the caller to file under the concatenated data (:meth:`remember_residual`).
+        ``info`` goes the way of :meth:`factor_`: checked at once or when the enclosing ``deferred_checks()`` block ends, the order
+        of a non-positive pivot counted in the grown matrix."""
+        if self.l.dim() != 2:
+            raise NotImplementedError("Chol.append is implemented for unbatched factors")
+        self.vetted()
+        be = ops.get_backend()
+        n = self.n
+        if k12.dim() != 2 or k12.shape[0] != n or k22_lower.dim() != 2 or tuple(k22_lower.shape) != (k12.shape[1],) * 2:
+            raise ValueError(f"append: k12 is (n, q) and k22_lower (q, q) for a factor of order n = {n}")
+        q = k12.shape[1]
+        if q == 0:
+            return self
+        w = None
+        if r2 is not None:
+            w = self._remembered(source)
+            if w is not None:
+                r2 = r2.detach().reshape(-1).clone(memory_format=torch.contiguous_format)
+                if r2.shape[0] != q:
+                    raise ValueError("append: r2 has q values")
+        cur = self
+        for c0 in range(0, q, BORDER_MAX):
+            c1 = min(q, c0 + BORDER_MAX)
+            qc, m = c1 - c0, n + c0
+            col = k12[:, c0:c1]
+            if c0:
+                col = torch.cat([col, k22_lower[c0:c1, :c0].transpose(0, 1)], dim=0)      # (K22 is symmetric: its rows above the chunk)
+            v = cur.solve(col)
+            grow = cur._room_for(qc, q - c0)
+            buf = grow.buf
+            buf[m : m + qc, m : m + qc].copy_(k22_lower[c0:c1, c0:c1])
+            dinv = None
+            if cur.dinv is not None:
+                dinv = torch.empty((1, (m + qc + 127) // 128, 128, 128), dtype=buf.dtype, device=buf.device)
+                keep = m // 128
+                if keep:
+                    dinv[0, :keep].copy_(cur.dinv.reshape(-1, 128, 128)[:keep])
+            r2c = r2[c0:c1] if w is not None else None
+            info = be.potrf_border(buf, m, qc, v, dinv, w.reshape(-1).contiguous() if w is not None else None, r2c)
+            grow.filled = m + qc
+            new = Chol(buf[: m + qc, : m + qc], dinv, info)
+            new._grow = grow
+            new.refine = self.refine
+            if w is not None:
+                w = torch.cat([w.reshape(-1, 1), r2c.reshape(-1, 1)], dim=0)
+            if config.check_info:
+                if _deferred_state.pending is not None:
+                    _deferred_state.pending.append(new)
+                else:
+                    new.check()
+            cur = new
+        cur.appended_residual = w
+        return cur
 
     def remember_residual(self, source, w):
         """File ``w = L^{-1} (y - 0)`` under the data tensor ``y`` it came from (see :meth:`solve_residual`): the log-density of the same

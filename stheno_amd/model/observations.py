@@ -145,6 +145,30 @@ class AbstractObservations:
     def posterior_mean(self, measure, p):  # pragma: no cover
         raise NotImplementedError("Posterior mean construction not implemented.")
 
+    def _like_self(self, *args):
+        return type(self)(*args)
+
+    def append(self, fdd_new, y_new):
+        """These observations with ``(fdd_new, y_new)`` behind them: by definition the same kind of observations on the concatenated
+        data -- the inputs, the noise (block-diagonal; diagonal where both are) and ``y`` concatenated, NaN rows of ``y_new`` dropped as
+        at construction.  Lazy and differentiable like any freshly built observations.  (:class:`Observations` grows the factor it
+        already holds where that applies.)"""
+        new = Observations(fdd_new, y_new)           # (y as a column, missing rows dropped)
+        if _k.num_elements(self.fdd.x) == 0:
+            return self._like_self(new.fdd, new.y)
+        return self._concatenated(new.fdd, new.y)
+
+    def _concatenated(self, fdd_new, y_new):
+        p, x, xn = self.fdd.p, getattr(self.fdd, "_xr", None), getattr(fdd_new, "_xr", None)
+        if (fdd_new.p is p and not isinstance(p, int) and torch.is_tensor(x) and torch.is_tensor(xn) and x.dim() == xn.dim()
+                and tuple(x.shape[:-2]) == tuple(xn.shape[:-2]) and x.shape[-1] == xn.shape[-1]):
+            noise = _block_diag_noise((self.fdd, fdd_new))
+            a, b = self.fdd.noise, fdd_new.noise
+            if isinstance(noise, Diagonal) and getattr(a, "host_min", None) is not None and getattr(b, "host_min", None) is not None:
+                noise.host_min = min(a.host_min, b.host_min)      # (what the host knows about the diagonal: KernelDense.cond_bound)
+            return self._like_self(FDD(p, torch.cat([x, xn], dim=-2), noise), torch.cat([self.y, y_new], dim=-2))
+        return self._like_self((self.fdd, self.y), (fdd_new, y_new))
+
 
 class Observations(AbstractObservations):
     """Exact conditioning (``observations.py:112-168``)."""
@@ -171,6 +195,72 @@ class Observations(AbstractObservations):
                 K_x = _kernel_matrix(measure.kernels[p], self.fdd._xr, self.fdd.noise)
             self._K_x[measure] = K_x
             return K_x
+
+    def append(self, fdd_new, y_new):
+        """``Observations`` on the concatenated data (:meth:`AbstractObservations.append`), with the Cholesky factors this object
+        already holds GROWN instead of rebuilt: for every measure whose ``K_x`` has been factorised, ``k(x, x_new)`` and the lower
+        triangle of ``k(x_new) + noise + epsilon`` are evaluated (O(N q D)), :meth:`Chol.append` borders the factor (O(N^2 q), against
+        N^3 / 3 for conditioning on everything again) and the new object's ``K_x`` of that measure starts out factorised; a whitened
+        residual the factor remembers is extended and filed under the concatenated ``y``.  A measure without a factor is left to build
+        lazily.  The result is indistinguishable from ``Observations`` on all the data at once, except for rounding and time.
+        The factor is grown only where nothing is cut off by it (:meth:`_can_grow`): one process, unbatched inputs of one dtype and
+        device, scalar / per-point / no noise, nothing behind the kernel, mean, noise, inputs or ``y`` that requires a gradient while
+        gradients are enabled, a backend with ``potrf_border`` -- and not when one append brings more than
+        ``config.append_refactor_fraction`` of the current points.  Everything else gets the plain, lazy, differentiable object."""
+        new = Observations(fdd_new, y_new)           # (y as a column, missing rows dropped)
+        fdd_new, y_new = new.fdd, new.y
+        if _k.num_elements(self.fdd.x) == 0:
+            return new
+        out = self._concatenated(fdd_new, y_new)
+        if not self._can_grow(fdd_new, y_new):
+            return out
+        from .. import learnable
+        p, x, xn = self.fdd.p, self.fdd._xr, fdd_new._xr
+        n, q = x.shape[-2], xn.shape[-2]
+        frac = config.append_refactor_fraction
+        if q == 0 or (frac is not None and q > frac * n):
+            return out
+        dvec = fdd_new.noise.diag() if isinstance(fdd_new.noise, Diagonal) else None
+        for measure, K in list(self._K_x.items()):
+            chol = getattr(K, "_chol", None)
+            if not isinstance(chol, Chol) or chol.l.dim() != 2 or chol.n != n or chol._error is not None:
+                continue
+            kernel, mean = measure.kernels[p], measure.means[p]
+            if not kernel.terms() or kernel.num_outputs(xn) != q:
+                continue
+            if torch.is_grad_enabled() and (learnable.kernel_requires_grad(kernel) or learnable.mean_requires_grad(mean)):
+                continue
+            k12 = kernel.pairwise(x, xn)
+            k22 = kernel.pairwise(xn, None, lower=True, diag_add=config.epsilon, diag_vec=dvec)
+            r2 = y_new if isinstance(mean, _k.ZeroMean) else y_new - mean(xn)
+            grown = chol.append(k12, k22, r2=r2, source=self.y)
+            K_new = KernelDense(kernel, out.fdd._xr, out.fdd.noise)
+            K_new._chol = grown
+            grown.refine = K_new.wants_refinement()
+            if grown.appended_residual is not None:
+                grown.remember_residual(out.y, grown.appended_residual)
+            out._K_x[measure] = K_new
+        return out
+
+    def _can_grow(self, fdd_new, y_new):
+        from .. import learnable
+        p = self.fdd.p
+        if fdd_new.p is not p or isinstance(p, int) or not hasattr(ops.get_backend(), "potrf_border"):
+            return False
+        x, xn = getattr(self.fdd, "_xr", None), getattr(fdd_new, "_xr", None)
+        if not (torch.is_tensor(x) and torch.is_tensor(xn) and x.dim() == 2 and xn.dim() == 2 and x.shape[-1] == xn.shape[-1]
+                and x.dtype == xn.dtype and x.device == xn.device and self.y.dim() == 2 and y_new.dim() == 2
+                and self.y.dtype == x.dtype and y_new.dtype == x.dtype and y_new.device == x.device):
+            return False
+        if p.kernel.num_outputs(x) != x.shape[-2]:
+            return False
+        for nz in (self.fdd.noise, fdd_new.noise):
+            if not (nz is None or isinstance(nz, Zero) or (isinstance(nz, Diagonal) and nz.diag().dim() == 1)):
+                return False
+        if torch.is_grad_enabled() and (learnable.density_requires_grad(p.kernel, x, self.fdd.noise, self.y)
+                                        or learnable.density_requires_grad(p.kernel, xn, fdd_new.noise, y_new)):
+            return False
+        return True
 
     def posterior_kernel(self, measure, p_i, p_j):
         if _k.num_elements(self.fdd.x) == 0:
@@ -201,6 +291,9 @@ class AbstractPseudoObservations(AbstractObservations):
         self.u = u
         self._K_z, self._elbo, self._mu, self._A, self._parts = (weakref.WeakKeyDictionary() for _ in range(5))
         self._links = weakref.WeakKeyDictionary()
+
+    def _like_self(self, *args):
+        return type(self)(self.u, *args)
 
     def K_z(self, measure):
         if measure not in self._K_z:

@@ -441,6 +441,39 @@ class HipBackend:
         return dinv[:, : n // 128], info, dnb
 
     @_on_operand_device
+    def potrf_border(self, a_buf, n, q, v, dinv, w1=None, r2=None):
+        """Grow the factor in the leading ``n x n`` of ``a_buf`` by ``q <= 128`` rows IN PLACE (``gpk_potrf_border``): ``a_buf`` (rows,
+        cols >= n + q each, unit inner stride) holds ``L11`` in its rows ``< n`` and the lower triangle of ``K22`` (diagonal additions in)
+        at ``[n:n+q, n:n+q]``; ``v = L11^{-1} K12`` (n, q), unit inner stride.  On return rows ``n .. n + q`` hold ``[V^T, L22]``.
+        ``dinv``: ``ceil((n + q) / 128)`` contiguous 128 x 128 blocks, those of ``L11`` in front; the blocks from ``n // 128`` on are
+        written.  ``w1`` (n values, ``L11^{-1} r1``) and ``r2`` (q values, contiguous; overwritten by ``L22^{-1} (r2 - V^T w1)``): both or
+        neither.  Returns ``info`` (one int32: 0, or the order of the leading minor that is not positive definite)."""
+        n, q = int(n), int(q)
+        if a_buf.dim() != 2 or (a_buf.shape[1] > 1 and a_buf.stride(1) != 1) or min(a_buf.shape) < n + q:
+            raise ValueError("potrf_border: the buffer is one matrix of at least n + q rows and columns with unit inner stride")
+        if v.dim() != 2 or tuple(v.shape) != (n, q) or (q > 1 and v.stride(1) != 1):
+            raise ValueError("potrf_border: v is (n, q) with unit inner stride")
+        if (w1 is None) != (r2 is None):
+            raise ValueError("potrf_border: w1 and r2 are given together or not at all")
+        if dinv is None or not dinv.is_contiguous() or dinv.numel() < (n + q + 127) // 128 * 128 * 128:
+            raise ValueError("potrf_border: dinv holds ceil((n + q) / 128) contiguous blocks of 128 x 128")
+        if r2 is not None and (w1.numel() != n or r2.numel() != q or not w1.is_contiguous() or not r2.is_contiguous()):
+            raise ValueError("potrf_border: w1 has n and r2 has q contiguous values")
+        for t in (v, dinv, w1, r2):
+            if t is not None and (t.dtype != a_buf.dtype or t.device != a_buf.device):
+                raise TypeError("potrf_border: one dtype and one device")
+        self._check(a_buf, v, dinv, w1, r2)
+        info = torch.zeros((1,), dtype=torch.int32, device=a_buf.device)
+        ws = torch.empty((max(int(self.lib.gpk_potrf_border_ws_elems(n, q)), 1),), dtype=a_buf.dtype, device=a_buf.device)
+        ld = a_buf.stride(0) if a_buf.shape[0] > 1 else a_buf.shape[1]
+        ldv = v.stride(0) if n > 1 else q
+        code = self.lib.gpk_potrf_border(_dtype_id(a_buf), self._ptr(a_buf), n, q, ld, self._ptr(v), ldv, self._ptr(dinv), self._ptr(w1),
+                                         self._ptr(r2), self._ptr(info), self._ptr(ws), self._stream())
+        self._st(code, "gpk_potrf_border")
+        # (`ws` is released here: the caching allocator hands it to later work of THIS stream only)
+        return info
+
+    @_on_operand_device
     def rowreduce(self, z, w=None, *, want_dot=True, want_ss=False):
         """Row reductions of ``z`` (rows, n): ``dot[i] = sum_k z[i, k] w[k]`` and / or ``ss[i] = sum_k z[i, k]^2`` in one pass
         (``gpk_rowreduce``) -- the posterior mean and marginal variance from the TRANSPOSED whitened cross-covariance."""
@@ -912,12 +945,16 @@ class HipBackend:
         return v
 
     @_on_operand_device
-    def copy(self, src):
-        """Fresh copy of a (..., R, C) tensor (strided 2-D copy kernel; rows 16-byte aligned)."""
+    def copy(self, src, out=None):
+        """Fresh copy of a (..., R, C) tensor (strided 2-D copy kernel; rows 16-byte aligned); ``out``: into that tensor of the same
+        shape and dtype (unit inner stride) instead -- a view of a larger buffer, say."""
         s3, bshape = _as3(src)
-        self._check(s3)
+        self._check(s3, out)
         B, R, C = s3.shape
-        out = _alloc(bshape, R, C, src.dtype, src.device)
+        if out is None:
+            out = _alloc(bshape, R, C, src.dtype, src.device)
+        elif tuple(out.shape) != tuple(src.shape) or out.dtype != src.dtype:
+            raise ValueError("copy: the output has the source's shape and dtype")
         o3, _ = _as3_out(out)
         self._st(self.lib.gpk_copy2d(_dtype_id(s3), self._ptr(s3), _ld(s3), _bs(s3), self._ptr(o3), _ld(o3), _bs(o3),
                                      R, C, B, self._stream()), "gpk_copy2d")
