@@ -7,17 +7,21 @@ of the backend calls, the refusals, and every value and gradient BIT FOR BIT.
 
 The script uses the public API only (``GP``, ``Measure``, ``PseudoObs``, ``.logpdf``, ``.elbo``, ``post(xs).mean`` ...) and the package
 of the tree it lies in: run it at two commits and compare.  ``--backend host`` (the default) runs on the test-only NumPy backends of
-``tests/`` (``GroupsOracle``; ``BlockOracle`` for the models of ``tests/block_posterior_cases.py``, which need the Matern kinds);
+``tests/`` (``GroupsOracle``; ``BlockOracle`` for the models of ``tests/block_posterior_cases.py``, which need the Matern kinds;
+``BatchOracle`` for the batched posteriors of ``tests/batch_posterior_cases.py``, which need ``kmat_vjp_dense_batch``);
 ``--backend hip`` on ``libgpk.so``.  The dump holds, per scenario, the values and every gradient as raw bytes, the exception type of a
 refusal, and the trace: the backend methods in the order they were called, each with the shapes of its tensor arguments and the
 optional arguments it was given.  ``--trace`` writes the traces and exception types alone, as JSON: the machine-independent part of a
-host run (``tests/golden/learnable_backend_trace.json``, recorded before the admission layer moved into one module, is what
-``tests/test_learnable_trace_host.py`` replays against).
+host run (``tests/golden/learnable_backend_trace.json``, recorded before the admission layer moved into one module -- the entries of
+``LATER_SCENARIOS`` before the autograd functions came to share their stages --, is what ``tests/test_learnable_trace_host.py`` replays
+against).
 
-Shapes: N = 70 observations (one 64-wide tile and a partial one), N* = 9 test points, M = 13 inducing points, d = 2 or 3; every
+Shapes: N = 70 observations (one 64-wide tile and a partial one), N* = 9 test points, M = 13 inducing points, d = 2 or 3 (1 under the
+net of the function-scaled scenarios), a batch of 3; every
 scenario draws its data from a generator with a fixed seed.  The ``rows_*`` scenarios (a posterior predicted before anything
 factorised: the cross-covariance rides through the factorisation as rows under the matrix, ``WhitenedT``) run at N = 130 with
 ``matrix.config.posterior_rows_from`` / ``posterior_rows_min_points`` lowered to 128 / 8 for their duration."""
+import inspect
 import json
 import os
 import sys
@@ -31,11 +35,15 @@ import stheno_amd.torch as st  # noqa: E402
 from stheno_amd import ops  # noqa: E402
 from stheno_amd.matrix import config  # noqa: E402
 from stheno_amd.torch import EQ, RQ, Linear  # noqa: E402
+from tests import batch_posterior_cases as BP  # noqa: E402
 from tests import block_posterior_cases as BC  # noqa: E402
+from tests import function_product_cases as FP  # noqa: E402
 from tests import input_maps_cases as IC  # noqa: E402
 from tests import map_groups_cases as MC  # noqa: E402
+from tests import posterior_cov_cases as PC  # noqa: E402
 
 N, NS, M = 70, 9, 13
+NB = 3                       # (the batch of the batched scenarios)
 NR = 130                     # (the rows-path scenarios: an order the factorisation with rows takes once its thresholds are lowered)
 NOISE = 0.3
 DEV = ["cpu"]
@@ -75,37 +83,53 @@ def describe(v):
     return type(v).__name__
 
 
-class Recorder:
-    """Delegates everything to ``inner`` and keeps ``calls``: one line per method called from outside the backend."""
+def _defaults(fn):
+    """The default values in the signature of ``fn``, by parameter name."""
+    try:
+        params = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        return {}
+    return {p.name: p.default for p in params if p.default is not inspect.Parameter.empty}
 
-    def __init__(self, inner):
-        self._inner, self.calls = inner, []
+
+class Recorder:
+    """Delegates everything to ``inner`` and keeps ``calls``: one line per method called from outside the backend.  An optional argument
+    given as None is not listed; with ``drop_defaults`` neither is one given at the default value of the wrapped method's signature:
+    leaving it out is the same call."""
+
+    def __init__(self, inner, drop_defaults=False):
+        self._inner, self.calls, self._drop = inner, [], drop_defaults
 
     def __getattr__(self, name):
         attr = getattr(self._inner, name)
         if name.startswith("_") or not callable(attr):
             return attr
+        defaults = _defaults(attr)
+
+        def is_default(k, v):
+            return self._drop and k in defaults and type(v) is type(defaults[k]) and isinstance(v, (bool, int, float, str)) and v == defaults[k]
 
         def call(*args, **kw):
-            given = [describe(a) for a in args] + [f"{k}={describe(v)}" for k, v in sorted(kw.items()) if v is not None]
+            given = [describe(a) for a in args] + [f"{k}={describe(v)}" for k, v in sorted(kw.items()) if v is not None and not is_default(k, v)]
             self.calls.append(f"{name}({', '.join(given)})")
             return attr(*args, **kw)
 
         return call
 
 
-def install(which):
-    """Install the recording wrapper around the backend ``which`` (``"hip"``, or the name of a host backend); returns
-    ``(recorder, previous backend)``."""
+def install(which, drop_defaults=False):
+    """Install the recording wrapper (``Recorder(backend, drop_defaults)``) around the backend ``which`` (``"hip"``, or the name of a host
+    backend); returns ``(recorder, previous backend)``."""
     if which == "hip":
         prev = ops.set_backend(None)
-        rec = Recorder(ops.get_backend())
+        rec = Recorder(ops.get_backend(), drop_defaults)
         ops.set_backend(rec)                      # (it answers to the name "hip": installed as it is)
         return rec, prev
+    from tests.test_batch_posterior_grad_host import BatchOracle
     from tests.test_map_groups_grad_host import GroupsOracle
 
-    prev = ops.set_backend({"groups": GroupsOracle, "block": BC.BlockOracle}[which]())
-    rec = Recorder(ops.get_backend())             # around the host wrapper that serves the Delta kind and the derivative blocks, so
+    prev = ops.set_backend({"groups": GroupsOracle, "block": BC.BlockOracle, "batch": BatchOracle}[which]())
+    rec = Recorder(ops.get_backend(), drop_defaults)      # around the host wrapper that serves the Delta kind and the derivative blocks, so
     ops._backend = rec                            # that those are recorded too (`set_backend` would put a second one around it)
     return rec, prev
 
@@ -177,11 +201,11 @@ def logpdf_rq_table():
     return st.GP(v * RQ(a).stretch(s) + 0.4 * EQ())(T(x), NOISE).logpdf(T(y)), dict(alpha=a, v=v, s=s)
 
 
-def _batch(dx):
+def _batch(dx, per_batch=False):
     rng = np.random.default_rng(7)
-    xb, yb = rng.uniform(-2.0, 2.0, (3, N, 2)), rng.standard_normal((3, N, 1))
-    v, s = P(1.2), P(0.9)
-    txb, tyb, nzb = T(xb, dx), T(yb, True), T(rng.uniform(0.1, 0.4, (3, N)), True)
+    xb, yb = rng.uniform(-2.0, 2.0, (NB, N, 2)), rng.standard_normal((NB, N, 1))
+    v, s = (T(np.reshape([1.2, 0.7, 1.9], (NB, 1, 1)), True) if per_batch else P(1.2)), P(0.9)
+    txb, tyb, nzb = T(xb, dx), T(yb, True), T(rng.uniform(0.1, 0.4, (NB, N)), True)
     leaves = dict(v=v, s=s, y=tyb, noise=nzb)
     if dx:
         leaves["x"] = txb
@@ -194,6 +218,34 @@ def logpdf_batch():
 
 def logpdf_batch_dx():
     return _batch(True)
+
+
+def logpdf_batch_variance_per_entry():
+    return _batch(False, per_batch=True)
+
+
+def logpdf_batch_variance_per_entry_dx():
+    return _batch(True, per_batch=True)
+
+
+def _scaled(learn_fn):
+    """``(1 + a) * net + b`` of ``tests/function_product_cases.py`` (one input dimension: the net's): a function-scaled group beside a
+    plain one."""
+    x, y = FP.modulated_data(N)
+    p = FP.net_params()
+    net = FP.TanhNet(p, DEV[0]).requires_grad_(learn_fn)
+    f, _, _, _, t = FP.modulated_model(p, net, DEV[0])
+    if learn_fn:
+        t = dict(t, w1=net.l1.weight, b1=net.l1.bias, w2=net.l2.weight, b2=net.l2.bias)
+    return f(T(x), t["noise"]).logpdf(T(y)[:, None]), t
+
+
+def logpdf_scaled_learnable_function():
+    return _scaled(True)
+
+
+def logpdf_scaled_constant_function():
+    return _scaled(False)
 
 
 def _joint(learn_period):
@@ -373,6 +425,59 @@ def block_slope_predicted():
     return _block("slope")
 
 
+def _batch_exact(seed, what, model="rq", dx=False, dxs=False):
+    """A batch of exact posteriors under shared hyper-parameters, per-point noise: the models of ``tests/batch_posterior_cases.py``."""
+    p, _ = BP.values(model, NB, N, NS, 2, True, seed)
+    names = ["lv", "ls", "lnoise"] + list(BP.MODELS[model][2]) + ["y"] * (what != "var") + ["x"] * dx + ["xs"] * dxs
+    Pm = {k: T(p[k], k in names) for k in p}
+    f = st.GP(BP.MODELS[model][0](Pm))
+    fdd = (f | (f(Pm["x"], torch.exp(Pm["lnoise"])), Pm["y"]))(Pm["xs"])
+    outs = (fdd.mean,) if what == "mean" else (fdd.var_diag,) if what == "var" else tuple(fdd.marginals())
+    return outs, {k: Pm[k] for k in names}
+
+
+def batch_exact_mean_only():
+    return _batch_exact(27, "mean")
+
+
+def batch_exact_var_only():
+    return _batch_exact(28, "var")
+
+
+def batch_exact_both_dx_dxs():
+    return _batch_exact(29, "both", dx=True, dxs=True)
+
+
+def batch_exact_two_groups():
+    return _batch_exact(30, "both", model="two_groups", dxs=True)
+
+
+def _covariance(seed, kinds=("eq", "linear"), dx=False, dxs=False, n=N):
+    """The joint posterior covariance under a fixed cotangent: the models of ``tests/posterior_cov_cases.py``."""
+    p, fixed = PC.make(kinds, n=n, ns=NS, d=2, seed=seed)
+    names = ["lv", "lnoise"] + (["l12", "lp"] if kinds == PC.TWO_GROUP else ["ls"]) + ["x"] * dx + ["xs"] * dxs
+    Pm = PC.leaves(p, names, torch.float64, DEV[0])
+    loss, cov = PC.ours(kinds, Pm, "var", {k: T(v) for k, v in fixed.items()}, False)
+    return (cov,), {k: Pm[k] for k in names}, loss
+
+
+def covariance_parameters_only():
+    return _covariance(31)
+
+
+def covariance_dx_dxs():
+    return _covariance(32, dx=True, dxs=True)
+
+
+def covariance_two_groups():
+    return _covariance(33, kinds=PC.TWO_GROUP, dxs=True)
+
+
+@rows_path
+def rows_covariance():
+    return _covariance(34, dxs=True, n=NR)
+
+
 def _sparse(cls, seed, what, only_xs=False):
     x, xs, z, y = data(seed)
     g = not only_xs
@@ -466,6 +571,16 @@ SCENARIOS = [(fn.__name__, host, fn) for host, fn in [
     ("groups", refuse_derivative_under_a_joint_logpdf),
 ]]
 
+#: the scenarios added when the autograd functions came to share their stages.  Their traces do not list an optional argument given at
+#: its default (``Recorder(..., drop_defaults=True)``): one function leaves ``want_gradx`` out where another passes False for the same
+#: launch.  The scenarios above keep the listing their fixture entries were recorded with.
+LATER_SCENARIOS = [(fn.__name__, host, fn) for host, fn in [
+    ("groups", logpdf_scaled_learnable_function), ("groups", logpdf_scaled_constant_function),
+    ("batch", batch_exact_mean_only), ("batch", batch_exact_var_only), ("batch", batch_exact_both_dx_dxs), ("batch", batch_exact_two_groups),
+    ("groups", covariance_parameters_only), ("groups", covariance_dx_dxs), ("groups", covariance_two_groups), ("groups", rows_covariance),
+    ("groups", logpdf_batch_variance_per_entry), ("groups", logpdf_batch_variance_per_entry_dx),
+]]
+
 
 # ---------------------------------------------------------------------------------------------
 def raw(t):
@@ -474,7 +589,7 @@ def raw(t):
 
 def run_scenario(name, host, fn, backend="host"):
     """``(trace, arrays)`` of one scenario: ``trace`` = ``{"calls": [...], "raises": exception type or None}``."""
-    rec, prev = install("hip" if backend == "hip" else host)
+    rec, prev = install("hip" if backend == "hip" else host, drop_defaults=any(name == later for later, _, _ in LATER_SCENARIOS))
     old = st.B.epsilon
     st.B.epsilon = MC.EPS
     arrays, raised = {}, None
@@ -502,7 +617,7 @@ def run_scenario(name, host, fn, backend="host"):
 def dump(path, backend, trace_path):
     DEV[0] = "cuda" if backend == "hip" else "cpu"
     traces, out = {}, {}
-    for name, host, fn in SCENARIOS:
+    for name, host, fn in SCENARIOS + LATER_SCENARIOS:
         traces[name], arrays = run_scenario(name, host, fn, backend)
         out.update(arrays)
     if backend == "hip":
@@ -513,7 +628,7 @@ def dump(path, backend, trace_path):
         with open(trace_path, "w") as fh:
             json.dump(traces, fh, indent=0, sort_keys=True)
             fh.write("\n")
-    print(f"{len(SCENARIOS)} scenarios, {len(out) - 1} arrays, {sum(len(t['calls']) for t in traces.values())} backend calls -> {path}")
+    print(f"{len(SCENARIOS + LATER_SCENARIOS)} scenarios, {len(out) - 1} arrays, {sum(len(t['calls']) for t in traces.values())} backend calls -> {path}")
 
 
 def compare(pa, pb):
@@ -525,7 +640,7 @@ def compare(pa, pb):
             bad += [f"trace of {s}" for s in sorted(set(ta) | set(tb)) if ta.get(s) != tb.get(s)]
         elif a[name].shape != b[name].shape or a[name].dtype != b[name].dtype or a[name].tobytes() != b[name].tobytes():
             bad.append(name)
-    print(f"{len(SCENARIOS)} scenarios, {len(a.files) - 1} / {len(b.files) - 1} arrays compared, {len(bad)} differ" + "".join(f"\n  {n}" for n in bad))
+    print(f"{len(SCENARIOS + LATER_SCENARIOS)} scenarios, {len(a.files) - 1} / {len(b.files) - 1} arrays compared, {len(bad)} differ" + "".join(f"\n  {n}" for n in bad))
     return 1 if bad else 0
 
 

@@ -20,6 +20,13 @@ per-dimension length scales, the periodic embedding), formed in torch by the cal
 the reductions against it run once per group, on that group's term table and mapped inputs, and each group's input gradient goes back to
 torch, which carries it through the map to its parameter and to ``x``.  One group is the plain case: the same launches as ever.
 
+A stage that several functions share is written once, as a plain function in front of its first user: the tail of every log-density
+forward (``_density``); the pieces of its backward (``_inverse_parts``, ``_cotangent``, ``_grad_inputs``); the cotangents the
+posterior-marginal backwards start from (``_output_cotangents``, ``_posterior_cotangents``) and their reduction through ``k(x, xs)``
+(``_through_cross``), for one posterior or a batch alike; the rank-two update of an explicit cotangent (``_rank_two_``); the walk over
+the blocks of several processes (``_walk_blocks``); and the way from the per-term sums to the parameters' gradients (``_param_grads``,
+``_sum_param_grads``).  A group between one function on both sides (``f * fn``) is a case of ``_GPLogpdf``, not a function of its own.
+
 The posterior marginals (``post(xs).mean`` / ``.var_diag`` / ``.marginals()`` / ``.marginal_credible_bounds()``) have three functions
 further down: ``_PosteriorMarginals`` (an exact posterior of one process predicted from its own observations; a batch of them under
 shared hyper-parameters: ``_BatchedPosteriorMarginals``, every reduction one ``gpk_kmat_vjp_dense_batch`` launch), ``_BlockPosteriorMarginals``
@@ -103,22 +110,10 @@ def check_input_dims(u):
 
 def _unpack(kinds, params):
     """``(terms, values)``: the host descriptor for the fused kernels and the parameters' values
-    ``(variances, scales, alphas or None)`` as floats."""
+    ``(variances, scales, alphas or None)`` as floats.  A parameter that comes once per batch entry (a ``(B, 1, 1)`` tensor) stays on the
+    device, as a detached fp64 vector ``(B,)``, in the descriptor (``ops.KTerms``, per batch) and in the values."""
     nt = len(kinds)
-    if any(torch.is_tensor(p) and p.numel() > 1 for p in params):
-        return _unpack_per_batch(kinds, params)
-    variances = [float(v) for v in params[:nt]]
-    scales = [float(v) for v in params[nt:2 * nt]]
-    alphas = [float(v) for v in params[2 * nt:3 * nt]] if len(params) > 2 * nt else None
-    shapes = None if alphas is None else [a if k in ops._SHAPED else None for k, a in zip(kinds, alphas)]
-    return ops.KTerms(list(zip(kinds, variances, scales)), shapes), (variances, scales, alphas)
-
-
-def _unpack_per_batch(kinds, params):
-    """``_unpack`` where some parameter comes once per batch entry (a ``(B, 1, 1)`` tensor): its values stay on the device, as a detached
-    fp64 vector ``(B,)``, in the descriptor (``ops.KTerms``, per batch) and in the values; the scalar parameters are floats as ever."""
-    nt = len(kinds)
-    vals = [p.detach().reshape(-1).to(torch.float64) if p.numel() > 1 else float(p) for p in params]
+    vals = [p.detach().reshape(-1).to(torch.float64) if torch.is_tensor(p) and p.numel() > 1 else float(p) for p in params]
     variances, scales = vals[:nt], vals[nt:2 * nt]
     alphas = vals[2 * nt:3 * nt] if len(params) > 2 * nt else None
     shapes = None if alphas is None else [a if k in ops._SHAPED else None for k, a in zip(kinds, alphas)]
@@ -153,6 +148,25 @@ def _param_grads(kinds, values, S, meta, wgt=1.0):
     return [None if g_ is None else g_.to(device=dev, dtype=dt) for g_, (dev, dt) in zip(gr, meta)]
 
 
+def _sum_param_grads(groups, S):
+    """The gradients of the flat parameter list of ``groups`` (``_param_grads``, group after group) from one table of sums per group."""
+    grads = []
+    for grp, S_g in zip(groups, S):
+        grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
+    return grads
+
+
+def _density(be, k, r):
+    """The tail of every log-density forward: ``k`` (the lower triangle of the covariance, jitter and noise on its diagonal) is factorised
+    in place; ``r`` (n, C), or (B, n, 1) against a batch of matrices.  Returns ``(log-densities (C,) or (B,), factor, w = L^{-1} r)``."""
+    chol = Chol.factor_(k)
+    w = chol.solve(r)                                            # L^{-1} r
+    _, ss = be.colreduce(w, want_ss=True)                        # (C,), or (B, 1)
+    if r.dim() == 3:
+        ss = ss[..., 0]
+    return -(chol.logdet() + r.shape[-2] * LOG_2_PI + ss) / 2, chol, w
+
+
 def _cotangent(be, kinv_lower, alpha, g):
     """``G = d logpdf / dK = 1/2 (alpha diag(g) alpha^T - sum(g) K^{-1})`` as an explicit symmetric (n, n) matrix, formed in the
     buffer of the lower triangle of ``K^{-1}`` (consumed): ``alpha = K^{-1} r`` (n, C), ``g`` the C output cotangents."""
@@ -179,8 +193,16 @@ def _inverse_parts(be, chol, w):
 
 
 def _zeros(rows, cols, like):
-    """An all-zero (rows, cols) operand read through a zero row stride (no rows x cols buffer), dtype and device of ``like``."""
-    return torch.zeros((1, cols), dtype=like.dtype, device=like.device).expand(rows, cols)
+    """An all-zero (rows, cols) operand read through a zero row stride (no rows x cols buffer): dtype, device and leading batch
+    dimension (another zero stride) of ``like``."""
+    lead = like.shape[:-2]
+    return torch.zeros((1,) * len(lead) + (1, cols), dtype=like.dtype, device=like.device).expand(*lead, rows, cols)
+
+
+def _rank_two_(be, G, alpha, beta):
+    """``G -= 1/2 (beta alpha^T + alpha beta^T)`` in place, as a GEMM of contraction length 2; vectors (n,), or (B, n) against a batch."""
+    return be.gemm(torch.stack([beta, alpha], dim=-1), torch.stack([alpha, beta], dim=-1), a_kmajor=True, b_kmajor=True, alpha=-0.5,
+                   beta=1.0, out=G)
 
 
 def _offsets(sizes):
@@ -242,58 +264,83 @@ def _walk_blocks(be, layout, sizes, values, meta, us, need_u, kbar, cbar=None):
 
 
 class _GPLogpdf(torch.autograd.Function):
+    """The log-density of one process.  A group may stand between one function on both sides, ``K = sum_g diag(s_g) k_g(u_g) diag(s_g)``
+    (a group without a function: ``s_g`` absent) -- the kernel of ``(1 + a) * net + b``.  ``s_g = fn(x)`` is formed in torch by the
+    caller and is an input here, so the graph carries the gradient on into the function's parameters."""
+
     @staticmethod
-    def forward(ctx, r, noise_vec, noise_mat, layout, *tensors):
-        """``layout`` = one ``(kinds, number of parameters)`` per group of terms; ``tensors`` = the groups' inputs ``u_g`` (n, D_g),
-        then their parameters group after group -- variances, scales (and shape parameters: ``_pack``; scalar tensors, any device);
-        ``noise_vec`` (n,) or None; ``noise_mat`` (n, n) dense noise covariance or None; ``r = y - mean`` (n, C).  Returns (C,)."""
+    def forward(ctx, r, noise_vec, noise_mat, layout, scaled, *tensors):
+        """``layout`` = one ``(kinds, number of parameters)`` per group of terms; ``scaled``: one bool per group; ``tensors`` = the
+        groups' inputs ``u_g`` (n, D_g), then one scale ``s_g`` (n,) per scaled group, then the parameters group after group --
+        variances, scales (and shape parameters: ``_pack``; scalar tensors, any device); ``noise_vec`` (n,) or None; ``noise_mat`` (n, n)
+        dense noise covariance or None; ``r = y - mean`` (n, C).  Returns (C,)."""
         be = ops.get_backend()
-        groups = _split_groups(layout, tensors)
-        n, C = r.shape
-        # the first group writes the lower triangle with the diagonal additions, the others add to it (as `Sum.pairwise` does)
-        k = be.kmat(groups[0].terms, groups[0].inputs[0], None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
-        for grp in groups[1:]:
-            be.kmat(grp.terms, grp.inputs[0], None, lower=True, out=k, accumulate=True)
+        ng, ns = len(layout), sum(scaled)
+        groups = _split_groups(layout, tensors[:ng] + tensors[ng + ns:])
+        it = iter(tensors[ng: ng + ns])
+        scales = [next(it).detach() if sc else None for sc in scaled]
+        k = None
+        for grp, s in zip(groups, scales):
+            # the first group writes the lower triangle with the (unscaled) diagonal additions, the others add to it (as `Sum.pairwise` does)
+            kw = dict(lower=True, diag_add=config.epsilon, diag_vec=noise_vec) if k is None else dict(lower=True, out=k, accumulate=True)
+            if s is None:
+                k = be.kmat(grp.terms, grp.inputs[0], None, **kw)
+            else:
+                k = be.kmat_scaled(grp.terms, grp.inputs[0], None, s, s, **kw)
         if noise_mat is not None:
             k += noise_mat                                       # (only the lower triangle is read from here on)
-        chol = Chol.factor_(k)
-        w = chol.solve(r)                                        # L^{-1} r
-        _, ss = be.colreduce(w, want_ss=True)
-        out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
-        ctx.chol, ctx.w, ctx.groups = chol, w, groups
+        out, ctx.chol, ctx.w = _density(be, k, r)
+        ctx.groups, ctx.scales = groups, scales
         ctx.has_noise, ctx.has_noise_mat = noise_vec is not None, noise_mat is not None
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         be = ops.get_backend()
-        chol, w, groups = ctx.chol, ctx.w, ctx.groups
+        chol, w, groups, scales = ctx.chol, ctx.w, ctx.groups, ctx.scales
         n, C = w.shape
         ng = len(groups)
+        any_scaled = any(s is not None for s in scales)
         if C > 8:
             raise NotImplementedError("backward through logpdf supports at most 8 columns of y")
-        need_u = [ctx.needs_input_grad[4 + i] for i in range(ng)]
+        need_u = [ctx.needs_input_grad[5 + i] for i in range(ng)]
         need_nm = ctx.has_noise_mat and ctx.needs_input_grad[2]
+        if any_scaled and any(need_u):
+            raise NotImplementedError("gradients with respect to the inputs of a function-scaled kernel are not implemented")
         for grp, need in zip(groups, need_u):
             if need:
                 check_input_dims(grp.inputs[0])
         g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
         _, kinv, alpha = _inverse_parts(be, chol, w)
         # several groups of which one passes a gradient to its inputs: every group reads the explicit cotangent once, its sums and its
-        # input gradient out of the same pass; otherwise the implicit form, one pass over the lower triangle of K^{-1} per group
-        dense = ng > 1 and any(need_u)
-        S, grad_us, diag_g = [None] * ng, [None] * ng, None
+        # input gradient out of the same pass -- and so under a scale, where a group has no implicit form; otherwise the implicit form,
+        # one pass over the lower triangle of K^{-1} per group
+        dense = (ng > 1 and any(need_u)) or any_scaled
+        S, grad_us, grad_s, diag_g = [None] * ng, [None] * ng, [], None
         if not dense:
             for i, grp in enumerate(groups):
                 S[i], _, dg = be.kmat_vjp(grp.terms, grp.inputs[0], kinv, alpha, g)
                 if i == 0:
                     diag_g = dg                                  # (the cotangent's diagonal: the same from every group)
         grad_nm = None
-        if any(need_u) or need_nm:
+        if dense or any(need_u) or need_nm:
             G = _cotangent(be, kinv, alpha, g)                   # explicit, in the buffer of K^{-1}
-            for i, grp in enumerate(groups):
+            pos = 5 + ng
+            for i, (grp, s) in enumerate(zip(groups, scales)):
                 u = grp.inputs[0]
-                if dense:
+                if s is not None:
+                    # d/d theta of sum_ij G_ij s_i s_j k_ij: the row factor in the cotangent G_r = diag(s) G, the column factor as `colscale`
+                    Gr = G * s[:, None]
+                    S[i], _, _ = be.kmat_vjp_dense(grp.terms, u, u, Gr, colscale=s)
+                    gs = None
+                    if ctx.needs_input_grad[pos]:
+                        # d/ds_j = 2 sum_i s_i G_ij k_ij (G and K are symmetric): the column sums of G_r . K -- never a scaled sum
+                        # divided by s_j, which may vanish
+                        _, colsum, _ = be.kmat_vjp_dense(grp.terms, u, u, Gr, want_colsum=True)
+                        gs = 2.0 * colsum
+                    grad_s.append(gs)
+                    pos += 1
+                elif dense:
                     S[i], _, gx = be.kmat_vjp_dense(grp.terms, u, u, G, want_gradx=need_u[i])
                     if need_u[i]:
                         grad_us[i] = 2.0 * gx
@@ -303,79 +350,9 @@ class _GPLogpdf(torch.autograd.Function):
                 diag_g = torch.diagonal(G).clone()
             if need_nm:
                 grad_nm = G                                      # d/d noise matrix: the cotangent of K itself
-        grads = []
-        for grp, S_g in zip(groups, S):
-            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
         grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype))
         grad_noise = diag_g if ctx.has_noise else None
-        return (grad_r, grad_noise, grad_nm, None, *grad_us, *grads)
-
-
-class _GPLogpdfScaled(torch.autograd.Function):
-    """``_GPLogpdf`` for a kernel with function-scaled groups, ``K = sum_g diag(s_g) k_g(u_g) diag(s_g)`` (a group without a function:
-    ``s_g`` absent) -- the kernel of ``(1 + a) * net + b``.  ``s_g = fn(x)`` is formed in torch by the caller and is an input here, so the
-    graph carries the gradient on into the function's parameters."""
-
-    @staticmethod
-    def forward(ctx, r, noise_vec, layout, scaled, *tensors):
-        """``scaled``: one bool per group; ``tensors`` = the groups' inputs ``u_g`` (n, D_g), then one scale ``s_g`` (n,) per scaled
-        group, then the parameters group after group (``_pack``).  Returns (C,)."""
-        be = ops.get_backend()
-        ng = len(layout)
-        ns = sum(scaled)
-        groups = _split_groups(layout, tensors[:ng] + tensors[ng + ns:])
-        it = iter(tensors[ng: ng + ns])
-        scales = [next(it).detach() if sc else None for sc in scaled]
-        n, C = r.shape
-        k = None
-        for grp, s in zip(groups, scales):
-            # the first group writes the lower triangle with the (unscaled) diagonal additions, the others add to it
-            kw = dict(lower=True, diag_add=config.epsilon, diag_vec=noise_vec) if k is None else dict(lower=True, out=k, accumulate=True)
-            if s is None:
-                k = be.kmat(grp.terms, grp.inputs[0], None, **kw)
-            else:
-                k = be.kmat_scaled(grp.terms, grp.inputs[0], None, s, s, **kw)
-        chol = Chol.factor_(k)
-        w = chol.solve(r)
-        _, ss = be.colreduce(w, want_ss=True)
-        out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
-        ctx.chol, ctx.w, ctx.groups, ctx.scales, ctx.has_noise = chol, w, groups, scales, noise_vec is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        be = ops.get_backend()
-        chol, w, groups, scales = ctx.chol, ctx.w, ctx.groups, ctx.scales
-        n, C = w.shape
-        ng, ns = len(groups), sum(s is not None for s in scales)
-        if C > 8:
-            raise NotImplementedError("backward through logpdf supports at most 8 columns of y")
-        if any(ctx.needs_input_grad[4: 4 + ng]):
-            raise NotImplementedError("gradients with respect to the inputs of a function-scaled kernel are not implemented")
-        g = [float(v) for v in grad_out.reshape(-1).tolist()]    # host sync: C scalars
-        _, kinv, alpha = _inverse_parts(be, chol, w)
-        G = _cotangent(be, kinv, alpha, g)                       # explicit: a scaled group has no implicit form
-        diag_g = torch.diagonal(G).clone()
-        grads, grad_s, pos = [], [], 4 + ng
-        for grp, s in zip(groups, scales):
-            u = grp.inputs[0]
-            if s is None:
-                S_g, _, _ = be.kmat_vjp_dense(grp.terms, u, u, G)
-            else:
-                # d/d theta of sum_ij G_ij s_i s_j k_ij: the row factor in the cotangent G_r = diag(s) G, the column factor as `colscale`
-                Gr = G * s[:, None]
-                S_g, _, _ = be.kmat_vjp_dense(grp.terms, u, u, Gr, colscale=s)
-                gs = None
-                if ctx.needs_input_grad[pos]:
-                    # d/ds_j = 2 sum_i s_i G_ij k_ij (G and K are symmetric): the column sums of G_r . K -- never a scaled sum divided
-                    # by s_j, which may vanish
-                    _, colsum, _ = be.kmat_vjp_dense(grp.terms, u, u, Gr, want_colsum=True)
-                    gs = 2.0 * colsum
-                grad_s.append(gs)
-                pos += 1
-            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
-        grad_r = -(alpha * grad_out.reshape(1, -1).to(alpha.dtype))
-        return (grad_r, diag_g if ctx.has_noise else None, None, None, *([None] * ng), *grad_s, *grads)
+        return (grad_r, grad_noise, grad_nm, None, None, *grad_us, *grad_s, *_sum_param_grads(groups, S))
 
 
 def gp_logpdf_scaled(groups, noise_vec, r):
@@ -383,7 +360,7 @@ def gp_logpdf_scaled(groups, noise_vec, r):
     ``[(k_g, u_g, s_g)]`` with ``s_g`` (n,) a torch expression in the graph, or None for a group without a function.  Unbatched."""
     layout, params = _pack_groups([kern for kern, _, _ in groups])
     scaled = tuple(s is not None for _, _, s in groups)
-    return _GPLogpdfScaled.apply(r, noise_vec, layout, scaled, *[u for _, u, _ in groups], *[s for _, _, s in groups if s is not None], *params)
+    return _GPLogpdf.apply(r, noise_vec, None, layout, scaled, *[u for _, u, _ in groups], *[s for _, _, s in groups if s is not None], *params)
 
 
 class _GPLogpdfBatched(torch.autograd.Function):
@@ -401,14 +378,9 @@ class _GPLogpdfBatched(torch.autograd.Function):
         """``layout`` / ``tensors`` as in ``_GPLogpdf``, ONE group: its inputs ``x`` (B, N, D), then its parameters."""
         be = ops.get_backend()
         (grp,) = _split_groups(layout, tensors)
-        x, terms = grp.inputs[0], grp.terms
-        n = r.shape[-2]
-        k = be.kmat(terms, x, None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
-        chol = Chol.factor_(k)
-        w = chol.solve(r)                                        # (B, N, 1)
-        _, ss = be.colreduce(w, want_ss=True)                    # (B, 1)
-        out = -(chol.logdet() + n * LOG_2_PI + ss[..., 0]) / 2   # (B,)
-        ctx.chol, ctx.w, ctx.group, ctx.has_noise = chol, w, grp, noise_vec is not None
+        k = be.kmat(grp.terms, grp.inputs[0], None, lower=True, diag_add=config.epsilon, diag_vec=noise_vec)
+        out, ctx.chol, ctx.w = _density(be, k, r)                # (B,), the batched factor, (B, N, 1)
+        ctx.group, ctx.has_noise = grp, noise_vec is not None
         ctx.param_shapes = [tuple(p.shape) for p in tensors[1:]]
         return out
 
@@ -461,15 +433,9 @@ class _JointLogpdf(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r, noise_vec, build, sizes, layout, nu, *tensors):
-        be = ops.get_backend()
-        n = r.shape[0]
-        k = build()                                              # lower block triangle + eps + noise on the diagonal
-        chol = Chol.factor_(k)
-        w = chol.solve(r)
-        _, ss = be.colreduce(w, want_ss=True)
-        out = -(chol.logdet() + n * LOG_2_PI + ss) / 2
+        out, ctx.chol, ctx.w = _density(ops.get_backend(), build(), r)      # (build: lower block triangle + eps + noise on the diagonal)
         params = tensors[nu:]
-        ctx.chol, ctx.w, ctx.sizes, ctx.layout, ctx.us = chol, w, sizes, layout, tensors[:nu]
+        ctx.sizes, ctx.layout, ctx.us = sizes, layout, tensors[:nu]
         ctx.has_noise = noise_vec is not None
         ctx.param_meta = [(p.device, p.dtype) for p in params]
         ctx.values = [float(p) for p in params]
@@ -505,7 +471,7 @@ def gp_logpdf(groups, noise_vec, r, noise_mat=None):
     if groups[0][1].dim() == 3:
         (x,) = [u for _, u in groups]
         return _GPLogpdfBatched.apply(r, noise_vec, layout, x, *params)
-    return _GPLogpdf.apply(r, noise_vec, noise_mat, layout, *[u for _, u in groups], *params)
+    return _GPLogpdf.apply(r, noise_vec, noise_mat, layout, (False,) * len(groups), *[u for _, u in groups], *params)
 
 
 def _diag_share(grp, x, g_kd, gr, gx, need_x):
@@ -649,10 +615,14 @@ class _SparseELBO(torch.autograd.Function):
         return (grad_r, grad_noise, None, None, grad_x, grad_z, *grads)
 
 
-def sparse_elbo(kernel, x, z, noise_vec, r, method):
-    """Differentiable VFE / FITC / DTC bound for ``r = y - m(x)`` with inducing inputs ``z``."""
+def _check_method(method):
     if method not in ("vfe", "fitc", "dtc"):
         raise ValueError(f'Invalid approximation method "{method}".')
+
+
+def sparse_elbo(kernel, x, z, noise_vec, r, method):
+    """Differentiable VFE / FITC / DTC bound for ``r = y - m(x)`` with inducing inputs ``z``."""
+    _check_method(method)
     layout, params = _pack_groups([kernel])
     return _SparseELBO.apply(r, noise_vec, {"vfe": 1.0, "dtc": 0.0, "fitc": -1.0}[method], layout, x, z, *params)
 
@@ -670,39 +640,83 @@ def sparse_elbo(kernel, x, z, noise_vec, r, method):
 #     dL/dK        = -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T)        (N x N, symmetric; its diagonal: d/dnoise)
 #     dL/dr        = beta
 # The cross cotangent is reduced by gpk_kmat_vjp_dense on (x, xs): the rank-1 part rides in its w / b operands, 2 diag(gs) in its
-# colscale; d/dxs takes the same reduction on (xs, x) over the explicit transpose.  dL/dK is reduced by gpk_kmat_vjp in its own form
+# colscale; d/dxs takes the same reduction on (xs, x) over the explicit transpose (_through_cross).  dL/dK is reduced by gpk_kmat_vjp in its own form
 # 1/2 (A diag(g) A^T - sum(g) S) with S = B diag(gs) B^T (ONE lower SYRK on the MFMA GEMM), A = [alpha + beta, alpha - beta, 0],
 # g = [-1/2, 1/2, 2] (the rank-2 part as a difference of squares); d/dx through K takes the explicit symmetric cotangent
 # (gpk_kmat_vjp_dense, x 2, as in the log-density).  The one new operation is the back-substitution with the transposed factor,
 # gpk_trsm_lower_t / gpk_trsv_lower_t: N^2 N* flops for B against N^3/3 for an explicit inverse.
 # ---------------------------------------------------------------------------------------------
-def _posterior_cotangents(be, ctx, g_mu, g_s, dt, dims=()):
-    """What the backward of the exact posterior marginals starts from, one process or several: ``(gm, gs, alpha, bm, beta)`` -- the
-    cotangents of ``mu`` and ``s`` (None for an output that has none; ``gs`` also for a loss of the mean only), ``alpha = K^{-1} r``,
-    ``bm = B = L^{-T} V`` (only with ``gs``: the N x N* back-substitution) and ``beta = B gm`` (without ``gs``: one single-column
-    back-substitution) -- or None when neither output has a cotangent.  ``dims``: the inputs whose gradient is wanted (``check_input_dims``
-    behind that answer, in front of the first launch)."""
-    chol, v = ctx.chol, ctx.v
-    gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
-    gs = g_s.to(dt).contiguous() if g_s is not None else None
-    if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
+def _output_cotangents(g_mu, g_s, has_mu, has_s, dt):
+    """``(gm, gs)``: the cotangents of the two outputs of a posterior-marginals function in the path's dtype, None for an output that has
+    none or that the forward returned as zeros (``has_mu`` / ``has_s``) -- ``gs`` also when it is all zero (one host read): a loss of the
+    mean only."""
+    gm = g_mu.to(dt).contiguous() if (g_mu is not None and has_mu) else None
+    gs = g_s.to(dt).contiguous() if (g_s is not None and has_s) else None
+    if gs is not None and not bool(torch.any(gs != 0)):
         gs = None
+    return gm, gs
+
+
+def _posterior_cotangents(be, ctx, g_mu, g_s, dt, dims=()):
+    """What the backward of the exact posterior marginals starts from, one process, a batch of them or several processes:
+    ``(gm, gs, alpha, bm, beta)`` -- the cotangents of ``mu`` and ``s`` (``_output_cotangents``), ``alpha = K^{-1} r``, ``bm = B = L^{-T} V``
+    (only with ``gs``: the N x N* back-substitution) and ``beta = B gm`` (without ``gs``: one single-column back-substitution) -- or None
+    when neither output has a cotangent.  With the batched factor every one of them has the leading batch dimension and each solve is ONE
+    batched launch.  ``dims``: the inputs whose gradient is wanted (``check_input_dims`` behind that answer, in front of the first launch)."""
+    chol, v = ctx.chol, ctx.v
+    gm, gs = _output_cotangents(g_mu, g_s, ctx.has_r, True, dt)
     if gm is None and gs is None:
         return None
     for u in dims:
         check_input_dims(u)
-    transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T)
-    alpha = chol.solve_t(ctx.w)[:, 0] if gm is not None else None  # K^{-1} r
+    transposed = hasattr(v, "zt")                                 # (the rows that rode through the factorisation: V^T; never a batch)
+    alpha = chol.solve_t(ctx.w)[..., 0] if gm is not None else None  # K^{-1} r
     bm = beta = None
     if gs is not None:
         # B = L^{-T} V: the N x N* back-substitution (its right-hand side is a private copy: the solve uses it up)
         bm = chol.solve_t_(v.plain() if transposed else be.copy(v))
         if gm is not None:
-            beta = be.gemv(bm, gm[:, None])[:, 0]
+            beta = be.gemv(bm, gm[..., None])[..., 0]
     else:
-        vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[:, None])[:, 0]
-        beta = chol.solve_t(vg[:, None])[:, 0]
+        vg = be.colreduce(v.zt, gm, want_dot=True, want_ss=False)[0] if transposed else be.gemv(v, gm[..., None])[..., 0]
+        beta = chol.solve_t(vg[..., None])[..., 0]
     return gm, gs, alpha, bm, beta
+
+
+def _marginals_forward(ctx, r, noise_vec, run, layout, tensors):
+    """The forward of ``_PosteriorMarginals`` and ``_BatchedPosteriorMarginals``: the plain path ``run()`` and what the backward keeps."""
+    chol, w, v, mu, s = run()
+    ctx.groups = _split_groups(layout, tensors, 2)
+    ctx.chol, ctx.w, ctx.v = chol, w, v
+    ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
+    ctx.set_materialize_grads(False)
+    if mu is None:
+        mu = torch.zeros_like(s)
+    return mu, s
+
+
+def _through_cross(be, groups, bm, cs, alpha, gm, need_x, need_xs):
+    """The cotangent ``alpha gm^T + B diag(cs)`` of ``k(x, xs)``, the same for every group, reduced per group on (x, xs) -- the rank-one
+    part in ``w`` / ``b``, ``cs = 2 gs`` in ``colscale``, ``B`` absent (``bm`` None): a zero operand of zero stride -- and, for ``d/dxs``,
+    on (xs, x) over the explicit transpose.  ``gpk_kmat_vjp_dense``, or ONE ``gpk_kmat_vjp_dense_batch`` launch over all entries for
+    batched inputs.  Returns ``(S, grad_x, grad_xs)``, one entry per group."""
+    ng = len(groups)
+    x0, xs0 = groups[0].inputs
+    n, ns = x0.shape[-2], xs0.shape[-2]
+    reduce = be.kmat_vjp_dense_batch if x0.dim() == 3 else be.kmat_vjp_dense
+    S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
+    g_t = None
+    for i, grp in enumerate(groups):
+        terms, (x, xs) = grp.terms, grp.inputs
+        S[i], _, grad_x[i] = reduce(terms, x, xs, bm if bm is not None else _zeros(n, ns, x0), colscale=cs, w=alpha, b=gm, want_gradx=need_x[i])
+        if need_xs[i]:
+            if g_t is None:
+                if bm is not None:
+                    g_t = be.scale_cols_(be.copy(bm), cs).transpose(-1, -2).contiguous()      # (N*, N): diag(cs) B^T, explicit
+                else:
+                    g_t = _zeros(ns, n, x0)
+            _, _, grad_xs[i] = reduce(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
+    return S, grad_x, grad_xs
 
 
 class _PosteriorMarginals(torch.autograd.Function):
@@ -713,22 +727,15 @@ class _PosteriorMarginals(torch.autograd.Function):
         ``L^{-1} k(x, xs)`` (N, N*) or its transpose as a ``WhitenedT``.  ``layout`` = one ``(kinds, number of parameters)`` per group of
         terms; ``tensors`` = per group ``x`` / ``xs`` as its fused kernels see them (behind the group's input map), then the groups'
         parameters; ``r`` (N, 1) or None (marginal variances only: ``mu`` comes back as zeros)."""
-        chol, w, v, mu, s = run()
-        ctx.groups = _split_groups(layout, tensors, 2)
-        ctx.chol, ctx.w, ctx.v = chol, w, v
-        ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
-        ctx.set_materialize_grads(False)
-        if mu is None:
-            mu = torch.zeros_like(s)
-        return mu, s
+        return _marginals_forward(ctx, r, noise_vec, run, layout, tensors)
 
     @staticmethod
     def backward(ctx, g_mu, g_s):
         be = ops.get_backend()
         groups = ctx.groups
         ng = len(groups)
-        x0, xs0 = groups[0].inputs
-        n, ns = x0.shape[0], xs0.shape[0]
+        x0 = groups[0].inputs[0]
+        n = x0.shape[0]
         dt, dev = x0.dtype, x0.device
         need_x = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
         need_xs = [ctx.needs_input_grad[5 + 2 * i] for i in range(ng)]
@@ -736,24 +743,7 @@ class _PosteriorMarginals(torch.autograd.Function):
         if pre is None:
             return (None,) * (4 + 2 * ng + sum(len(grp.meta) for grp in groups))
         gm, gs, alpha, bm, beta = pre
-        # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs), the same for every group
-        cs = 2.0 * gs if gs is not None else None
-        S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
-        g_t = None
-        for i, grp in enumerate(groups):
-            terms, (x, xs) = grp.terms, grp.inputs
-            S[i], _, grad_x[i] = be.kmat_vjp_dense(terms, x, xs, bm if bm is not None else _zeros(n, ns, x0), colscale=cs, w=alpha, b=gm,
-                                                   want_gradx=need_x[i])
-            if need_xs[i]:
-                if g_t is None:
-                    if bm is not None:
-                        g_t = be.copy(bm)
-                        be.scale_cols_(g_t, cs)
-                        g_t = g_t.t().contiguous()                       # (N*, N): 2 diag(gs) B^T, explicit
-                    else:
-                        g_t = _zeros(ns, n, x0)
-                _, _, grad_xs[i] = be.kmat_vjp_dense(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
-        del g_t
+        S, grad_x, grad_xs = _through_cross(be, groups, bm, 2.0 * gs if gs is not None else None, alpha, gm, need_x, need_xs)
         # through K: -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T) = 1/2 (A diag(g) A^T - sum(g) S)
         cols, g = [], []
         if gm is not None:
@@ -782,24 +772,22 @@ class _PosteriorMarginals(torch.autograd.Function):
             for i, grp in enumerate(groups):
                 if need_x[i]:
                     grad_x[i] = grad_x[i] + _grad_inputs(be, grp.terms, grp.inputs[0], G)
-        grads = []
-        for grp, S_g in zip(groups, S):
-            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
         grad_r = beta[:, None] if (beta is not None and ctx.needs_input_grad[0]) else None
         grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[1]) else None
         inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
-        return (grad_r, grad_noise, None, None, *inputs, *grads)
+        return (grad_r, grad_noise, None, None, *inputs, *_sum_param_grads(groups, S))
 
 
 # ---------------------------------------------------------------------------------------------
 # The same for a BATCH of independent exact posteriors under SHARED hyper-parameters: x (B, N, D), xs (B, N*, D), r (B, N, 1), noise
 # (B, N) -- a held-out predictive loss over B tasks, B acquisition ascents at once.  The forward is the plain batched path as it is; the
-# backward is the algebra above for all entries at once, on the batched factor: one batched back-substitution for B = L^{-T} V (or, for
-# a loss of the mean only, one single-column one for beta), and every reduction against a kernel matrix one launch of
-# gpk_kmat_vjp_dense_batch over all entries -- on (x, xs) with the rank-one part in w / b and 2 gs in colscale, on (xs, x) over the
-# explicit transpose for d/dxs, and on (x, x) over the explicit symmetric cotangent of K,
+# backward is the algebra above for all entries at once, in the same two functions (_posterior_cotangents, _through_cross) on the batched
+# factor: one batched back-substitution for B = L^{-T} V (or, for a loss of the mean only, one single-column one for beta), and every
+# reduction against a kernel matrix one launch of gpk_kmat_vjp_dense_batch over all entries -- on (x, xs) with the rank-one part in
+# w / b and 2 gs in colscale, on (xs, x) over the explicit transpose for d/dxs, and, the one stage of its own, on (x, x) over the
+# explicit symmetric cotangent of K,
 #     G = -B diag(gs) B^T - 1/2 (beta alpha^T + alpha beta^T)
-# (one batched lower GEMM, gpk_symmetrize, and the rank-two part as a GEMM of contraction length 2), whose diagonal is d/dnoise and
+# (one batched lower GEMM, gpk_symmetrize, and the rank-two part as a GEMM of contraction length 2: _rank_two_), whose diagonal is d/dnoise and
 # whose input gradient counts twice.  The launch gives the sums per entry; the parameters are shared, so their gradients come from the
 # sum over the batch.  The number of backend calls does not depend on B.
 # ---------------------------------------------------------------------------------------------
@@ -808,85 +796,41 @@ class _BatchedPosteriorMarginals(torch.autograd.Function):
     def forward(ctx, r, noise_vec, run, layout, *tensors):
         """As ``_PosteriorMarginals.forward``, every tensor with a leading batch dimension: ``run()`` -> ``(chol, w, v, mu, s)`` with the
         batched factor, ``w`` (B, N, 1), ``v`` (B, N, N*), ``mu`` / ``s`` (B, N*); per group ``x`` (B, N, D_g) / ``xs`` (B, N*, D_g)."""
-        chol, w, v, mu, s = run()
-        ctx.groups = _split_groups(layout, tensors, 2)
-        ctx.chol, ctx.w, ctx.v = chol, w, v
-        ctx.has_noise, ctx.has_r = noise_vec is not None, r is not None
-        ctx.set_materialize_grads(False)
-        if mu is None:
-            mu = torch.zeros_like(s)
-        return mu, s
+        return _marginals_forward(ctx, r, noise_vec, run, layout, tensors)
 
     @staticmethod
     def backward(ctx, g_mu, g_s):
         be = ops.get_backend()
-        groups, chol, v = ctx.groups, ctx.chol, ctx.v
+        groups = ctx.groups
         ng = len(groups)
-        x0, xs0 = groups[0].inputs
-        (nb, n), ns = x0.shape[:2], xs0.shape[1]
-        dt, dev = x0.dtype, x0.device
+        x0 = groups[0].inputs[0]
+        nb, n = x0.shape[:2]
         need_x = [ctx.needs_input_grad[4 + 2 * i] for i in range(ng)]
         need_xs = [ctx.needs_input_grad[5 + 2 * i] for i in range(ng)]
-        gm = g_mu.to(dt).contiguous() if (g_mu is not None and ctx.has_r) else None
-        gs = g_s.to(dt).contiguous() if g_s is not None else None
-        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
-            gs = None
-        if gm is None and gs is None:
+        pre = _posterior_cotangents(be, ctx, g_mu, g_s, x0.dtype, [grp.inputs[0] for grp, nx, nxs in zip(groups, need_x, need_xs) if nx or nxs])
+        if pre is None:
             return (None,) * (4 + 2 * ng + sum(len(grp.meta) for grp in groups))
-        for grp, nx, nxs in zip(groups, need_x, need_xs):
-            if nx or nxs:
-                check_input_dims(grp.inputs[0])
-
-        def zeros(rows, cols):
-            return torch.zeros((1, 1, cols), dtype=dt, device=dev).expand(nb, rows, cols)
-
-        alpha = chol.solve_t(ctx.w)[..., 0] if gm is not None else None            # K^{-1} r   (B, N)
-        bm = beta = None
-        if gs is not None:
-            bm = chol.solve_t_(be.copy(v))                                          # B = L^{-T} V: ONE batched back-substitution
-            if gm is not None:
-                beta = be.gemv(bm, gm[..., None])[..., 0]
-        else:
-            beta = chol.solve_t(be.gemv(v, gm[..., None]))[..., 0]
-        # through k(x, xs): cotangent alpha gm^T + 2 B diag(gs), the same for every group
-        cs = 2.0 * gs if gs is not None else None
-        S, grad_x, grad_xs = [None] * ng, [None] * ng, [None] * ng
-        g_t = None
-        for i, grp in enumerate(groups):
-            terms, (x, xs) = grp.terms, grp.inputs
-            S[i], _, grad_x[i] = be.kmat_vjp_dense_batch(terms, x, xs, bm if bm is not None else zeros(n, ns), colscale=cs, w=alpha, b=gm,
-                                                         want_gradx=need_x[i])
-            if need_xs[i]:
-                if g_t is None:
-                    if bm is not None:
-                        g_t = be.scale_cols_(be.copy(bm), cs).transpose(-1, -2).contiguous()     # (B, N*, N): 2 diag(gs) B^T, explicit
-                    else:
-                        g_t = zeros(ns, n)
-                _, _, grad_xs[i] = be.kmat_vjp_dense_batch(terms, xs, x, g_t, w=gm, b=alpha, want_gradx=True)
-        del g_t
+        gm, gs, alpha, bm, beta = pre                            # (B, N*), (B, N*), (B, N), (B, N, N*), (B, N)
+        S, grad_x, grad_xs = _through_cross(be, groups, bm, 2.0 * gs if gs is not None else None, alpha, gm, need_x, need_xs)
         # through K: the explicit symmetric cotangent, once
         if bm is not None:
             bs = be.scale_cols_(be.copy(bm), gs)
             G = be.symmetrize_(be.gemm(bs, bm, a_kmajor=True, b_kmajor=True, alpha=-1.0, lower_only=True))
             del bs, bm
         else:
-            G = torch.zeros((nb, n, n), dtype=dt, device=dev)
+            G = torch.zeros((nb, n, n), dtype=x0.dtype, device=x0.device)
         if gm is not None:
-            be.gemm(torch.stack([beta, alpha], dim=-1), torch.stack([alpha, beta], dim=-1), a_kmajor=True, b_kmajor=True, alpha=-0.5,
-                    beta=1.0, out=G)
+            _rank_two_(be, G, alpha, beta)
         for i, grp in enumerate(groups):
             u = grp.inputs[0]
             S_k, _, gx = be.kmat_vjp_dense_batch(grp.terms, u, u, G, want_gradx=need_x[i])
             S[i] = S[i] + S_k
             if need_x[i]:
                 grad_x[i] = grad_x[i] + 2.0 * gx                       # (both arguments of k(x, x) move with x)
-        grads = []
-        for grp, S_g in zip(groups, S):
-            grads += _param_grads(grp.kinds, grp.values, S_g.sum(0), grp.meta)      # (shared by the batch)
         grad_r = beta[..., None] if (beta is not None and ctx.needs_input_grad[0]) else None
         grad_noise = torch.diagonal(G, dim1=-2, dim2=-1).clone() if (ctx.has_noise and ctx.needs_input_grad[1]) else None
         inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
-        return (grad_r, grad_noise, None, None, *inputs, *grads)
+        return (grad_r, grad_noise, None, None, *inputs, *_sum_param_grads(groups, [S_g.sum(0) for S_g in S]))      # (shared by the batch)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -947,8 +891,7 @@ class _BlockPosteriorMarginals(torch.autograd.Function):
             kbar = torch.zeros((n, n), dtype=dt, device=dev)
         if gm is not None:
             be.gemm(alpha[:, None].contiguous(), gm[:, None].contiguous(), a_kmajor=True, b_kmajor=True, alpha=1.0, beta=1.0, out=cbar)
-            be.gemm(torch.stack([beta, alpha], dim=1), torch.stack([alpha, beta], dim=1), a_kmajor=True, b_kmajor=True, alpha=-0.5,
-                    beta=1.0, out=kbar)
+            _rank_two_(be, kbar, alpha, beta)
         grad_us, grads = _walk_blocks(be, ctx.layout, ctx.sizes, ctx.values, ctx.param_meta, us, need_u, kbar, cbar)
         grad_r = beta[:, None] if (beta is not None and ctx.has_r and ctx.needs_input_grad[0]) else None
         grad_noise = torch.diagonal(kbar).clone() if (ctx.has_noise and ctx.needs_input_grad[1]) else None
@@ -1006,10 +949,7 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
         x, z, xs = x.detach(), z.detach(), xs.detach()
         n, m, ns = x.shape[0], z.shape[0], xs.shape[0]
         dt, dev = x.dtype, x.device
-        gm = g_mu.to(dt).contiguous() if (g_mu is not None and w is not None) else None
-        gs = g_s.to(dt).contiguous() if (g_s is not None and va is not None) else None
-        if gs is not None and not bool(torch.any(gs != 0)):           # (one host read) a loss of the mean only
-            gs = None
+        gm, gs = _output_cotangents(g_mu, g_s, w is not None, va is not None, dt)
         need_r, need_noise, need_x, need_z, need_xs = (ctx.needs_input_grad[i] for i in (0, 1, 5, 6, 7))
         if gm is None and gs is None:
             return (None,) * (8 + len(grp.meta))
@@ -1142,8 +1082,7 @@ class _SparsePosteriorMarginals(torch.autograd.Function):
 def sparse_posterior_marginals(kernel, x, z, xs, r, noise_vec, method, run):
     """Differentiable ``(mu, s)`` of ``_SparsePosteriorMarginals``: ``kernel`` a sum of primitives evaluated on ``x`` / ``z`` / ``xs``
     (already behind its input map, so torch carries the map's parameter)."""
-    if method not in ("vfe", "fitc", "dtc"):
-        raise ValueError(f'Invalid approximation method "{method}".')
+    _check_method(method)
     layout, params = _pack_groups([kernel])
     return _SparsePosteriorMarginals.apply(r, noise_vec, run, method == "fitc", layout, x, z, xs, *params)
 
@@ -1219,12 +1158,9 @@ class _PosteriorCovariance(torch.autograd.Function):
                 grad_xs[i] = 2.0 * gx_ss - 2.0 * gx_t
             if need_x[i]:
                 grad_x[i] = _grad_inputs(be, terms, x, gk) - 2.0 * gx_c
-        grads = []
-        for grp, S_g in zip(groups, S):
-            grads += _param_grads(grp.kinds, grp.values, S_g, grp.meta)
         grad_noise = diag_g if (ctx.has_noise and ctx.needs_input_grad[0]) else None
         inputs = [t for pair in zip(grad_x, grad_xs) for t in pair]
-        return (grad_noise, None, None, *inputs, *grads)
+        return (grad_noise, None, None, *inputs, *_sum_param_grads(groups, S))
 
 
 def posterior_covariance(groups, noise_vec, run):

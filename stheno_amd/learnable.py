@@ -291,8 +291,8 @@ def _exact_marginals(pm, pk, x, cache):
     (``_block_marginals``), which answers None itself where it does not apply: pseudo-point posteriors, chained conditioning, batched
     inputs, a block that is no sum of groups of primitives behind input maps, dense noise.  BATCHED inputs -- ``x`` and the observed
     inputs (B, ., D) with one batch size, scalar or (B, N) noise, hyper-parameters shared by the batch -- are the same case through
-    ``autograd._BatchedPosteriorMarginals``; per-batch hyper-parameters were refused by the caller, without a gradient they stay the
-    plain path's."""
+    ``autograd._BatchedPosteriorMarginals`` (the forward and the first stages of the backward are the unbatched function's own code);
+    per-batch hyper-parameters were refused by the caller, without a gradient they stay the plain path's."""
     src = pm if pm is not None else pk
     if not getattr(src, "exact", False):
         return None
@@ -677,7 +677,7 @@ def _process_logpdf(var, r):
 def _scaled_process_logpdf(var, r):
     """One process, unbatched, whose kernel is a sum of groups, each optionally between one function on both sides: ``k(x) = sum_g
     diag(s_g) k_g(m_g(x)) diag(s_g)``, ``s_g = fn_g(x)`` formed HERE in torch -- the graph carries its gradient into the function's
-    parameters -- and handed to ``autograd._GPLogpdfScaled`` as a tensor.  None when nothing behind the density is learnable; every other
+    parameters -- and handed to ``autograd._GPLogpdf`` (``gp_logpdf_scaled``) as a tensor.  None when nothing behind the density is learnable; every other
     call under a learnable quantity is refused, before any launch."""
     what = "this log-density (inputs with a gradient, a batch, several processes, a posterior, dense noise, learnable input maps)"
     noise = var.noise
